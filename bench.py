@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the north-star metric on synthetic wind tunnels (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4] [--dump-outputs DIR]
 
 A "step" is one iteration of the reference's time loop (Simulation::run(), simulation.cpp:63-71:
 inlet density, buffer = dens, Simulation::step()) with frame dumps off.  Fields live in HBM for
@@ -153,6 +153,44 @@ def cpu_baseline(budget_s=10.0):
     return out
 
 
+DUMP_FIELDS = ("dens", "v_x", "v_y", "v_z", "pressure", "divergence")
+DUMP_SAMPLE = 1 << 20        # cells per field: at most 6 fields x 1 Mi x 8 B (fp64) = 48 MiB per dump
+DUMP_SEED = 20240601
+
+
+def dump_outputs(F, sim, outdir, W, H, D, dist=None, world=1, ctl_device=None):
+    """--dump-outputs: the fields the timed steps left on the device, as DIR/<field>.npy in the run's precision.
+    A field that fits is written whole, shape (D+2, H+2, W+2); a larger one as the same fixed, seeded sample of
+    DUMP_SAMPLE cells of the global padded grid (sorted flat indices, duplicates possible), so that N = 1 and N > 1
+    runs of one workload write comparable files.  Under z-slabs each cell is read on the rank that owns its plane
+    (rank 0 also owns plane 0, the last rank plane D+1) and combined by a max over the ranks, the others holding -inf."""
+    import numpy as np
+    n = (D + 2) * (H + 2) * (W + 2)
+    idx = None if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+    dl, zoff = sim.local_depth, sim.z_offset
+    if world > 1:
+        plane = (idx if idx is not None else np.arange(n)) // ((H + 2) * (W + 2))
+        lo = 0 if zoff == 0 else zoff + 1
+        hi = D + 1 if zoff + dl == D else zoff + dl
+        mine = (plane >= lo) & (plane <= hi)
+    for name in DUMP_FIELDS:
+        a = sim.get(F.FIELD_NAMES.index(name))
+        if world == 1:
+            out = a if idx is None else a.reshape(-1)[idx]
+        else:
+            import torch
+            local = (idx if idx is not None else np.arange(n))[mine] - zoff * (H + 2) * (W + 2)
+            vals = np.full(n if idx is None else idx.size, -np.inf)
+            vals[mine] = a.reshape(-1)[local]
+            t = torch.from_numpy(vals).to(ctl_device or "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)          # one owner per sample: its value comes through bit for bit
+            out = t.cpu().numpy().astype(a.dtype)
+            if idx is None:
+                out = out.reshape(D + 2, H + 2, W + 2)
+        if outdir is not None:
+            np.save(os.path.join(outdir, name + ".npy"), out)
+
+
 def slab_parity_check(F, fsdist, dist, rank, world, transport, ctl_device, schedules=None):
     """N>1 only, before the timed run: every rank runs a small tunnel whole on its own GPU, then as its z-slab of
     a world-wide run over the real transport -- once per communication schedule (overlap = auto, 0, 1, 2: "auto" times
@@ -229,7 +267,13 @@ def main():
     ap.add_argument("--comm-cus", default="auto",
                     help="CUs kept free of solver workgroups for the transport's kernels: auto (default: none and 8 are both timed with "
                          "the schedules, the slowest rank's time decides), 0, or N")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fields they computed (%s) as DIR/<field>.npy: whole where a field "
+                         "has at most %d cells, else a fixed seeded sample of that many (see dump_outputs)"
+                    % (", ".join(DUMP_FIELDS), DUMP_SAMPLE))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -338,6 +382,13 @@ def main():
     achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if k_n else 0.0
     total_iters = 3 * tri_n + 2 * pair_n + one_n
     iters_per_sec = total_iters / ((tri_ms + pair_ms + one_ms) * 1e-3) if total_iters else None
+
+    # before the extras below, which overwrite the pressure field
+    if args.dump_outputs:
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+        dump_outputs(F, sim, args.dump_outputs if rank == 0 else None, W, H, D,
+                     dist=dist if world > 1 else None, world=world, ctl_device=ctl_device)
 
     if rank != 0:
         if world > 1:

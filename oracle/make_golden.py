@@ -192,6 +192,7 @@ def main():
     g4_layout()
     g5_stock_run()
     g6_stock_run_console()
+    g7_live_ref_cases()
     manifest = dict(
         compiler=subprocess.check_output(["g++", "--version"]).decode().splitlines()[0],
         flags="-std=c++20 -O2 -fopenmp -fPIC (reference Makefile:5 + -fPIC)",
@@ -237,6 +238,50 @@ def g5_stock_run():
     print("wrote g5_stock_run_digests.json")
 
 
+def g7_live_ref_cases():
+    """The cases tests/test_oracle_vs_ref.py compares the oracle with the live reference on -- six random tunnels
+    (3 steps each) and two voxelizer calls -- with SHA-256 digests of every field the reference computed for them,
+    and the voxelizer seed it drew: where the reference is not built, the test holds the oracle to these.
+    JSON fixture: inputs and digests of outputs only."""
+    import hashlib
+
+    def digest(a):
+        return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+    rng = np.random.default_rng(11)
+    cases = []
+    for _ in range(6):
+        W, H, D = (int(v) for v in rng.integers(3, 22, size=3))
+        acc = int(rng.integers(0, 9))
+        speed = int(rng.integers(1, 40))
+        dt = float(rng.choice([0.05, 0.02, 0.1]))
+        diff = float(rng.choice([2.0e-5, 1.0e-3]))
+        ball = [float(rng.uniform(1, n)) for n in (W, H, D)] + [float(rng.uniform(0.8, 3.0))]
+        c = dict(W=W, H=H, D=D, iter=3, acc=acc, speed=speed, dt=dt, diff=diff, ball=ball, sha256=[])
+        r = O.Reference(W, H, D, iter=3, acc=acc, speed=speed, dt=dt, diff=diff)
+        r.set_mask(ball_mask(W, H, D, *ball))
+        r.add_density(1 + W // 2, 1 + H // 2, 1 + D // 2, 0.7)
+        r.set_velocity(1, 1, 1, 0.5, -0.25, 2.0)
+        for _ in range(3):
+            r.run_one()
+            c["sha256"].append([digest(r.get(f)) for f in range(11)])
+        r.close()
+        cases.append(c)
+    vox = []
+    for stl, kw in (("sphere_24x12.stl", dict(scale=0.9, rot=[15.0, 0.0, 30.0], translate=[1.0, -2.0, 0.5])),
+                    ("plate_ascii.stl", dict(scale=0.4, rot=[0.0, 45.0, 0.0], translate=[-3.0, 0.0, 2.0]))):
+        W, H, D = 28, 20, 24
+        r = O.Reference(W, H, D)
+        seed = r.thread_seed()
+        r.load_stl(os.path.join(OUT, stl), **kw)
+        obs = r.get(O.OBS)
+        vox.append(dict(stl=stl, W=W, H=H, D=D, seed=seed, obs_sha256=digest(obs), obs_cells=int(obs.sum()), **kw))
+        r.close()
+    with open(os.path.join(OUT, "g7_live_ref_digests.json"), "w") as f:
+        json.dump(dict(kind="live_ref_cases", cases=cases, voxelizer=vox), f, indent=1)
+    print("wrote g7_live_ref_digests.json")
+
+
 def g6_stock_run_console():
     """What the reference program prints during that same default run (simulation.cpp:51-53, 73-77, 81-90):
     the `density sum` line is std::reduce over floats in libstdc++'s order, the min / max lines are exact.
@@ -256,10 +301,10 @@ def g6_stock_run_console():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "g6":      # add the console fixture without regenerating the others
+    if len(sys.argv) > 1 and sys.argv[1] in ("g6", "g7"):      # add one fixture without regenerating the others
         if os.environ.get("OMP_NUM_THREADS") != "1":
             sys.exit("run with OMP_NUM_THREADS=1")
         O.build()
-        g6_stock_run_console()
+        g6_stock_run_console() if sys.argv[1] == "g6" else g7_live_ref_cases()
     else:
         main()

@@ -392,7 +392,8 @@ def test_bench_line_contract(tmp_path):
     import sys
     from conftest import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "1", "--warmup", "1",
-                          "--cpu-budget", "1.0"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+                          "--cpu-budget", "1.0", "--dump-outputs", str(tmp_path / "outputs")],
+                         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -412,6 +413,13 @@ def test_bench_line_contract(tmp_path):
     assert r["min_traffic_bytes"] == 12 * 256 ** 3 and d["scaling"] is None and d["comm"] is None
     c = d["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0 and "64x64x64" in c["sample"]
+    # --dump-outputs: the fields of the last timed step, a seeded sample of each (258^3 cells do not fit), 64 MiB at most
+    total = 0
+    for name in ("dens", "v_x", "v_y", "v_z", "pressure", "divergence"):
+        a = np.load(str(tmp_path / "outputs" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (1 << 20,) and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 << 20 and np.load(str(tmp_path / "outputs" / "v_x.npy")).max() > 1.0
 
 
 def test_stock_run_of_the_reference_program_byte_identical(tmp_path):
