@@ -27,8 +27,8 @@
 // Bands overlap by 2(NL-1) rows and z chunks by 2(NL-1) planes.
 //
 // Instantiations (LDS = (NL-1)*2*BY*TW + NL*(BY-2)*RW elements must stay under 160 KB):
-//   fp32 NL=3  rows <= 512 cells   the solver kernel at 256^3 and 512^3: 0.43 ms per pass at 512^3
-//                                  = 0.14 ms per sweep, 12 waves of two rows, 152 VGPRs, no scratch
+//   fp32 NL=3  rows <= 512 cells   the solver kernel at 256^3 and 512^3: 0.37 ms per pass at 512^3
+//                                  = 0.12 ms per sweep, 12 waves of two rows, 150 VGPRs, no scratch
 //   fp32 NL=2  rows 513..1024      config 4: bands of 8 or 9 rows (6 or 7 productive) where the older
 //                                  jacobi_pair_kernel (kernels.hip) only fits 6 (4 productive)
 //   fp64 NL=2  rows <= 512         config 5: bands of 10 rows (8 productive) against 8 (6)
@@ -62,6 +62,22 @@ struct IC {
 template <class T>
 using Vec4 = T __attribute__((ext_vector_type(4)));
 
+// x neighbours across lanes (fp32): lane i takes lane i - 1's (wave_shr:1) or lane i + 1's (wave_shl:1) value; the one
+// lane without a source (lane 0 / lane 63) keeps `edge`, the cell beyond the wave (bound_ctrl off).  Needs all 64 lanes on.
+__device__ __forceinline__ float lane_from_left(float v, float edge)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float lane_from_right(float v, float edge)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
+}
+// a wave-uniform fp32 load through the scalar cache (s_load_dword)
+__device__ __forceinline__ float load_uniform(const char* p)
+{
+    return *(const __attribute__((address_space(4))) float*)p;
+}
+
 template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL>
 __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ src,
                                                                       const T* __restrict__ rhs, T* __restrict__ dst,
@@ -77,6 +93,10 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     // the rhs rows from memory (L2 / MALL hits) -- which frees 61 KB of LDS for 16-row bands, and only the wall-free body
     // (workgroups that touch no wall).  See DESIGN.md section 4 for what it measured.
     constexpr bool RS = (WALLSEL != 2);
+    // XS: three fp32 sweeps on lane-aligned rows take the x neighbours of a lane's four cells from the lanes beside it (DPP
+    // wave shifts) and only the one value beyond either end of the wave from memory (level 1: a scalar load) or the LDS tile
+    // (levels 2, 3: one read of the tile cell `publish` wrote).  Same values as the per-lane reads of the other builds.
+    constexpr bool XS = ALIGNED && NL == 3 && sizeof(T) == 4;
     static_assert(((NL - 1) * 2 * BY * TW + (RS ? NL * (BY - 2) * RW : 0)) * ES <= 160 * 1024, "LDS budget");
     __shared__ T ring[NL - 1][2][BY][TW];                // [level-1][plane & 1][tile row][x + 3]
     __shared__ T rsave[RS ? NL : 1][RS ? BY - 2 : 1][RW];   // thread-private: rhs of the last NL planes
@@ -139,6 +159,9 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     // Per-row byte offsets inside a plane sit in vector registers, the plane pointers in scalar ones --
     // the scalar file is the scarce one here (every spilled scalar costs a v_readlane plus hazard nops).
     const unsigned col0 = lane_on ? (unsigned)x0 : 1u;
+    // levels 2, 3 (XS): the tile column holding lane 0's left neighbour (lanes 0-31) or lane 63's right one (lanes 32-63) --
+    // one ds_read_b32 with two addresses, one per half-wave, in place of a 4-way bank conflict per x neighbour
+    const int xe = wx * 256 + (lane < 32 ? 3 : 260);
     auto clampy = [&](int y) { return (unsigned)min(max(y, 0), H + 1); };
     unsigned oc[RY];                                     // bytes into a plane of T; kill byte index = (element + 3) >> 2
 #pragma unroll
@@ -166,8 +189,14 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         ld4(sp + step_t + oc[RY - 1], ht);
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
-            eL[r] = *reinterpret_cast<const T*>(sp + oc[r] - ES);        // every lane fetches its own x neighbours:
-            eR[r] = *reinterpret_cast<const T*>(sp + oc[r] + 4 * ES);    // no shuffles, no edge lanes
+            if constexpr (XS) {                          // the cells x = 256 wx and 256 wx + 257 of the row (wave-uniform)
+                const char* rowp = sp + (long)(wx * 256 + (int)clampy(y0 + r) * g.sy) * ES;
+                eL[r] = load_uniform(rowp);
+                eR[r] = load_uniform(rowp + 257 * ES);
+            } else {
+                eL[r] = *reinterpret_cast<const T*>(sp + oc[r] - ES);    // every lane fetches its own x neighbours:
+                eR[r] = *reinterpret_cast<const T*>(sp + oc[r] + 4 * ES);    // no shuffles, no edge lanes
+            }
             if (FS_EXP_NT & 1) {
                 const Vec4<T> q = __builtin_nontemporal_load(reinterpret_cast<const Vec4<T>*>(rp + oc[r]));
 #pragma unroll
@@ -249,8 +278,15 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         constexpr int RG = decltype(rgc)::value;
         const int y = y0 + r, t = ty0 + r;
         T(*tl)[TW] = ring[RG][P & 1];
-        const T left = tl[t][x0 + 2];                    // neighbour lane's / wave's cell, or the ghost column x = 0
-        const T right = tl[t][x0 + 7];                   // ... or the ghost column x = W+1
+        T left, right;
+        if constexpr (XS) {                              // lane 0's left / lane 63's right: one address per half-wave
+            const T edge = tl[t][xe];
+            left = lane_from_left(s1[r][3], edge);
+            right = lane_from_right(s1[r][0], edge);
+        } else {
+            left = tl[t][x0 + 2];                        // neighbour lane's / wave's cell, or the ghost column x = 0
+            right = tl[t][x0 + 7];                       // ... or the ghost column x = W+1
+        }
         T ym[4], yp[4];
         if (r > 0 && (!WALLS || y != 1)) {
 #pragma unroll
@@ -332,7 +368,12 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
                         ym[e] = (r > 0) ? L0[I1][r > 0 ? r - 1 : 0][e] : hb[e];
                         yp[e] = (r < RY - 1) ? L0[I1][r < RY - 1 ? r + 1 : r][e] : ht[e];
                     }
-                    relax4(L0[I1][r], eL[r], eR[r], ym, yp, L0[I0][r], L0[I2][r], rcur[r], u);
+                    T left = eL[r], right = eR[r];
+                    if constexpr (XS) {
+                        left = lane_from_left(L0[I1][r][3], eL[r]);
+                        right = lane_from_right(L0[I1][r][0], eR[r]);
+                    }
+                    relax4(L0[I1][r], left, right, ym, yp, L0[I0][r], L0[I2][r], rcur[r], u);
                     settle4(u, flc[r], L1[I2][r]);
                     publish(IC<0>{}, zl, r, u, L1[I2][r]);
                     if (RS && t >= 1 && t <= BY - 2) lds_set(&rs_put[t - 1][xl], rcur[r]);
