@@ -16,6 +16,7 @@ DENS, VX, VY, VZ, OBS, PRESSURE, DIVERGENCE, VX_PREV, VY_PREV, VZ_PREV, BUFFER =
 FIELD_NAMES = ["dens", "v_x", "v_y", "v_z", "obs", "pressure", "divergence",
                "v_x_prev", "v_y_prev", "v_z_prev", "buffer"]
 COMM_ID_BYTES = 128
+FORCE_LOG_COLS = 9      # FS_FORCE_LOG_COLS: step, S1x, S1y, S1z, S2x, S2y, S2z, faces, frontal
 
 
 class FluidsimError(RuntimeError):
@@ -63,6 +64,8 @@ _SIGNATURES = {
     "fs_obstacle_surface": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_obstacle_surface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_surface_case_table": (C.c_int, [C.c_int, C.c_void_p]),
+    "fs_obstacle_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fs_force_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

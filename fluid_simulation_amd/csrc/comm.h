@@ -616,6 +616,56 @@ struct Comm {
         FS_NCCL(api->AllReduce(d3 + 2, d3 + 2, 1, ncclDouble, ncclMax, comm, st));
         return 0;
     }
+
+    // All-gather of `bytes` of HOST memory per rank: `all` receives rank r's `mine` at r * bytes on every rank.
+    // Synchronous (the obstacle-force queries, which return host results anyway).  RCCL: through device buffers;
+    // FSSHM / FSIPC: through a POSIX shared-memory segment of its own, paced by the transport's host barrier.
+    int allgather_host(hipStream_t st, const void* mine, void* all, size_t bytes, const GridDesc& g, int Dglobal)
+    {
+        if (!active()) { memcpy(all, mine, bytes); return 0; }
+        if (null_transport) { err = "the FSNULL transport moves no data"; return -1; }
+        FS_HIPC(hipStreamSynchronize(st));
+        if (shm || ipc) {
+            if (shm && shm_ready(g, Dglobal)) return -1;
+            if (ipc && ipc->open(&err)) return -1;
+            auto bar = [&]() { if (shm) shm->barrier(); else ipc->barrier(); };
+            const std::string seg = (shm ? shm->name : ipc->name) + "_ag" + std::to_string(++ag_calls);
+            const size_t total = bytes * (size_t)nranks;
+            int fd = -1;
+            if (rank == 0) {
+                shm_unlink(seg.c_str());
+                fd = shm_open(seg.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
+                if (fd >= 0 && ftruncate(fd, (off_t)total) != 0) { close(fd); fd = -1; }
+            }
+            bar();                                       // the segment exists (or rank 0 failed to make it)
+            if (rank != 0) fd = shm_open(seg.c_str(), O_RDWR, 0600);
+            void* m = fd >= 0 ? mmap(nullptr, total, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : MAP_FAILED;
+            if (fd >= 0) close(fd);
+            char* base = m == MAP_FAILED ? nullptr : static_cast<char*>(m);
+            if (base) memcpy(base + (size_t)rank * bytes, mine, bytes);
+            bar();                                       // every rank has written its part
+            if (base) memcpy(all, base, total);
+            bar();                                       // every rank has read everything: the segment goes
+            if (base) munmap(base, total);
+            if (rank == 0) shm_unlink(seg.c_str());
+            if (!base) { err = "shared segment " + seg + " for the force records could not be mapped"; return -1; }
+            return 0;
+        }
+        char* d = nullptr;
+        FS_HIPC(hipMalloc((void**)&d, bytes * ((size_t)nranks + 1)));
+        char* send = d + bytes * (size_t)nranks;
+        int rc = 0;
+        do {
+            if (hipMemcpyAsync(send, mine, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { err = "force records upload"; rc = -1; break; }
+            ncclResult_t r = api->AllGather(send, d, bytes, ncclInt8, comm, st);
+            if (r != ncclSuccess) { err = api->GetErrorString(r); rc = -1; break; }
+            if (hipMemcpyAsync(all, d, bytes * (size_t)nranks, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) { err = "force records download"; rc = -1; break; }
+        } while (0);
+        hipFree(d);
+        return rc;
+    }
+    unsigned long ag_calls = 0;
 #undef FS_NCCL
 #undef FS_HIPC
 };

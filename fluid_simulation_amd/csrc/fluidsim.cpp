@@ -15,6 +15,7 @@
 #include "streamlines.h"
 #include "surface.h"
 #include "multigrid.h"
+#include "forces.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -50,8 +51,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -88,6 +89,8 @@ struct EngineBase {
     virtual int obstacle_surface() = 0;
     virtual int reference_order_sum(int which, double* out) = 0;
     virtual int multigrid_levels() const = 0;
+    virtual int obstacle_force(double* out5, double* per_plane) = 0;
+    virtual int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
 };
 
 struct fs_sim {
@@ -144,6 +147,9 @@ struct fs_sim {
     FILE* dump_fp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool dump_open = false, dump_warned = false, in_run = false;
     long step_no = 0;
+    long steps_total = 0;        // steps this handle has completed (the "step" column of fs_force_log)
+    int force_log = 0;           // "force_log": steps the per-step force log keeps, 0 = off
+    long force_log_gen = 0;      // bumped by every fs_set_option("force_log"): the ring is reallocated and cleared
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -254,6 +260,13 @@ struct Engine : EngineBase {
     double vzmax_prev = -1.0;           // max |v_z| at the end of the previous step (= v_z_prev of this one), -1 = unknown
     double vzmax_end = -1.0;            // the same for the step that is running
     bool in_step = false;               // inside step(): the data flow between the solver's calls is known
+    // pressure force (forces.h): the per-step log is a device ring of force_cap steps x 2 projections x g.D plane records
+    double* force_ring = nullptr;
+    double* force_scratch = nullptr;    // fs_obstacle_force: one record per local plane
+    int force_cap = 0;
+    long force_gen = -1;                // S->force_log_gen the ring was allocated for
+    long force_logged = 0;              // steps logged since the ring was cleared or last drained
+    std::vector<long> force_step;       // step number held by each ring slot
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -371,6 +384,8 @@ struct Engine : EngineBase {
         if (dense) hipFree(dense);
         if (red) hipFree(red);
         if (coltab) hipFree(coltab);
+        if (force_ring) hipFree(force_ring);
+        if (force_scratch) hipFree(force_scratch);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1074,11 +1089,17 @@ struct Engine : EngineBase {
             fs::launch_gradient<T>(S->stream, S->tune, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
                                    arr[slot[FS_VZ]], flags, h, (T)2 * h);
         }
+        const int proj = in_step ? projections_this_step++ : -1;   // which of the step's two projections this is
+        if (proj >= 0 && proj < 2 && force_cap > 0) {
+            // "force_log": this projection's plane records go straight into the step's ring slot (no host sync)
+            ScopedSpan sp(S, FAM_FORCES);
+            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_slot(force_logged % force_cap, proj));
+        }
         // the next consumer of v's z-halo planes is the divergence of the second projection
         // (v_z[z+-1]) and the advection back-trace; refresh them now.
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = halo(arr[slot[f]]))) return rc;
-        if (in_step && S->comm.active() && (rc = post_vzmax(projections_this_step++))) return rc;
+        if (proj >= 0 && S->comm.active() && (rc = post_vzmax(proj))) return rc;
         return FS_OK;
     }
 
@@ -1279,6 +1300,7 @@ struct Engine : EngineBase {
         } scope(this);
         int rc = ensure_flags();
         if (rc) return rc;
+        if ((rc = ensure_force_ring())) return rc;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
@@ -1343,6 +1365,8 @@ struct Engine : EngineBase {
         if ((rc = advect(0, FS_DENS, FS_BUFFER))) return rc;   // :136
         slack_check();
         S->step_no++;
+        S->steps_total++;
+        if (force_cap > 0) force_step[(size_t)(force_logged++ % force_cap)] = S->steps_total;
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -1737,6 +1761,113 @@ struct Engine : EngineBase {
         *ms = (double)t / reps;
         return FS_OK;
     }
+
+    // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
+    // ring slot k, projection j: g.D plane records
+    double* force_slot(long k, int j) const { return force_ring + ((size_t)k * 2 + (size_t)j) * plane_doubles(); }
+    size_t plane_doubles() const { return (size_t)fs::FORCE_REC * (size_t)g.D; }
+
+    // (re)allocate and clear the ring after fs_set_option("force_log")
+    int ensure_force_ring()
+    {
+        if (force_gen == S->force_log_gen) return FS_OK;
+        if (force_ring) HIP_TRY(hipFree(force_ring));
+        force_ring = nullptr;
+        force_cap = 0;
+        force_logged = 0;
+        force_step.clear();
+        force_gen = S->force_log_gen;
+        if (S->force_log <= 0) return FS_OK;
+        const size_t bytes = (size_t)S->force_log * 2 * plane_doubles() * sizeof(double);
+        HIP_TRY(hipMalloc((void**)&force_ring, bytes));
+        HIP_TRY(hipMemsetAsync(force_ring, 0, bytes, S->stream));
+        force_cap = S->force_log;
+        force_step.assign((size_t)force_cap, 0);
+        return FS_OK;
+    }
+
+    // Every rank's plane records (`mine`: `blocks` blocks of g.D records each) -> `all`: rank r's blocks at r * mine.size()
+    // (a slab's planes follow the lower slabs' planes).  Collective on slab handles; the host holds everything afterwards.
+    int gather_force_records(const std::vector<double>& mine, std::vector<double>& all)
+    {
+        if (!S->comm.active()) { all = mine; return FS_OK; }
+        if (S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
+        all.assign(mine.size() * (size_t)S->comm.nranks, 0.0);
+        if (mine.empty()) return FS_OK;
+        return comm_op([&](hipStream_t st) { return S->comm.allgather_host(st, mine.data(), all.data(), mine.size() * sizeof(double), g, S->D); },
+                       "gather of the force records");
+    }
+
+    // Sum of the records of global planes 1..D in increasing z, in fp64: `rec(r, zl)` = record of local plane zl of rank r.
+    // Single-GPU and slab handles add the same numbers in the same order.
+    template <class F>
+    void combine_planes(F&& rec, double* out5) const
+    {
+        const int nr = S->comm.active() ? S->comm.nranks : 1;
+        for (int k = 0; k < fs::FORCE_REC; ++k) out5[k] = 0.0;
+        for (int r = 0; r < nr; ++r)
+            for (int zl = 0; zl < g.D; ++zl) {
+                const double* q = rec(r, zl);
+                for (int k = 0; k < fs::FORCE_REC; ++k) out5[k] += q[k];
+            }
+    }
+
+    int obstacle_force(double* out5, double* per_plane) override
+    {
+        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
+        int rc = ensure_flags();
+        if (rc) return rc;
+        const size_t n = plane_doubles();
+        if (!force_scratch) HIP_TRY(hipMalloc((void**)&force_scratch, n * sizeof(double)));
+        {
+            ScopedSpan sp(S, FAM_FORCES);
+            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_scratch);
+        }
+        std::vector<double> mine(n), all;
+        HIP_TRY(hipMemcpyAsync(mine.data(), force_scratch, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        if ((rc = gather_force_records(mine, all))) return rc;
+        combine_planes([&](int r, int zl) { return &all[(size_t)r * n + (size_t)zl * fs::FORCE_REC]; }, out5);
+        if (per_plane) memcpy(per_plane, all.data(), all.size() * sizeof(double));
+        return FS_OK;
+    }
+
+    int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        int rc = ensure_force_ring();
+        if (rc) return rc;
+        const long n = force_cap > 0 ? std::min<long>(force_logged, force_cap) : 0;
+        if (n_rows) *n_rows = n;
+        if (n_dropped) *n_dropped = force_logged - n;
+        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
+        if (max_rows < n) return fail(FS_EINVAL, "fs_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
+        const size_t per = 2 * plane_doubles();   // one step: both projections
+        const long first = force_logged - n;
+        std::vector<double> mine((size_t)n * per), all;
+        for (long i = 0; i < n; ++i)
+            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, force_slot((first + i) % force_cap, 0), per * sizeof(double),
+                                   hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        if ((rc = gather_force_records(mine, all))) return rc;
+        const size_t blob = mine.size();
+        for (long i = 0; i < n; ++i) {
+            double s[2][fs::FORCE_REC];
+            for (int j = 0; j < 2; ++j)
+                combine_planes([&](int r, int zl) {
+                    return &all[(size_t)r * blob + (size_t)i * per + (size_t)j * (per / 2) + (size_t)zl * fs::FORCE_REC]; }, s[j]);
+            double* o = rows + (size_t)i * FS_FORCE_LOG_COLS;
+            o[0] = (double)force_step[(size_t)((first + i) % force_cap)];
+            for (int k = 0; k < 3; ++k) {
+                o[1 + k] = s[0][k];
+                o[4 + k] = s[1][k];
+            }
+            o[7] = s[1][3];
+            o[8] = s[1][4];
+        }
+        force_logged = 0;                                // drained
+        return FS_OK;
+    }
 };
 
 int ensure_engine(fs_sim* s)
@@ -1872,6 +2003,12 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         s->profile = (v != "0");
     } else if (k == "elide_dead_density_solve") {
         s->elide_dead = (v != "0");
+    } else if (k == "force_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "force_log: steps kept, 0 (off) .. 1048576");
+        s->force_log = (int)n;
+        s->force_log_gen++;
     } else if (k == "dump_async") {
         s->dump_async = (v != "0");
     } else if (k == "fuse_advect") {
@@ -2239,6 +2376,19 @@ int fs_surface_case_table(int config, int* edges)
     int n = fs::surface_case(config, edges);
     if (n < 0) return fail(FS_EINVAL, "bad cube configuration %d (0..255)", config);
     return n;
+}
+
+int fs_obstacle_force(fs_sim* s, double out[5], double* per_plane)
+{
+    ENGINE_OR_RETURN(s);
+    if (!out) return fail(FS_EINVAL, "null output");
+    return s->eng->obstacle_force(out, per_plane);
+}
+
+int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->force_log_fetch(rows, max_rows, n_rows, n_dropped);
 }
 
 int fs_comm_unique_id(void* id_out)

@@ -14,6 +14,28 @@ import numpy as np
 from . import _lib
 from ._lib import FluidsimError, check  # noqa: F401
 
+# Columns of Simulation.force_log(): fs_force_log's raw columns, then F and C of the step (S = S1 + S2)
+FORCE_LOG_DTYPE = np.dtype([("step", np.int64), ("s1x", np.float64), ("s1y", np.float64), ("s1z", np.float64),
+                            ("s2x", np.float64), ("s2y", np.float64), ("s2z", np.float64), ("faces", np.int64),
+                            ("frontal", np.int64), ("fx", np.float64), ("fy", np.float64), ("fz", np.float64),
+                            ("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
+
+
+def pressure_force(s, frontal, dt, speed, width, height, depth):
+    """Force and force coefficients of raw pressure sums (include/fluidsim.h, "pressure force on the obstacles"):
+    F = S * h^2 / dt with h = 1 / cbrt(width * height * depth), and C = 2 * S / (dt * speed^2 * N_front), N_front =
+    `frontal` (NaN where dt * speed^2 * N_front is 0).  `s` has shape (..., 3), `frontal` the leading shape; returns
+    (F, C), both (..., 3), in fp64.  For a row of the force log, S = S1 + S2 (a step applies both projections)."""
+    s = np.asarray(s, dtype=np.float64)
+    n = np.asarray(frontal, dtype=np.float64)[..., None]
+    h = 1.0 / np.cbrt(float(int(width) * int(height) * int(depth)))
+    dt = float(dt)
+    force = s * (h * h) / dt
+    denom = dt * (float(speed) * float(speed)) * n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        coeff = np.where(denom != 0.0, 2.0 * s / np.where(denom != 0.0, denom, 1.0), np.nan)
+    return force, coeff
+
 
 class Simulation:
     """Simulation(w, h, d, iter, speed=30, dt=0.05, diff=2.0e-5, visc=1.5e-5, acc=15)
@@ -185,6 +207,38 @@ class Simulation:
         faces = np.zeros((nt.value, 3), dtype=np.int32)
         check(self._L.fs_obstacle_surface_fetch(self._h, verts.ctypes.data, faces.ctypes.data))
         return verts, faces
+
+    def obstacle_force(self, per_plane=False):
+        """Pressure force on the obstacles from FS_PRESSURE as it is now (fs_obstacle_force; collective on z-slabs):
+        a dict with the raw sums "S" (3,), the counts "faces" and "frontal" (N_front), "force" and "coeff" (see
+        pressure_force), and with per_plane=True "per_plane", (depth, 5) records {Sx, Sy, Sz, faces, frontal} of the
+        global planes 1..depth."""
+        out = np.zeros(5, dtype=np.float64)
+        pp = np.zeros((self.depth, 5), dtype=np.float64) if per_plane else None
+        check(self._L.fs_obstacle_force(self._h, out.ctypes.data, None if pp is None else pp.ctypes.data))
+        force, coeff = pressure_force(out[:3], out[4], self.dt, self.speed, self.width, self.height, self.depth)
+        r = {"S": out[:3].copy(), "faces": int(out[3]), "frontal": int(out[4]), "force": force, "coeff": coeff}
+        if per_plane:
+            r["per_plane"] = pp
+        return r
+
+    def force_log(self, with_dropped=False):
+        """Drains the per-step force log (option force_log=N; fs_force_log, collective on z-slabs): one row per
+        retained step, oldest first, as a FORCE_LOG_DTYPE structured array.  with_dropped=True returns
+        (rows, number of logged steps the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_force_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        raw = np.zeros((n.value, _lib.FORCE_LOG_COLS), dtype=np.float64)
+        check(self._L.fs_force_log(self._h, raw.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        rows = np.zeros(n.value, dtype=FORCE_LOG_DTYPE)
+        for k, name in enumerate(FORCE_LOG_DTYPE.names[:_lib.FORCE_LOG_COLS]):
+            rows[name] = raw[:, k]
+        force, coeff = pressure_force(raw[:, 1:4] + raw[:, 4:7], raw[:, 8], self.dt, self.speed, self.width,
+                                      self.height, self.depth)
+        for k, a in enumerate("xyz"):
+            rows["f" + a] = force[:, k]
+            rows["c" + a] = coeff[:, k]
+        return (rows, dropped.value) if with_dropped else rows
 
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()

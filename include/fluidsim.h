@@ -102,6 +102,9 @@ int fs_destroy(fs_sim* s);
  *   "profile"     "1" brackets each kernel family with HIP events (see fs_get_timing)
  *   "elide_dead_density_solve" "1" skips diffuse(0,dens,buffer) whose result the next
  *                 advect overwrites (simulation.cpp:135-136); default "0" = do it
+ *   "force_log"   N >= 0: keep the obstacle pressure forces of the last N steps (fs_force_log); 0 (default) =
+ *                 off, and the step launches nothing for it.  Setting it (re)allocates and clears the log.
+ *                 May be changed at any time.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -203,7 +206,7 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "sweep_pair" (two iterations per launch) "sweep_triple" (three iterations per launch)
  * "divergence" "gradient" "advect" "bounds" "misc" "comm" (z-slab exchanges and gathers)
  * "multigrid" (the coarse-level work of solver "mg"; its level-0 smoothing passes count as
- * "sweep_pair").  Events are recorded on the handle's own stream. */
+ * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -248,6 +251,39 @@ int fs_obstacle_surface_fetch(fs_sim* s, float* vertices, int* triangles);
  * edges[24] and returns the triangle count (0..8); edge id = 4 * axis + 2 * (offset on the higher
  * other axis) + (offset on the lower other axis).  Needs neither a handle nor a GPU. */
 int fs_surface_case_table(int config, int* edges);
+
+/* ---- pressure force on the obstacles (beyond the reference: it has no force output, no file:line counterpart) ----
+ *
+ * A face is BLOCKED where the projection's gradient (simulation.cpp:328-356) takes its one-sided form across it: it
+ * lies between a cell c with obs(c) != 1 (a cell the gradient updates) and a 6-neighbour n inside the interior range
+ * (1..w, 1..h, 1..d) with obs(n) != 0.  Tunnel walls and ghost cells are never bodies.  For the pressure field p,
+ *     S = sum over blocked faces of p(c) * e,   e = unit vector from c toward n
+ * (pressure pushes into the body; the face pressure is the fluid cell's own p, the zero-gradient treatment the
+ * one-sided stencil gives solids).  In the reference p solves lap(p) = div(v) and then v -= grad(p), so
+ * p = dt * P / rho and, with h = 1 / cbrt(w * h * d) (simulation.cpp:295), the force per unit density is
+ *     F = S * h^2 / dt
+ * and the force coefficients are
+ *     C = 2 * S / (dt * speed^2 * N_front)
+ * (h^2 cancels), N_front = the number of (y, z) rows that hold at least one solid (obs == 1) cell, the frontal area
+ * in cells.  This is the PRESSURE force only: the reference diffuses the velocities with `diff`
+ * (simulation.cpp:282) and models no viscous stress.  Sums run in fp64 over the z-planes in increasing z; a z-slab
+ * run gives the single-GPU bits.
+ *
+ * fs_obstacle_force: S of the pressure in FS_PRESSURE now.  out = {Sx, Sy, Sz, blocked faces, N_front}; per_plane
+ * (may be NULL) receives the same five numbers for each global z-plane 1..d (5 * d doubles), the spanwise load
+ * distribution.  On z-slab handles every rank calls it and every rank gets the global result.
+ *
+ * fs_force_log (option "force_log" = N): inside fs_step, S is taken right after EACH of the step's two projections
+ * (simulation.cpp:120 and :130), S1 and S2, into a device ring without a host synchronisation; a step applies both
+ * impulses, so its force is F = (S1 + S2) * h^2 / dt.  The call drains the log: rows[FS_FORCE_LOG_COLS * i + ...] =
+ * {step, S1x, S1y, S1z, S2x, S2y, S2z, blocked faces, N_front}, oldest first, one per retained step (step = how many
+ * steps the handle had completed with that one); *n_dropped = logged steps the ring overwrote since the last drain.
+ * rows = NULL only reports *n_rows / *n_dropped and drains nothing; max_rows < *n_rows is FS_EINVAL.  Collective on
+ * z-slab handles (every rank calls it with the same arguments).  Both need a transport that moves data (FSNULL: FS_EINVAL).
+ */
+#define FS_FORCE_LOG_COLS 9
+int fs_obstacle_force(fs_sim* s, double out[5], double* per_plane);
+int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

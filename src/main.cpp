@@ -19,8 +19,12 @@
 //   --resume DIR   start from the last frame of DIR/{data,obs,v_x,v_y,v_z}.bin (a dumped frame is
 //                  a complete state: everything else is rebuilt every step)
 //   --json         append one machine-readable timing line to stdout
+//   --forces FILE  log the obstacle pressure force of every step (option "force_log") and write it to FILE as CSV:
+//                  fs_force_log's columns, then F = (S1 + S2) h^2 / dt and C = 2 (S1 + S2) / (dt speed^2 N_front)
+//                  (include/fluidsim.h)
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -80,6 +84,34 @@ int resume_field(fs_sim* sim, const std::string& dir, const char* name, int whic
     return 0;
 }
 
+// the per-step force log of the run -> CSV (the columns of Simulation.force_log() in the Python package)
+int write_forces(fs_sim* sim, const char* path, int w, int h, int d, float dt, int speed)
+{
+    long n = 0, dropped = 0;
+    if (fs_force_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * FS_FORCE_LOG_COLS);
+    if (fs_force_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step,s1x,s1y,s1z,s2x,s2y,s2z,faces,frontal,fx,fy,fz,cx,cy,cz\n");
+    const double hh = 1.0 / std::cbrt((double)((long)w * h * d)), t = (double)dt, sp = (double)speed;
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * FS_FORCE_LOG_COLS];
+        double f[3], c[3];
+        const double denom = t * (sp * sp) * r[8];
+        for (int k = 0; k < 3; ++k) {
+            const double s = r[1 + k] + r[4 + k];
+            f[k] = s * (hh * hh) / t;
+            c[k] = denom != 0.0 ? 2.0 * s / denom : NAN;
+        }
+        fprintf(fp, "%ld,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%ld,%ld,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", (long)r[0], r[1], r[2],
+                r[3], r[4], r[5], r[6], (long)r[7], (long)r[8], f[0], f[1], f[2], c[0], c[1], c[2]);
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "simulation.out: %s: %s\n", what, fs_last_error());
@@ -97,7 +129,7 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir;
+    std::string resume_dir, forces_path;
     std::vector<std::pair<std::string, std::string>> options;
 
     auto apply = [&](const std::string& key, const char* val) -> bool {
@@ -116,10 +148,11 @@ int main(int argc, char** argv)
         if (key == "mg-cycles") { options.push_back({ "mg_cycles", val }); return true; }
         if (key == "seed") { options.push_back({ "voxel_seed", val }); return true; }
         if (key == "resume") { resume_dir = val; return true; }
+        if (key == "forces") { forces_path = val; return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
-                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume" };
+                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -145,6 +178,7 @@ int main(int argc, char** argv)
 
     fs_sim* sim = fs_create(width, height, depth, iter, speed, dt, diff, visc, acc);   // simulation.cpp:438
     if (!sim) return die("fs_create");
+    if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
     for (const Stl& s : stls) {
@@ -161,6 +195,7 @@ int main(int argc, char** argv)
     if (fs_run(sim)) return die("fs_run");                              // simulation.cpp:448
     if (fs_sync(sim)) return die("fs_sync");
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
     if (json)
         printf("{\"grid\": [%d, %d, %d], \"steps\": %d, \"acc\": %d, \"seconds\": %.6f, \"cells_steps_per_sec\": %.6g}\n",
                width, height, depth, iter, acc, secs, (double)width * height * depth * iter / secs);
