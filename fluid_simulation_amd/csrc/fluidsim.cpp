@@ -228,6 +228,7 @@ struct Engine : EngineBase {
     bool held[NPOOL] = {false};         // temporaries owned by a running solve
     uint8_t* flags = nullptr;           // shifted like the fields
     uint8_t* kill = nullptr;            // one byte per four cells for the sweeps; byte (cell+3)/4
+    fs::MaskPlan maskplan;              // single GPU, fp32: which rows are free of kill bytes (the three-sweep kernel's mask-free body)
     bool flags_dirty = true;
     bool halos_dirty = false;           // a host-side mutation may have changed a slab boundary plane
     void* dense = nullptr;              // device staging of fs_get_field / fs_set_field (dense local slab), on demand
@@ -453,8 +454,27 @@ struct Engine : EngineBase {
         ScopedSpan sp(S, FAM_MISC);
         fs::launch_build_flags<T>(S->stream, g, sc, arr[slot[FS_OBS]], flags);
         fs::launch_build_kill(S->stream, g, sc, flags, kill);
+        if ((rc = build_clean())) return rc;
         flags_dirty = false;
         mg_current = false;
+        return FS_OK;
+    }
+
+    // The clean table and its host copy (one small device-to-host copy per mask change); the balanced chunk tables made from the
+    // old one are dropped
+    int build_clean()
+    {
+        maskplan.clear_chunks();
+        if (!std::is_same<T, float>::value || S->comm.active() || g.W > 512) return FS_OK;   // where the three-sweep kernel is fp32 x 3
+        const int words = (g.H + 2 + 31) / 32 + 1;
+        if (words > 64) return FS_OK;                    // (rows beyond what build_clean_kernel's LDS holds: no mask-free body)
+        const size_t n = (size_t)(g.D + 2) * words;
+        if (!maskplan.tab) HIP_TRY(hipMalloc((void**)&maskplan.tab, n * sizeof(uint32_t)));
+        maskplan.words = words;
+        maskplan.host.resize(n);
+        fs::launch_build_clean(S->stream, g, kill, maskplan.tab, words);
+        HIP_TRY(hipMemcpyAsync(maskplan.host.data(), maskplan.tab, n * sizeof(uint32_t), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
         return FS_OK;
     }
 
@@ -497,7 +517,8 @@ struct Engine : EngineBase {
     {
         const T omega = rb ? rb_omega : (T)0;
         if (levels == 3)
-            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, triple_alt, second, push);
+            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, triple_alt, second, push,
+                                       &maskplan);
         else if (levels == 2 && !rb && pair_shape >= FUSED2)
             fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 2, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, pair_shape - FUSED2, second, push);
         else if (levels == 2)
@@ -2059,6 +2080,18 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         else if (v == "auto") s->tune.wall_free = 1;
         else if (v == "1") s->tune.wall_free = 2;
         else return fail(FS_EINVAL, "wall_free: 0 | auto | 1");
+    } else if (k == "mask_free") {
+        if (v == "0") s->tune.mask_free = 0;
+        else if (v == "auto") s->tune.mask_free = 1;
+        else if (v == "1") s->tune.mask_free = 2;
+        else return fail(FS_EINVAL, "mask_free: 0 | auto | 1");
+    } else if (k == "chunk_cost") {
+        // per-iteration costs of the general, wall-free and mask-free bodies the z chunks are balanced by; "0" = equal chunks
+        fs::ChunkCost c;
+        if (v != "0" && (sscanf(value, "%d,%d,%d", &c.general, &c.wall_free, &c.mask_free) != 3 || c.general <= 0 ||
+                         c.wall_free <= 0 || c.mask_free <= 0 || c.general > 1000000 || c.wall_free > 1000000 || c.mask_free > 1000000))
+            return fail(FS_EINVAL, "chunk_cost: 0 | general,wall_free,mask_free (positive integers)");
+        s->tune.chunk_cost = c;
     } else if (k == "pair_zc") {
         s->tune.pair_zc = atoi(value);
     } else if (k == "pair_shape") {

@@ -1,6 +1,7 @@
 // kernels.h -- launch interface between the host driver (fluidsim.cpp) and the gfx950
 // kernels (kernels.hip, voxelize.hip).  Internal to libfluidsim.so.
 #pragma once
+#include "chunk_plan.h"
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
@@ -60,7 +61,31 @@ struct SweepTune {
     int wall_free = 1;        // three-sweep kernel, whole-domain aligned grids: plane iterations that touch no y / z wall run a wall-free
                               // second body -- 0 never, 1 (default) and 2 always (round 3: selected per group of three iterations)
     int two_kind = 0;         // which two-sweep kernel: 0 = timed choice, 1 = jacobi_pair_kernel only, 2 = jacobi_fused_kernel<NL=2> only
+    int mask_free = 1;        // three-sweep kernel where it runs the wall-free body (single GPU): groups of plane iterations whose rows
+                              // hold no kill byte run a third, mask-free body -- 0 never, 1 (default) on rows of 512 cells (two waves; it
+                              // is slower on 256-cell rows), 2 always
+    ChunkCost chunk_cost;     // z chunks of that build balanced per band by this cost model (chunk_plan.h); 0,0,0 (default) = equal
+                              // chunks, which measured faster
 };
+
+// Single GPU: the clean table of the mask-free three-sweep build (chunk_plan.h), rebuilt with the kill bytes, and the
+// per-workgroup tables derived from it on the host (one per launch shape, made at its first launch after a mask change).
+struct MaskPlan {
+    uint32_t* tab = nullptr;             // device staging of `host`, (D + 2) planes x `words`
+    int words = 0;                       // per plane: (H + 2 + 31) / 32 rows' words + one pad word
+    std::vector<uint32_t> host;          // copy of `tab`
+    struct Chunks {
+        int BY, nbands, nzc, zc_len;     // zc_len: equal chunks of that length, 0 = balanced by `cost`
+        ChunkCost cost;
+        std::vector<int> plan;           // chunk_plan.h: mask_free_plan
+        int* dev;
+    };
+    std::vector<Chunks> chunks;
+    void clear_chunks();                 // the mask changed
+    void release();
+    ~MaskPlan() { release(); }
+};
+void launch_build_clean(hipStream_t st, const GridDesc& g, const uint8_t* kill, uint32_t* tab, int words);
 
 // z-slab "push" exchange (FSIPC transport, csrc/ipc.h): a solver pass stores the planes its neighbours need next straight
 // into THEIR halo planes (peer-mapped arrays) beside its own -- no boundary launch, no copy, no second stream.
@@ -100,7 +125,8 @@ int fused_shape_count(const GridDesc& g, int levels);
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
-                         int second_first = -1, const PeerPush* push = nullptr);
+                         int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr);
+// mp: the single-GPU clean table (fp32 three sweeps only; nullptr = no mask-free body)
 // number of workgroup shapes (0 .. count-1) worth timing for this grid; results do not depend on the shape
 template <class T>
 int pair_shape_count(const GridDesc& g);

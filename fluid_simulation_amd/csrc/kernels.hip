@@ -1728,6 +1728,29 @@ void launch_build_kill(hipStream_t st, const GridDesc& g, const SlabCtx& sc, con
                        flags, kill, zlo);
 }
 
+// Clean table of the mask-free three-sweep build (chunk_plan.h): one workgroup per plane 0..D+1, one wave per row at a time;
+// bit y of the plane's words is set iff no kill byte of row y has a bit in either nibble.  Kill bytes outside rows 1..H,
+// planes 1..D are the zeros the array was cleared to.
+__global__ void build_clean_kernel(GridDesc g, const uint8_t* __restrict__ kill, uint32_t* __restrict__ tab, int words)
+{
+    __shared__ uint32_t w[64];
+    const int z = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < words; i += blockDim.x) w[i] = 0u;
+    __syncthreads();
+    const int ng = (g.W + 3) / 4;
+    for (int y = wave; y <= g.H + 1; y += blockDim.x / 64) {
+        bool dirty = false;
+        for (int gx = lane; gx < ng; gx += 64) dirty |= kill[(cell(g, 1 + 4 * gx, y, z) + 3) >> 2] != 0;
+        if (__builtin_amdgcn_ballot_w64(dirty) == 0 && lane == 0) atomicOr(&w[y >> 5], 1u << (y & 31));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < words; i += blockDim.x) tab[(long)z * words + i] = w[i];
+}
+void launch_build_clean(hipStream_t st, const GridDesc& g, const uint8_t* kill, uint32_t* tab, int words)
+{
+    hipLaunchKernelGGL(build_clean_kernel, dim3(g.D + 2), dim3(256), 0, st, g, kill, tab, words);
+}
+
 // =====================================================================================
 // Inlet forcing: velocity (speed,0,0) on the x=1 face (simulation.cpp:103-105) and
 // +amount density on the same face (simulation.cpp:65-67).

@@ -78,12 +78,17 @@ __device__ __forceinline__ float load_uniform(const char* p)
     return *(const __attribute__((address_space(4))) float*)p;
 }
 
+// WALLSEL = 3 (mask-free build): {zbeg, zend, ga, gb} per workgroup, made on the host (chunk_plan.h: mask_free_plan)
+struct CleanArgs {
+    const int* plan = nullptr;
+};
+
 template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL>
 __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ src,
                                                                       const T* __restrict__ rhs, T* __restrict__ dst,
                                                                       const uint8_t* __restrict__ flags, int b, T a, T inv_c,
                                                                       int z_first, int z_last, int zc_len, int z_stride,
-                                                                      int nbands, int nblk, PeerPush pp)
+                                                                      int nbands, int nblk, PeerPush pp, CleanArgs ca)
 {
     static_assert(NL == 2 || NL == 3, "two or three sweeps per pass");
     constexpr int BY = NYW * RY, TW = NXW * 256 + 8, RW = NXW * 256;
@@ -119,8 +124,9 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     const bool full_group = ALIGNED || (x0 + 3 <= W);
     // physical z walls: both on one GPU; on a slab only the first / last rank has one
     const bool lo_wall = SLAB ? (sc.lo_wall != 0) : true, hi_wall = SLAB ? (sc.hi_wall != 0) : true;
-    const int zbeg = SLAB ? z_first + zc * z_stride : 1 + zc * zc_len;                  // level-NL output planes
-    const int zend = min(SLAB ? z_last : D, zbeg + zc_len - 1);
+    const int* plan = WALLSEL == 3 ? ca.plan + 4 * v : nullptr;                          // (wave-uniform: scalar loads)
+    const int zbeg = WALLSEL == 3 ? plan[0] : SLAB ? z_first + zc * z_stride : 1 + zc * zc_len;   // level-NL output planes
+    const int zend = WALLSEL == 3 ? plan[1] : min(SLAB ? z_last : D, zbeg + zc_len - 1);
     if (zbeg > zend) return;                             // block-uniform
     // planes of level j: NL-j beyond the output chunk on each side; beyond a physical wall there is no
     // such plane (its ghost is derived below), beyond a slab boundary it is the neighbour's plane,
@@ -140,9 +146,10 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     unsigned flc[RY], kl[3][RY] = {};                    // (not in idle load registers: a select on those would wait for the loads)
     // `ngroups` groups of three plane iterations from z_from on with one of the bodies (the register slots rotate with period
     // three: a group starts and ends with every plane in its home slot, so bodies can alternate between groups), then, with
-    // tail_to >= 0, the march's last one or two iterations up to tail_to
+    // tail_to >= 0, the march's last one or two iterations up to tail_to.  wallc: 1 general, 0 wall-free, 2 mask-free (wall-free,
+    // and every kill byte its settle4s would read is 0: no kill-byte loads, settle4 is a copy)
     auto run = [&](auto wallc, int z_from, int ngroups, int tail_to) {
-    constexpr bool WALLS = decltype(wallc)::value != 0;
+    constexpr bool WALLS = decltype(wallc)::value == 1, MF = decltype(wallc)::value == 2;
     const bool lo_wall_c = WALLS && lo_wall, hi_wall_c = WALLS && hi_wall;      // the ghost-plane code of the physical z walls
     // rows a level can be computed for: one fewer per level at a band edge, none lost at a wall
     const bool top_in_tile = WALLS && (s + BY - 1 >= H + 1), bottom_in_tile = WALLS && (s <= 0);
@@ -202,7 +209,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rcur[r][e] = q[e];
             } else ld4(rp + oc[r], rcur[r]);
-            flc[r] = (unsigned)fp[(oc[r] / (unsigned)ES + 3u) >> 2];
+            if constexpr (!MF) flc[r] = (unsigned)fp[(oc[r] / (unsigned)ES + 3u) >> 2];
         }
     };
 
@@ -223,6 +230,11 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     // what setBounds leaves in memory for the lane's four cells of an interior row.  Most waves
     // have no solid cell anywhere near: they skip the zeroing logic on one wave-uniform test.
     auto settle4 = [&](const T (&u)[4], unsigned fl, T (&st)[4]) {
+        if constexpr (MF) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) st[e] = u[e];
+            return;
+        }
         const unsigned kb = (fl >> kill_shift) & 15u;
         if (ALIGNED && __builtin_amdgcn_ballot_w64(kb != 0) == 0) {
 #pragma unroll
@@ -380,7 +392,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
                     if (wall_lo1) face4(u, b == 3, L1[I1][r]);      // ghost plane z = 0 takes plane 0's slot, :208-210
                     if (wall_hi1) face4(u, b == 3, gz1[r]);         // ghost plane z = D+1 waits for its slot, :212-214
                 }
-                kl[PH][r] = flc[r];
+                if constexpr (!MF) kl[PH][r] = flc[r];
             }
         }
         // next plane's level-0 data, one iteration ahead.  Unconditional (a conditional load merges
@@ -489,10 +501,18 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         iter(IC<0>{}, zl);
         if (zl + 1 <= tail_to) iter(IC<1>{}, zl + 1);
     }
+    if (MF && ngroups > 0) {                             // what a masked body that follows reads of planes z_from + 3 ngroups - 2 ..
+#pragma unroll                                           // + 3 ngroups: clean, so all 0
+        for (int r = 0; r < RY; ++r) {
+            flc[r] = 0u;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) kl[q][r] = 0u;
+        }
+    }
     };
     const int zl_end = zend + OV;                        // the march: iterations lo1 .. zl_end
     const int total = zl_end - lo1 + 1, ngroups = total / 3;
-    if constexpr (WALLSEL == 1) {
+    if constexpr (WALLSEL == 1 || WALLSEL == 3) {
         // Two bodies.  A band at a y wall runs the general one throughout (and is the lighter band, see `s`).  Any other band
         // needs it only where a level touches a physical z wall: the iterations up to NL (plane 1 as level 1 .. NL) and those
         // from D on; the groups of three iterations that contain none of those run the wall-free body.
@@ -504,7 +524,16 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
             g1 = hi_wall ? max(g0, min(ngroups, (D - lo1) / 3)) : ngroups;     // group k covers lo1 + 3k .. lo1 + 3k + 2 < D
         }
         run(IC<1>{}, lo1, g0, -1);
-        run(IC<0>{}, lo1 + 3 * g0, g1 - g0, -1);
+        if constexpr (WALLSEL == 1) run(IC<0>{}, lo1 + 3 * g0, g1 - g0, -1);
+        else {
+            // mask-free build: the wall-free groups run mask-free [g0, ga), wall-free [ga, gb), mask-free [gb, g1), the split the
+            // host made from the clean table (chunk_plan.h).  (Bodies alternating inside a loop spill at the loop's merge: 168
+            // VGPRs + 372 B of scratch, against 150 and none for these three straight-line runs.)
+            const int ga = plan[2], gb = plan[3];
+            run(IC<2>{}, lo1 + 3 * g0, ga - g0, -1);
+            run(IC<0>{}, lo1 + 3 * ga, gb - ga, -1);
+            run(IC<2>{}, lo1 + 3 * gb, g1 - gb, -1);
+        }
         run(IC<1>{}, lo1 + 3 * g1, ngroups - g1, zl_end);
     } else {
         run(IC<WALLSEL == 2 ? 0 : 1>{}, lo1, ngroups, zl_end);
@@ -522,10 +551,50 @@ static int fused_bands(int H, int BY)
     return (H + step - 1) / step;
 }
 
+// The mask-free build's per-workgroup table of one launch shape on the device: made and uploaded at its first launch after a mask
+// change (host work and one upload, no wait on the device), then reused.  z chunks balanced per band by `cost`, or equal ones of
+// zc_len planes when it is off.
+static const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& cost, const GridDesc& g, int BY, int nbands,
+                                 int nzc, int zc_len)
+{
+    const bool bal = cost.general > 0;
+    for (const MaskPlan::Chunks& c : mp.chunks)
+        if (c.BY == BY && c.nbands == nbands && c.nzc == nzc && c.zc_len == (bal ? 0 : zc_len) && c.cost.general == cost.general &&
+            c.cost.wall_free == cost.wall_free && c.cost.mask_free == cost.mask_free)
+            return c.dev;
+    std::vector<int> chunks;
+    if (bal) chunks = balanced_chunks(mp.host, mp.words, g.H, g.D, BY, nbands, nzc, cost);
+    else
+        for (int zc = 0; zc < nzc; ++zc)
+            for (int band = 0; band < nbands; ++band) {
+                chunks.push_back(1 + zc * zc_len);
+                chunks.push_back(std::min(g.D, zc * zc_len + zc_len));
+            }
+    MaskPlan::Chunks c{BY, nbands, nzc, bal ? 0 : zc_len, cost, mask_free_plan(mp.host, mp.words, g.H, g.D, BY, nbands, chunks), nullptr};
+    if (hipMalloc((void**)&c.dev, c.plan.size() * sizeof(int)) != hipSuccess) return nullptr;
+    mp.chunks.push_back(std::move(c));
+    MaskPlan::Chunks& k = mp.chunks.back();
+    if (hipMemcpyAsync(k.dev, k.plan.data(), k.plan.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+    return k.dev;
+}
+
+void MaskPlan::clear_chunks()
+{
+    for (Chunks& c : chunks) hipFree(c.dev);
+    chunks.clear();
+}
+void MaskPlan::release()
+{
+    clear_chunks();
+    if (tab) hipFree(tab);
+    tab = nullptr;
+    host.clear();
+}
+
 template <class T, int NL, int NXW, int NYW, int RY>
 static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
                            const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int alt,
-                           int second_first, const PeerPush* push)
+                           int second_first, const PeerPush* push, MaskPlan* mp)
 {
     const PeerPush pp = (push && second_first < 0) ? *push : PeerPush();
     constexpr int BY = NYW * RY, THREADS = NXW * NYW * 64;
@@ -571,9 +640,10 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
     }
     // whole-domain, lane-aligned rows (the benchmark grids) get the build without any slab logic; everything
     // else the general one
+    CleanArgs ca;
 #define FS_LAUNCH(AL, SL, WS)                                                                                            \
     hipLaunchKernelGGL((jacobi_fused_kernel<T, NL, NXW, NYW, RY, AL, SL, WS>), dim3(nblk), dim3(THREADS), 0, st, g, sc, src, \
-                       rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp)
+                       rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp, ca)
     // The wall-free second body exists for the three-sweep kernel on lane-aligned whole-domain grids (the benchmark grids).
     // Rounds 1-2 selected a body per WORKGROUP: 9 % (512^3) to 14 % (256^3) faster for the interior ones, but a pass ends with its
     // slowest workgroup, and at 512^3 (256 workgroups, one per CU) half of them touch a z wall.  Round 3 selects per GROUP OF
@@ -584,7 +654,12 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
     const bool two_bodies = tune.wall_free >= 1;
     if constexpr (NL == 3) {                             // (the two-body builds exist for three sweeps only)
         if (aligned && two_bodies) {
-            if (whole) FS_LAUNCH(true, false, 1);
+            // mask_free "auto": rows of two waves only -- on 256-cell rows (c2) this build measured slower (4.70 -> 4.81 ms per step)
+            const bool mask_free = tune.mask_free >= 2 || (tune.mask_free == 1 && NXW >= 2);
+            if (whole && mask_free && mp && !mp->host.empty() &&
+                (ca.plan = mask_free_plan(st, *mp, tune.chunk_cost, g, BY, nbands, nblk / nbands, zc_len)))
+                FS_LAUNCH(true, false, 3);   // the mask-free build, on z chunks balanced per band unless the cost model is off
+            else if (whole) FS_LAUNCH(true, false, 1);
             else FS_LAUNCH(true, true, 1);               // z-slabs: an inner rank has no z wall at all
             return;
         }
@@ -627,11 +702,12 @@ int fused_shape_count<double>(const GridDesc& g, int) { return (g.W <= 256) ? 1 
 template <>
 void launch_jacobi_fused<float>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels,
                                 const float* src, const float* rhs, float* dst, const uint8_t* flags, int b, float a,
-                                float inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push)
+                                float inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push,
+                                MaskPlan* mp)
 {
     if (plan < 0) plan = 0;
     const int alt = plan >> 3, shape = plan & 7;
-#define FS_F(NL, NX, NY, RY) launch_fused_v<float, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push)
+#define FS_F(NL, NX, NY, RY) launch_fused_v<float, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push, mp)
     if (levels == 3 && tune.abl == 16 && g.W == 512 && sc.lo_wall && sc.hi_wall && z_first == 1 && z_last == g.D && second_first < 0) {
         // EXPERIMENT, timing only (wrong at the walls): every workgroup runs the lean interior body in 16-row bands
         constexpr int BY = 16;
@@ -639,7 +715,7 @@ void launch_jacobi_fused<float>(hipStream_t st, const SweepTune& tune, const Gri
         const int nzc = alt == 0 ? 5 : alt == 1 ? 6 : 4;
         const int zc_len = (g.D + nzc - 1) / nzc, nblk = nbands * nzc;
         hipLaunchKernelGGL((jacobi_fused_kernel<float, 3, 2, 8, 2, true, false, 2>), dim3(nblk), dim3(1024), 0, st, g, sc, src, rhs, dst, flags,
-                           b, a, inv_c, z_first, z_last, zc_len, zc_len, nbands, nblk, PeerPush());
+                           b, a, inv_c, z_first, z_last, zc_len, zc_len, nbands, nblk, PeerPush(), CleanArgs());
         return;
     }
     if (levels == 3) {
@@ -665,11 +741,12 @@ void launch_jacobi_fused<float>(hipStream_t st, const SweepTune& tune, const Gri
 template <>
 void launch_jacobi_fused<double>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int,
                                  const double* src, const double* rhs, double* dst, const uint8_t* flags, int b, double a,
-                                 double inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push)
+                                 double inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push,
+                                 MaskPlan*)
 {
     if (plan < 0) plan = 0;
     const int alt = plan >> 3, shape = plan & 7;
-#define FS_F(NL, NX, NY, RY) launch_fused_v<double, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push)
+#define FS_F(NL, NX, NY, RY) launch_fused_v<double, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push, nullptr)
     // fp64: two sweeps per pass; rows up to 256 cells: 20-row bands; up to 512: 10-row bands (10 waves) or 8 (8 waves, 256 VGPRs)
     if (g.W <= 256) FS_F(2, 1, 10, 2);
     else if (shape == 1) FS_F(2, 2, 4, 2);
