@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the north-star metric on synthetic wind tunnels (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4] [--dump-outputs DIR] [--full]
 
 A "step" is one iteration of the reference's time loop (Simulation::run(), simulation.cpp:63-71:
 inlet density, buffer = dens, Simulation::step()) with frame dumps off.  Fields live in HBM for
@@ -11,6 +11,13 @@ the whole timed region.  Workloads (BASELINE.json configs):
     c4  1024x512x512,   sphere + plate, 80 solver iterations   <- N>1 default, z-slabs, strong scaling
 For N>1 the driver launches one rank per GPU with torch.distributed.run; ranks exchange halo
 planes over RCCL inside libfluidsim.so.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the
+headline and what the timed steps themselves measured (roofline from their HIP events, kernel
+families, communication schedule).  --full adds everything that takes runs of its own: for N>1 the
+slab-vs-whole parity check before the timed run; for N=1 afterwards the isolated pressure-sweep
+microbench, on c3 the config 2 / solver quality / dead-solve-elided / last-frame-dump / config 4
+extras (--no-extra drops these), and the CPU baseline (--no-cpu-baseline drops it).
 """
 import argparse
 import json
@@ -250,10 +257,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="auto", choices=["auto", "c2", "c3", "c4"])
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (slab_parity for N > 1; for N = 1 the "
+                         "pressure-sweep microbench, the c3 extras and cpu_baseline): off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out the microbench and the c3 extras")
     ap.add_argument("--cpu-budget", type=float, default=10.0,
-                    help="seconds for the one-thread leg of cpu_baseline; below 5 the 256^3 sample is skipped (tests)")
+                    help="with --full: seconds for the one-thread leg of cpu_baseline; below 5 the 256^3 sample is skipped (tests)")
     ap.add_argument("--launch-plans", default=None,
                     help="\"<two-sweep plan id>,<three-sweep plan id>\": replay the launch plans of another run instead of timing "
                          "them (tools/make_profiles.sh: counter passes must run what the bench line ran)")
@@ -274,6 +284,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    extra = args.full and not args.no_extra              # what takes runs of its own: --full only
+    cpu_base = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as dist
@@ -321,9 +333,10 @@ def main():
             sys.stderr.write("bench rank %d: %s\n" % (rank, msg))
             sys.stderr.flush()
 
-    slab_parity = None
+    slab_parity = None                                   # --full only; a plain line carries slab_parity = null
     if world > 1:
         from fluid_simulation_amd import dist as fsdist
+    if world > 1 and args.full:
         if os.environ.get("FS_BENCH_SKIP_PARITY"):       # development only: the line then carries slab_parity = null
             trace("parity check SKIPPED (FS_BENCH_SKIP_PARITY)")
         else:
@@ -480,7 +493,7 @@ def main():
         "step_bytes_per_cell_algorithmic": 208 + 72 * acc,
         "step_roofline_frac": (208 + 72 * acc) * (elem // 4) * cells * args.steps / elapsed / 1e9 / HBM_PEAK_GBS,
     }
-    if world == 1 and not args.no_extra:
+    if world == 1 and extra:
         # the pressure solve in isolation -- `acc` sweeps (a = 1, c = 6) on the divergence
         # field of the state the run ended in, repeated 20 times, HIP events around each repetition
         reps = [sim.time_sweeps(0, F.PRESSURE, F.DIVERGENCE, 1.0, 6.0, acc) for _ in range(20)]
@@ -493,7 +506,7 @@ def main():
         }
     sim.close()
 
-    if world == 1 and not args.no_extra and name == "c3":
+    if world == 1 and extra and name == "c3":
         # the other size the metric is quoted on: 256^3 (config 2), short run
         c2 = WORKLOADS["c2"]
         s2 = F.Simulation(c2["W"], c2["H"], c2["D"], 3, acc=c2["acc"], quiet=1, dump_every=0, profile=1)
@@ -548,7 +561,7 @@ def main():
         del div2, obs2
         s2.close()
 
-    if world == 1 and not args.no_extra and name == "c3":
+    if world == 1 and extra and name == "c3":
         # transparency: the reference's density diffusion is dead work (its result is overwritten by
         # the following advect, simulation.cpp:135-136).  The headline above executes it; this is
         # the same workload with it elided (identical fields, tests/test_gpu_parity.py).
@@ -565,7 +578,7 @@ def main():
                                                   "note": "not the headline; 5*acc instead of 6*acc sweeps per step"}
         s3.close()
 
-    if world == 1 and not args.no_extra and name == "c3":
+    if world == 1 and extra and name == "c3":
         # also with the last frame dumped (fs_run, dump_every = -1), writer flushed
         dump_root = "/dev/shm" if os.path.isdir("/dev/shm") else None
         with tempfile.TemporaryDirectory(dir=dump_root) as dtmp:
@@ -581,7 +594,7 @@ def main():
                                             "note": "3 steps through fs_run + one 2.7 GB frame written to " + (dump_root or "tmp")}
             s4.close()
 
-    if world == 1 and not args.no_extra and name == "c3":
+    if world == 1 and extra and name == "c3":
         # the N > 1 lines run config 4 (1024x512x512, strong scaling): the same workload on this one
         # GPU, so that whoever divides the multi-GPU values has the matching single-GPU number
         c4 = WORKLOADS["c4"]
@@ -599,7 +612,7 @@ def main():
                                       "note": "strong-scaling base of the --gpus N > 1 lines (same workload, one GPU)"}
         s5.close()
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and cpu_base:
         out["cpu_baseline"] = cpu_baseline(budget_s=args.cpu_budget)
     print(json.dumps(out))
     if world > 1:

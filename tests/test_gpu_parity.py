@@ -386,13 +386,13 @@ def test_simulation_out_reference_defaults(tmp_path):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "1", "--warmup", "1",
-                          "--cpu-budget", "1.0", "--dump-outputs", str(tmp_path / "outputs")],
+                          "--full", "--cpu-budget", "1.0", "--dump-outputs", str(tmp_path / "outputs")],
                          capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -420,6 +420,34 @@ def test_bench_line_contract(tmp_path):
         assert a.dtype == np.float32 and a.shape == (1 << 20,) and np.isfinite(a).all(), name
         total += a.nbytes
     assert total <= 64 << 20 and np.load(str(tmp_path / "outputs" / "v_x.npy")).max() > 1.0
+
+
+def test_bench_plain_line_is_lean(tmp_path):
+    """Without --full, bench.py prints the same headline line and dumps, and nothing that takes runs of its own."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "outputs")],
+                         capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "kernel_ms", "jacobi_iter_per_sec"):
+        assert k in d, k
+    assert d["metric"] == "cells_steps_per_sec" and d["unit"] == "cells*steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 1e8
+    assert abs(d["value"] - 256 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"]["launches"] > 0 and d["slab_parity"] is None
+    for k in ("cpu_baseline", "pressure_sweep_microbench", "extra_256", "solver_quality_256",
+              "extra_dead_density_solve_elided", "extra_last_frame_dump", "extra_c4_single_gpu"):
+        assert k not in d, k
+    for name in ("dens", "v_x", "v_y", "v_z", "pressure", "divergence"):
+        a = np.load(str(tmp_path / "outputs" / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (1 << 20,) and np.isfinite(a).all(), name
 
 
 def test_stock_run_of_the_reference_program_byte_identical(tmp_path):

@@ -15,8 +15,8 @@ OUT=gpurun_out/profiles_$TAG
 rm -rf $OUT && mkdir -p $OUT   # (gpurun merges into an existing local copy: clear that one by hand before re-running a tag)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 B="python3 bench.py --no-cpu-baseline --no-extra"
-# 1. the bench line itself (with cpu_baseline and the extras)
-timeout -k 10 400 python3 bench.py > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+# 1. the bench line itself (--full: with cpu_baseline and the extras)
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 # the launch plans that line ran: every profiled pass below replays them (under counter collection the clock is a
 # different one, and the plan is part of what roofline.traffic is stamped with)
 plans() { python3 -c "import json,sys; r=json.load(open(sys.argv[1]))['roofline']; print('%d,%d' % (r['workgroup_shape_id'], r['launch_plan_three_sweeps']))" "$1"; }
