@@ -1,4 +1,6 @@
-"""One rank of a z-slab run (spawned by tests/test_gpu_slabs.py).  argv: rank nranks idfile outdir W H D acc steps"""
+"""One rank of a z-slab run (spawned by tests/test_gpu_slabs.py).  argv: rank nranks idfile outdir W H D acc steps
+[stl precision solver options], options either k=v,k=v or one JSON object"""
+import json
 import os
 import sys
 
@@ -25,9 +27,15 @@ def main():
     precision = sys.argv[11] if len(sys.argv) > 11 else "fp32"
     solver = sys.argv[12] if len(sys.argv) > 12 else "jacobi"
     extra = {"sor_omega": 1.6} if solver == "rbsor" else {}
-    for kv in (sys.argv[13].split(",") if len(sys.argv) > 13 and sys.argv[13] else []):   # further options, k=v,k=v
-        k, v = kv.split("=")
-        extra[k] = v
+    opts = sys.argv[13] if len(sys.argv) > 13 else ""
+    if opts.startswith("{"):
+        # further options as one JSON object (values may hold commas, e.g. launch_plans); a list gives each rank its own value
+        for k, v in json.loads(opts).items():
+            extra[k] = v[rank] if isinstance(v, list) else v
+    else:
+        for kv in (opts.split(",") if opts else []):     # further options, k=v,k=v
+            k, v = kv.split("=")
+            extra[k] = v
     kw = dict(acc=acc, quiet=1, dump_dir=os.path.join(outdir, "data"), dump_every=1, voxel_seed=77, debug_poison_gather=1,
               precision=precision, solver=solver)
     kw.update(extra)                                     # options of the test case win (e.g. dump_every=0 at full size)
@@ -70,8 +78,9 @@ def main():
     stats = np.array(sim.stats(F.DENS) + sim.stats(F.VX))
     reach = sim._geti("last_advect_reach")
     kernels = np.array([sim._geti("triple_plan"), sim._geti("two_sweep_fused"), sim._geti("halo_depth")])
+    plans = np.array([sim._geti("pair_shape"), sim._geti("triple_plan")])
     sched_end = np.array([sim._geti(k) for k in ("stream_syncs", "reach_waits", "reach_waits_blocked")])
-    np.savez(os.path.join(outdir, "rank%d.npz" % rank), zoff=zoff, stats=stats, reach=reach, kernels=kernels, sched=sched,
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), zoff=zoff, stats=stats, reach=reach, kernels=kernels, plans=plans, sched=sched,
              sched_end=sched_end, **out)
     sim.close()
 

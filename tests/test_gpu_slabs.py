@@ -3,6 +3,7 @@ through the host-staged shared-memory transport (RCCL refuses ranks on the same 
 run the product's slab code path -- wall flags, global-z flags and back-trace, halo exchange
 after every sweep, all-gathered advection source, per-rank dump offsets, reduced statistics --
 and must reproduce the single-GPU run bit for bit (halo exchange does not change arithmetic)."""
+import json
 import os
 import subprocess
 import sys
@@ -164,6 +165,40 @@ def test_slabs_wide_rows_and_fp64(tmp_path, W, H, D, nranks, precision, solver, 
             assert (triple_plan >= 0) == (zh == 3)      # slab ranks run three sweeps per pass wherever the kernel exists
             if "fused" in opts:
                 assert fused2 == 1
+
+
+SLAB_PLANS = [
+    # (W, H, D, transport, launch_plans of rank 0 and rank 1): every three-sweep shape forced on both ranks (rows of 256 cells:
+    # 20-, 16- and 12-row bands, rows of 512: 12 and 10), ranks on different plans, and the two-sweep kernels of 1000-cell rows
+    (256, 30, 32, "shm", ["0,0", "0,0"]), (256, 30, 32, "ipc", ["0,1", "0,1"]), (256, 30, 32, "shm", ["0,10", "0,10"]),
+    (256, 30, 32, "ipc", ["1,2", "2,17"]), (512, 20, 32, "ipc", ["0,0", "0,0"]), (512, 20, 32, "shm", ["0,9", "0,9"]),
+    (512, 20, 32, "shm", ["2,16", "8,1"]), (1000, 8, 24, "shm", ["65,-1", "65,-1"]), (1000, 8, 24, "ipc", ["0,-1", "72,-1"]),
+]
+
+
+@pytest.mark.parametrize("W,H,D,transport,plans", SLAB_PLANS)
+def test_slabs_with_forced_and_mixed_launch_plans(tmp_path, W, H, D, transport, plans):
+    """Slab ranks agree on whether they run three sweeps per pass, but each rank times its own shape and chunk count: with
+    launch_plans forced per rank (the same plan, or a different one on each rank), 2 ranks still match one GPU bit for bit."""
+    if transport == "ipc":
+        ok, why = ipc_usable()
+        if not ok:
+            pytest.skip("FSIPC transport not usable on this box: " + why)
+    base = [W, H, D, 8, 2, os.path.join(GOLDEN, "plate_ascii.stl"), "fp32", "jacobi"]
+    ref_dir = run_ranks(str(tmp_path), 1, base + [""])
+    par_dir = run_ranks(str(tmp_path), 2, base + [json.dumps({"launch_plans": plans})], transport=transport)
+    ref = np.load(os.path.join(ref_dir, "rank0.npz"))
+    Dl = D // 2
+    for r in range(2):
+        z = np.load(os.path.join(par_dir, "rank%d.npz" % r))
+        zoff = int(z["zoff"])
+        two, three = (int(v) for v in plans[r].split(","))
+        assert [int(v) for v in z["plans"]] == [two, three], (r, z["plans"])
+        for k in ("dens", "v_x", "v_y", "v_z", "obs", "pressure"):
+            got, want = z[k], ref[k][zoff:zoff + Dl + 2]
+            lo = 0 if r == 0 else 1
+            hi = Dl + 2 if r == 1 else Dl + 1
+            assert np.array_equal(got[lo:hi].view(np.uint32), want[lo:hi].view(np.uint32)), (plans, r, k)
 
 
 def test_depth_must_divide(tmp_path):
