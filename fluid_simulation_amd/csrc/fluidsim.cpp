@@ -89,6 +89,7 @@ struct EngineBase {
     virtual int obstacle_surface() = 0;
     virtual int reference_order_sum(int which, double* out) = 0;
     virtual int multigrid_levels() const = 0;
+    virtual int multigrid_first_replicated() const = 0;
     virtual int obstacle_force(double* out5, double* per_plane) = 0;
     virtual int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
 };
@@ -1006,6 +1007,7 @@ struct Engine : EngineBase {
     // kernel (its red-black instantiation is 1.6x slower and smooths no better here), the coarse levels live in
     // multigrid.hip.  Single GPU.
     int multigrid_levels() const override { return mg.levels(); }
+    int multigrid_first_replicated() const override { return mg.first_repl; }
     // the transport's part in the coarse levels of a slab run (multigrid.h): one-plane halo refreshes of distributed levels,
     // all-gathers at the seam to the levels every rank holds whole
     fs::MgHooks<T> mg_hooks()
@@ -2121,6 +2123,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "two_sweep_fused") *out = (s->eng && s->eng->tuned_shape() >= 64) ? 1 : 0;   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
     else if (n == "halo_depth") *out = s->eng ? s->eng->halo_depth() : 0;
     else if (n == "mg_levels") *out = s->eng ? s->eng->multigrid_levels() : 0;          // levels of the last solver=mg solve, level 0 included
+    else if (n == "mg_first_replicated") *out = s->eng ? s->eng->multigrid_first_replicated() : 0;   // ... the first held whole by every rank
     // z-slab runs: the communication schedule in force (what "auto" chose), and the slab step's host-side waits
     else if (n == "overlap_plan") *out = s->overlap_plan;
     else if (n == "comm_cus_plan") *out = s->cus_plan;

@@ -54,8 +54,10 @@ struct Multigrid {
     size_t pool_elems = 0;
 
     int levels() const { return (int)lv.size(); }          // including level 0
-    // (re)allocates for this grid if needed and computes the coefficients of every level from the flag bytes.
-    // nranks > 1: g is the rank's slab; min_planes = fewest planes per rank a distributed level may have
+    // (re)allocates for this grid if needed and computes the coefficients of every level from the flag bytes (the levels:
+    // mg_plan.h).  nranks > 1: g is the rank's slab; min_planes = fewest planes per rank a distributed level may have.
+    // Returns 0; -1 after a fresh allocation that a slab run must export before it calls again; 2 if the plan refuses the
+    // split; 1 / 3 on a HIP / transport error
     int build(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const uint8_t* flags, int nranks_ = 1, int rank_ = 0,
               int min_planes = 4, const MgHooks<T>* hooks = nullptr);
     void release();

@@ -8,13 +8,12 @@
 
 #include "kernels.h"
 #include "kernels_dev.h"
+#include "mg_plan.h"
 #include "multigrid.h"
 
 namespace fs {
 
 namespace {
-
-constexpr int MG_MIN_DIM = 4;
 
 template <class T>
 __device__ __forceinline__ long lat(const MgLevel<T>& l, int x, int y, int z)
@@ -411,6 +410,7 @@ void Multigrid<T>::release()
     pool = nullptr;
     reg_pool = nullptr;
     pool_elems = 0;
+    first_repl = 1;
     lv.clear();
     W0 = H0 = D0 = 0;
 }
@@ -441,36 +441,28 @@ int Multigrid<T>::build(hipStream_t st, const GridDesc& g, const SlabCtx& sc, co
         W0 = g.W; H0 = g.H; D0 = g.D;
         nranks = nranks_;
         rank = rank_;
+        const MgPlan plan = mg_plan(g.W, g.H, Dg, nranks, min_planes);
+        if (plan.status != MgPlan::OK) { release(); return 2; }
+        first_repl = plan.first_repl;
         MgLevel<T> l0{};
         l0.W = g.W; l0.H = g.H; l0.D = g.D;
         lv.push_back(l0);
-        // the hierarchy is that of the GLOBAL grid (a slab run must coarsen exactly like the same run on one GPU)
-        int W = g.W, H = g.H, D = Dg;
-        first_repl = 1;
-        bool dist = nranks > 1;                           // one GPU: every level is held whole
         size_t total = 0;
-        while (W % 2 == 0 && H % 2 == 0 && D % 2 == 0 && W / 2 >= MG_MIN_DIM && H / 2 >= MG_MIN_DIM && D / 2 >= MG_MIN_DIM) {
-            W /= 2; H /= 2; D /= 2;
+        for (size_t i = 1; i < plan.lv.size(); ++i) {
+            const MgPlanLevel& pl = plan.lv[i];
             MgLevel<T> l{};
-            l.W = W; l.H = H;
-            // a level stays distributed while every rank keeps at least min_planes planes of it
-            dist = dist && D % nranks == 0 && D / nranks >= (min_planes > 1 ? min_planes : 1);
-            if (dist) {
-                l.D = D / nranks;
-                l.zoff = rank * l.D;
+            l.W = pl.W; l.H = pl.H; l.D = pl.Dl;
+            if (pl.dist) {
+                l.zoff = pl.zoff(rank);
                 l.lo_wall = sc.lo_wall;
                 l.hi_wall = sc.hi_wall;
-                first_repl = (int)lv.size() + 1;
-            } else {
-                l.D = D;
             }
-            l.sy = W + 2;
-            l.sz = l.sy * (H + 2);
+            l.sy = l.W + 2;
+            l.sz = l.sy * (l.H + 2);
             l.n = l.sz * (l.D + 2);
             total += 7 * (size_t)l.n;
             lv.push_back(l);
         }
-        if (nranks > 1 && lv.size() > 1 && (g.D % 2) != 0) { release(); return 2; }   // children of a coarse cell must be one rank's
         if (total) {
             hipError_t e = hipMalloc((void**)&pool, total * sizeof(T));
             if (e == hipSuccess) e = hipMalloc((void**)&reg_pool, total / 7);
@@ -486,7 +478,7 @@ int Multigrid<T>::build(hipStream_t st, const GridDesc& g, const SlabCtx& sc, co
                 rq += l.n;
             }
         }
-        if (nranks > 1) return -1;                       // fresh allocation: the caller exports it to its peers, then calls again
+        if (plan.export_pool) return -1;                 // fresh allocation: the caller exports it to its peers, then calls again
     }
     if (pool) {
         hipError_t e = hipMemsetAsync(pool, 0, pool_elems * sizeof(T), st);     // ghosts, dead cells and wall faces stay 0

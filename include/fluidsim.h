@@ -60,8 +60,9 @@ enum {
                             * oracle/cpu_ref_mg.h); so does fs_linear_solver when called with that equation's coefficients
                             * (b = 0, a = 1, c = 6); every other solve (diffusion) runs Jacobi.  One GPU or z-slabs
                             * (a rank must then hold an even number of planes; option "mg_min_planes": coarse levels stay
-                            * distributed while every rank keeps that many planes, default 32, and are held whole by every
-                            * rank below); grids whose extents cannot be halved get no coarse levels.  SURVEY.md 8f rank 4 */
+                            * distributed while every rank keeps that many planes, default 32, and an even number of them
+                            * unless the level is the coarsest, and are held whole by every rank below); grids whose extents
+                            * cannot be halved get no coarse levels.  SURVEY.md 8f rank 4 */
 };
 
 /* ---- construction -------------------------------------------------------------- */
@@ -138,8 +139,9 @@ int fs_destroy(fs_sim* s);
  *                 without stalling the device (same passes, same order, same bits);
  *   "debug_poison_gather" "1": fill the gathered advection source with NaN patterns before each gather (tests).
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
- * "two_sweep_fused" "mg_levels" and, for slab handles, "stream_syncs" (compute-stream synchronisations issued by slab
- * steps; 0 on the step path) "reach_waits" "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed".
+ * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
+ * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
+ * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed".
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 

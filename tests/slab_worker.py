@@ -80,8 +80,9 @@ def main():
     kernels = np.array([sim._geti("triple_plan"), sim._geti("two_sweep_fused"), sim._geti("halo_depth")])
     plans = np.array([sim._geti("pair_shape"), sim._geti("triple_plan")])
     sched_end = np.array([sim._geti(k) for k in ("stream_syncs", "reach_waits", "reach_waits_blocked")])
+    mg = np.array([sim._geti("mg_levels"), sim._geti("mg_first_replicated")])      # solver=mg: the hierarchy the run used
     np.savez(os.path.join(outdir, "rank%d.npz" % rank), zoff=zoff, stats=stats, reach=reach, kernels=kernels, plans=plans, sched=sched,
-             sched_end=sched_end, **out)
+             sched_end=sched_end, mg=mg, **out)
     sim.close()
 
 

@@ -40,10 +40,16 @@ def relative_residual(p, div, mask):
 @pytest.mark.parametrize("shape,fp64,mg", [((32, 32, 32), False, (3, 1, 1, 30)), ((64, 32, 16), False, (2, 2, 1, 10)),
                                            ((40, 24, 8), True, (2, 1, 2, 30)), ((128, 64, 64), False, (2, 1, 1, 30)),
                                            ((30, 20, 10), False, (2, 1, 1, 8)), ((33, 21, 5), False, (2, 1, 1, 4)),
-                                           ((512, 16, 8), False, (1, 1, 1, 5)), ((24, 16, 16), True, (4, 1, 1, 30))])
+                                           ((512, 16, 8), False, (1, 1, 1, 5)), ((24, 16, 16), True, (4, 1, 1, 30)),
+                                           # the single-GPU runs test_gpu_slabs.py compares its odd-seam and no-coarse-level
+                                           # z-slab cases with, at the cycle parameters those runs use (the defaults)
+                                           ((32, 16, 132), False, (4, 1, 1, 30)), ((32, 16, 264), False, (4, 1, 1, 30)),
+                                           ((32, 32, 264), True, (4, 1, 1, 30)), ((64, 64, 96), False, (4, 1, 1, 30)),
+                                           ((33, 16, 32), False, (4, 1, 1, 30)), ((32, 16, 6), False, (4, 1, 1, 30))])
 def test_multigrid_steps_match_the_oracle_bit_for_bit(F, oracle_mod, shape, fp64, mg):
-    """Whole steps under solver=mg against CR_MG: grids with 1 to 5 levels (33x21x5 cannot be halved at all: the
-    cycles degenerate to red-black iterations on level 0), a plate one cell thick, corner solids, fp32 and fp64."""
+    """Whole steps under solver=mg against CR_MG: grids with 1 to 5 levels (33x21x5, 33x16x32 and 32x16x6 cannot be halved
+    at all: the cycles degenerate to red-black iterations on level 0), a plate one cell thick, corner solids, fp32 and
+    fp64."""
     O = oracle_mod
     W, H, D = shape
     kw = dict(precision="fp64") if fp64 else {}

@@ -281,17 +281,34 @@ def test_config4_grid_split_into_slabs_matches_single_gpu(tmp_path):
         assert np.allclose(z["stats"], ref["stats"], rtol=1e-12, atol=1e-12)
 
 
-@pytest.mark.parametrize("W,H,D,nranks,precision,opts,transport",
-                         [(32, 16, 32, 2, "fp32", "mg_min_planes=4", "shm"),      # both coarse levels distributed (8 and 4 planes per rank)
-                          (32, 16, 32, 2, "fp32", "mg_min_planes=8", "ipc"),      # level 1 distributed, level 2 held whole by every rank
-                          (32, 16, 32, 2, "fp32", "mg_min_planes=16", "ipc"),     # every coarse level held whole (the seam is level 0 -> 1)
-                          (32, 16, 64, 4, "fp32", "", "ipc"), (32, 16, 64, 4, "fp64", "mg_min_planes=8,overlap=3", "ipc"),
-                          (64, 32, 48, 3, "fp32", "mg_min_planes=2", "shm"), (24, 16, 32, 2, "fp32", "mg_cycles=2,mg_pre=2,mg_post=2,overlap=1", "ipc")])
+# (W, H, D, nranks, precision, options of the slab run, transport): (levels with level 0, first level held whole by every rank)
+MG_SLAB_CASES = {
+    (32, 16, 32, 2, "fp32", "mg_min_planes=4", "shm"): (3, 3),        # both coarse levels distributed (8 and 4 planes per rank)
+    (32, 16, 32, 2, "fp32", "mg_min_planes=8", "ipc"): (3, 2),        # level 1 distributed, level 2 held whole by every rank
+    (32, 16, 32, 2, "fp32", "mg_min_planes=16", "ipc"): (3, 1),       # every coarse level held whole (the seam is level 0 -> 1)
+    (32, 16, 64, 4, "fp32", "", "ipc"): (3, 1),
+    (32, 16, 64, 4, "fp64", "mg_min_planes=8,overlap=3", "ipc"): (3, 2),
+    (64, 32, 48, 3, "fp32", "mg_min_planes=2", "shm"): (4, 4),
+    (24, 16, 32, 2, "fp32", "mg_cycles=2,mg_pre=2,mg_post=2,overlap=1", "ipc"): (3, 1),
+    # odd seams: level 1 (33 planes per rank) or level 2 (33) would be a distributed parent of a level held whole, whose coarse
+    # cells' children would then straddle two ranks; it is held whole itself, so the seam moves up one level
+    (32, 16, 132, 2, "fp32", "", "shm"): (3, 1),
+    (32, 16, 264, 4, "fp32", "", "ipc"): (3, 1),
+    (32, 32, 264, 2, "fp64", "mg_min_planes=8,overlap=3", "ipc"): (4, 2),
+    (64, 64, 96, 2, "fp32", "mg_min_planes=3", "shm"): (5, 5),       # 3 planes per rank on the coarsest level: all distributed
+    # no coarse level at all (odd W; D / 2 < 4): nothing to export over FSIPC, the cycles smooth level 0
+    (33, 16, 32, 2, "fp32", "", "ipc"): (1, 1),
+    (32, 16, 6, 2, "fp32", "", "ipc"): (1, 1),
+}
+
+
+@pytest.mark.parametrize("W,H,D,nranks,precision,opts,transport", list(MG_SLAB_CASES))
 def test_slabs_multigrid_matches_single_gpu(tmp_path, W, H, D, nranks, precision, opts, transport):
     """solver=mg on z-slabs (round 3): the pressure equation's V-cycles with the coarse levels distributed like level 0 (one
     halo exchange per red-black colour) down to `mg_min_planes` planes per rank and held whole by every rank below that
     (all-gather at the seam) -- same operations in the same order as on one GPU, so every field must come out bit-identical,
-    also across the obstacle edits between steps that rebuild the coarse operators."""
+    also across the obstacle edits between steps that rebuild the coarse operators.  Each case also runs the hierarchy it
+    was written for (csrc/mg_plan.h; tests/test_mg_plan_cpu.py checks the plan itself over every split)."""
     if transport == "ipc":
         ok, why = ipc_usable()
         if not ok:
@@ -311,6 +328,8 @@ def test_slabs_multigrid_matches_single_gpu(tmp_path, W, H, D, nranks, precision
             hi = Dl + 2 if r == nranks - 1 else Dl + 1
             assert np.array_equal(got[lo:hi].view(u), want[lo:hi].view(u)), (r, k)
         assert int(z["sched"][0]) == 0
+        assert tuple(int(v) for v in z["mg"]) == MG_SLAB_CASES[(W, H, D, nranks, precision, opts, transport)], (r, z["mg"])
+    assert tuple(int(v) for v in ref["mg"]) == (MG_SLAB_CASES[(W, H, D, nranks, precision, opts, transport)][0], 1)
     assert np.abs(ref["pressure"]).max() > 0
 
 
