@@ -5,8 +5,10 @@ when the first `Simulation` is created and there is no CPU fallback.
 """
 from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_PREV, VY, VY_PREV, VZ, VZ_PREV,
                    FluidsimError)
-from .simulation import FORCE_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force
+from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
+                         solve_reduction)
 
 __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_force", "FORCE_LOG_DTYPE", "FluidsimError",
+           "RESIDUAL_LOG_DTYPE", "solve_reduction",
            "FIELD_NAMES",
            "DENS", "VX", "VY", "VZ", "OBS", "PRESSURE", "DIVERGENCE", "VX_PREV", "VY_PREV", "VZ_PREV", "BUFFER"]

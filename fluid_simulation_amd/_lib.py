@@ -17,6 +17,9 @@ FIELD_NAMES = ["dens", "v_x", "v_y", "v_z", "obs", "pressure", "divergence",
                "v_x_prev", "v_y_prev", "v_z_prev", "buffer"]
 COMM_ID_BYTES = 128
 FORCE_LOG_COLS = 9      # FS_FORCE_LOG_COLS: step, S1x, S1y, S1z, S2x, S2y, S2z, faces, frontal
+RESIDUAL_COLS = 4       # FS_RESIDUAL_COLS: sum r^2, sum x0^2, max |r|, free cells
+RESIDUAL_LOG_SOLVES = 6     # FS_RESIDUAL_LOG_SOLVES: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density
+RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, r_sq, r_max, rhs_sq, cells
 
 
 class FluidsimError(RuntimeError):
@@ -66,6 +69,9 @@ _SIGNATURES = {
     "fs_surface_case_table": (C.c_int, [C.c_int, C.c_void_p]),
     "fs_obstacle_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_force_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_solve_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "fs_diffuse_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fs_residual_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

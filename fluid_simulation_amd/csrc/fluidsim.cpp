@@ -16,6 +16,7 @@
 #include "surface.h"
 #include "multigrid.h"
 #include "forces.h"
+#include "residual.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -51,8 +52,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -92,6 +93,9 @@ struct EngineBase {
     virtual int multigrid_first_replicated() const = 0;
     virtual int obstacle_force(double* out5, double* per_plane) = 0;
     virtual int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
+    virtual int solve_residual(int b, int field, int prev, double a, double c, double* out4, double* per_plane) = 0;
+    virtual int diffuse_residual(int b, int field, int prev, double* out4, double* per_plane) = 0;
+    virtual int residual_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
 };
 
 struct fs_sim {
@@ -151,6 +155,8 @@ struct fs_sim {
     long steps_total = 0;        // steps this handle has completed (the "step" column of fs_force_log)
     int force_log = 0;           // "force_log": steps the per-step force log keeps, 0 = off
     long force_log_gen = 0;      // bumped by every fs_set_option("force_log"): the ring is reallocated and cleared
+    int residual_log = 0;        // "residual_log": steps the per-step residual log keeps, 0 = off
+    long residual_log_gen = 0;   // bumped by every fs_set_option("residual_log")
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -269,6 +275,16 @@ struct Engine : EngineBase {
     long force_gen = -1;                // S->force_log_gen the ring was allocated for
     long force_logged = 0;              // steps logged since the ring was cleared or last drained
     std::vector<long> force_step;       // step number held by each ring slot
+    // solve residuals (residual.h): the per-step log is a device ring of res_cap steps x 6 solves x {before, after} x g.D plane records
+    double* res_ring = nullptr;
+    double* res_scratch = nullptr;      // fs_solve_residual: one record per local plane
+    double* res_partial = nullptr;      // the row-chunk records between the two kernels of a launch (stream-ordered reuse)
+    int res_cap = 0;
+    long res_gen = -1;                  // S->residual_log_gen the ring was allocated for
+    long res_logged = 0;                // steps logged since the ring was cleared or last drained
+    std::vector<long> res_step;         // step number held by each ring slot
+    std::vector<unsigned> res_ran;      // bit k: solve k of that step ran (an elided solve leaves no record)
+    unsigned res_ran_now = 0;           // the same for the step that is running
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -388,6 +404,9 @@ struct Engine : EngineBase {
         if (coltab) hipFree(coltab);
         if (force_ring) hipFree(force_ring);
         if (force_scratch) hipFree(force_scratch);
+        if (res_ring) hipFree(res_ring);
+        if (res_scratch) hipFree(res_scratch);
+        if (res_partial) hipFree(res_partial);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -977,17 +996,20 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int diffuse_T(int b, int field, int prev)
+    // log_k >= 0 (inside step() with "residual_log" on): solve k of the step, recorded before and after
+    int diffuse_T(int b, int field, int prev, int log_k = -1)
     {
         const T a = diffusion_a();
         int rc = ensure_flags();
         if (rc) return rc;
         if (S->solver == FS_SOLVER_GS_LEX && (rc = unalias(field))) return rc;
+        const T c = (T)1 + (T)6 * a;
+        if ((rc = log_residual(log_k, 0, b, slot[field], slot[prev], (double)a, (double)c))) return rc;
         int res;
-        rc = solve(b, slot[field], slot[prev], a, (T)1 + (T)6 * a, S->acc, &res);   // :283
+        rc = solve(b, slot[field], slot[prev], a, c, S->acc, &res);   // :283
         if (rc) return rc;
         adopt(field, res);
-        return FS_OK;
+        return log_residual(log_k, 1, b, slot[field], slot[prev], (double)a, (double)c);
     }
     int diffuse(int b, int field, int prev) override { if (!in_step) vzmax_prev = -1.0; return diffuse_T(b, field, prev); }
 
@@ -1102,17 +1124,20 @@ struct Engine : EngineBase {
         // rhs at the cell itself); the pressure halo planes still hold the previous projection and
         // must become the neighbours' freshly zeroed planes before the first sweep reads them.
         if ((rc = halo(arr[slot[FS_PRESSURE]]))) return rc;
+        const int proj = in_step ? projections_this_step++ : -1;   // which of the step's two projections this is
+        const int log_k = (proj >= 0 && proj < 2) ? 3 + proj : -1;
+        if ((rc = log_residual(log_k, 0, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
         int res;
         if (S->solver == FS_SOLVER_MG) rc = multigrid_solve(FS_PRESSURE, FS_DIVERGENCE, &res);
         else rc = solve(0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], (T)1, (T)6, S->acc, &res);   // :320
         if (rc) return rc;
         adopt(FS_PRESSURE, res);
+        if ((rc = log_residual(log_k, 1, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
         {
             ScopedSpan sp(S, FAM_GRAD);
             fs::launch_gradient<T>(S->stream, S->tune, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
                                    arr[slot[FS_VZ]], flags, h, (T)2 * h);
         }
-        const int proj = in_step ? projections_this_step++ : -1;   // which of the step's two projections this is
         if (proj >= 0 && proj < 2 && force_cap > 0) {
             // "force_log": this projection's plane records go straight into the step's ring slot (no host sync)
             ScopedSpan sp(S, FAM_FORCES);
@@ -1324,6 +1349,8 @@ struct Engine : EngineBase {
         int rc = ensure_flags();
         if (rc) return rc;
         if ((rc = ensure_force_ring())) return rc;
+        if ((rc = ensure_residual_ring())) return rc;
+        res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
@@ -1348,7 +1375,7 @@ struct Engine : EngineBase {
             }
         }
         for (int k = 0; k < 3; ++k)                      // :115-117
-            if ((rc = diffuse_T(k + 1, V[k], V0[k]))) return rc;
+            if ((rc = diffuse_T(k + 1, V[k], V0[k], k))) return rc;
         if ((rc = project())) return rc;                 // :120
         // z-slabs: :135's density solve (independent of the velocities; its result is dead, :136 overwrites it) is the work
         // the device does while the reach of each advection travels to the host -- half of its passes here, between the
@@ -1358,6 +1385,7 @@ struct Engine : EngineBase {
         SolveRun dens_run;
         if (split) {
             const T a = diffusion_a();
+            if ((rc = log_residual(5, 0, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
             if ((rc = solve_begin(dens_run, 0, slot[FS_DENS], slot[FS_BUFFER], a, (T)1 + (T)6 * a, S->acc))) return rc;   // :283
             if ((rc = solve_passes(dens_run, (int)dens_run.plan.size() / 2))) return rc;
             HIP_TRY(hipEventRecord(ev_slack, S->stream));
@@ -1381,15 +1409,21 @@ struct Engine : EngineBase {
             int res;
             if ((rc = solve_end(dens_run, &res))) return rc;
             adopt(FS_DENS, res);
+            const T a = diffusion_a();
+            if ((rc = log_residual(5, 1, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
             HIP_TRY(hipEventRecord(ev_slack, S->stream));
         } else if (!S->elide_dead) {                     // :135 (its result is overwritten by :136)
-            if ((rc = diffuse_T(0, FS_DENS, FS_BUFFER))) return rc;
+            if ((rc = diffuse_T(0, FS_DENS, FS_BUFFER, 5))) return rc;
         }
         if ((rc = advect(0, FS_DENS, FS_BUFFER))) return rc;   // :136
         slack_check();
         S->step_no++;
         S->steps_total++;
         if (force_cap > 0) force_step[(size_t)(force_logged++ % force_cap)] = S->steps_total;
+        if (res_cap > 0) {
+            res_ran[(size_t)(res_logged % res_cap)] = res_ran_now;
+            res_step[(size_t)(res_logged++ % res_cap)] = S->steps_total;
+        }
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -1811,27 +1845,29 @@ struct Engine : EngineBase {
 
     // Every rank's plane records (`mine`: `blocks` blocks of g.D records each) -> `all`: rank r's blocks at r * mine.size()
     // (a slab's planes follow the lower slabs' planes).  Collective on slab handles; the host holds everything afterwards.
-    int gather_force_records(const std::vector<double>& mine, std::vector<double>& all)
+    // `what`: "obstacle forces" / "solve residuals" (the records of both travel the same way)
+    int gather_plane_records(const std::vector<double>& mine, std::vector<double>& all, const char* what)
     {
         if (!S->comm.active()) { all = mine; return FS_OK; }
-        if (S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
+        if (S->comm.null_transport) return fail(FS_EINVAL, "%s need the other slabs' planes; the FSNULL transport carries none", what);
         all.assign(mine.size() * (size_t)S->comm.nranks, 0.0);
         if (mine.empty()) return FS_OK;
         return comm_op([&](hipStream_t st) { return S->comm.allgather_host(st, mine.data(), all.data(), mine.size() * sizeof(double), g, S->D); },
-                       "gather of the force records");
+                       "gather of the plane records");
     }
 
     // Sum of the records of global planes 1..D in increasing z, in fp64: `rec(r, zl)` = record of local plane zl of rank r.
     // Single-GPU and slab handles add the same numbers in the same order.
+    // Records of `ncols` columns; column `maxcol` (if any) is a maximum, not a sum.
     template <class F>
-    void combine_planes(F&& rec, double* out5) const
+    void combine_planes(F&& rec, double* out, int ncols = fs::FORCE_REC, int maxcol = -1) const
     {
         const int nr = S->comm.active() ? S->comm.nranks : 1;
-        for (int k = 0; k < fs::FORCE_REC; ++k) out5[k] = 0.0;
+        for (int k = 0; k < ncols; ++k) out[k] = 0.0;
         for (int r = 0; r < nr; ++r)
             for (int zl = 0; zl < g.D; ++zl) {
                 const double* q = rec(r, zl);
-                for (int k = 0; k < fs::FORCE_REC; ++k) out5[k] += q[k];
+                for (int k = 0; k < ncols; ++k) out[k] = (k == maxcol) ? std::fmax(out[k], q[k]) : out[k] + q[k];
             }
     }
 
@@ -1849,7 +1885,7 @@ struct Engine : EngineBase {
         std::vector<double> mine(n), all;
         HIP_TRY(hipMemcpyAsync(mine.data(), force_scratch, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
-        if ((rc = gather_force_records(mine, all))) return rc;
+        if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
         combine_planes([&](int r, int zl) { return &all[(size_t)r * n + (size_t)zl * fs::FORCE_REC]; }, out5);
         if (per_plane) memcpy(per_plane, all.data(), all.size() * sizeof(double));
         return FS_OK;
@@ -1872,7 +1908,7 @@ struct Engine : EngineBase {
             HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, force_slot((first + i) % force_cap, 0), per * sizeof(double),
                                    hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
-        if ((rc = gather_force_records(mine, all))) return rc;
+        if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
         const size_t blob = mine.size();
         for (long i = 0; i < n; ++i) {
             double s[2][fs::FORCE_REC];
@@ -1889,6 +1925,129 @@ struct Engine : EngineBase {
             o[8] = s[1][4];
         }
         force_logged = 0;                                // drained
+        return FS_OK;
+    }
+
+    // ---- residual of the linear solves (residual.h; beyond the reference) ------------------------------------
+    static constexpr int RES_SOLVES = FS_RESIDUAL_LOG_SOLVES;
+    size_t res_plane_doubles() const { return (size_t)fs::RESIDUAL_REC * (size_t)g.D; }
+    // ring slot k, solve j, when = 0 before the first sweep / 1 after the last: g.D plane records
+    double* res_slot(long k, int j, int when) const { return res_ring + (((size_t)k * RES_SOLVES + (size_t)j) * 2 + (size_t)when) * res_plane_doubles(); }
+
+    int ensure_res_partial()
+    {
+        if (!res_partial) HIP_TRY(hipMalloc((void**)&res_partial, fs::residual_partial_doubles(g) * sizeof(double)));
+        return FS_OK;
+    }
+
+    // (re)allocate and clear the ring after fs_set_option("residual_log")
+    int ensure_residual_ring()
+    {
+        if (res_gen == S->residual_log_gen) return FS_OK;
+        if (res_ring) HIP_TRY(hipFree(res_ring));
+        res_ring = nullptr;
+        res_cap = 0;
+        res_logged = 0;
+        res_step.clear();
+        res_ran.clear();
+        res_gen = S->residual_log_gen;
+        if (S->residual_log <= 0) return FS_OK;
+        int rc = ensure_res_partial();
+        if (rc) return rc;
+        const size_t bytes = (size_t)S->residual_log * RES_SOLVES * 2 * res_plane_doubles() * sizeof(double);
+        HIP_TRY(hipMalloc((void**)&res_ring, bytes));
+        HIP_TRY(hipMemsetAsync(res_ring, 0, bytes, S->stream));
+        res_cap = S->residual_log;
+        res_step.assign((size_t)res_cap, 0);
+        res_ran.assign((size_t)res_cap, 0u);
+        return FS_OK;
+    }
+
+    // "residual_log": solve k of the running step, before (when = 0) or after (1) its sweeps, straight into the step's ring
+    // slot on the compute stream (no host sync).  On a z-slab the halo planes of `x` are current at both points: the
+    // producer of x exchanged them (advection, inlet, the zeroed pressure), and so does the last pass of every solve.
+    int log_residual(int k, int when, int b, int x, int rhs, double a, double c)
+    {
+        if (k < 0 || res_cap <= 0 || !in_step) return FS_OK;
+        ScopedSpan sp(S, FAM_RESIDUAL);
+        fs::launch_residual<T>(S->stream, g, b, arr[x], arr[rhs], flags, a, c, res_partial, res_slot(res_logged % res_cap, k, when));
+        if (when == 1) res_ran_now |= 1u << k;
+        return FS_OK;
+    }
+
+    int residual_query(int b, int field, int prev, double a, double c, double* out4, double* per_plane)
+    {
+        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
+        int rc = ensure_flags();
+        if (rc) return rc;
+        // a boundary plane's record reads the neighbour's plane of x: one exchange, on the query's account only
+        if ((rc = halo(arr[slot[field]]))) return rc;
+        if ((rc = ensure_res_partial())) return rc;
+        const size_t n = res_plane_doubles();
+        if (!res_scratch) HIP_TRY(hipMalloc((void**)&res_scratch, n * sizeof(double)));
+        {
+            ScopedSpan sp(S, FAM_RESIDUAL);
+            fs::launch_residual<T>(S->stream, g, b, arr[slot[field]], arr[slot[prev]], flags, a, c, res_partial, res_scratch);
+        }
+        std::vector<double> mine(n), all;
+        HIP_TRY(hipMemcpyAsync(mine.data(), res_scratch, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
+        combine_planes([&](int r, int zl) { return &all[(size_t)r * n + (size_t)zl * fs::RESIDUAL_REC]; }, out4, fs::RESIDUAL_REC, 2);
+        if (per_plane) memcpy(per_plane, all.data(), all.size() * sizeof(double));
+        return FS_OK;
+    }
+    int solve_residual(int b, int field, int prev, double a, double c, double* out4, double* per_plane) override
+    {
+        if (!std::is_same<T, double>::value) { a = (double)(float)a; c = (double)(float)c; }   // what an fp32 solve would use
+        return residual_query(b, field, prev, a, c, out4, per_plane);
+    }
+    int diffuse_residual(int b, int field, int prev, double* out4, double* per_plane) override
+    {
+        const T a = diffusion_a();
+        return residual_query(b, field, prev, (double)a, (double)((T)1 + (T)6 * a), out4, per_plane);
+    }
+
+    int residual_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        int rc = ensure_residual_ring();
+        if (rc) return rc;
+        const long n = res_cap > 0 ? std::min<long>(res_logged, res_cap) : 0;
+        if (n_rows) *n_rows = n;
+        if (n_dropped) *n_dropped = res_logged - n;
+        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
+        if (max_rows < n) return fail(FS_EINVAL, "fs_residual_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
+        const size_t rec = res_plane_doubles(), per = (size_t)RES_SOLVES * 2 * rec;   // one step: six solves, before and after
+        const long first = res_logged - n;
+        std::vector<double> mine((size_t)n * per), all;
+        for (long i = 0; i < n; ++i)
+            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, res_slot((first + i) % res_cap, 0, 0), per * sizeof(double),
+                                   hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
+        const size_t blob = mine.size();
+        const double nan = std::nan("");
+        for (long i = 0; i < n; ++i) {
+            double* o = rows + (size_t)i * FS_RESIDUAL_LOG_COLS;
+            const size_t slot_i = (size_t)((first + i) % res_cap);
+            o[0] = (double)res_step[slot_i];
+            for (int j = 0; j < RES_SOLVES; ++j) {
+                double* q = o + 1 + 5 * j;               // r0_sq, r_sq, r_max, rhs_sq, cells
+                if (!(res_ran[slot_i] >> j & 1u)) { q[0] = q[1] = q[2] = q[3] = nan; q[4] = 0.0; continue; }
+                double s[2][fs::RESIDUAL_REC];
+                for (int when = 0; when < 2; ++when)
+                    combine_planes([&](int r, int zl) {
+                        return &all[(size_t)r * blob + (size_t)i * per + ((size_t)j * 2 + (size_t)when) * rec + (size_t)zl * fs::RESIDUAL_REC]; },
+                        s[when], fs::RESIDUAL_REC, 2);
+                q[0] = s[0][0];
+                q[1] = s[1][0];
+                q[2] = s[1][2];
+                q[3] = s[1][1];
+                q[4] = s[1][3];
+            }
+        }
+        res_logged = 0;                                  // drained
         return FS_OK;
     }
 };
@@ -2032,6 +2191,12 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "force_log: steps kept, 0 (off) .. 1048576");
         s->force_log = (int)n;
         s->force_log_gen++;
+    } else if (k == "residual_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "residual_log: steps kept, 0 (off) .. 1048576");
+        s->residual_log = (int)n;
+        s->residual_log_gen++;
     } else if (k == "dump_async") {
         s->dump_async = (v != "0");
     } else if (k == "fuse_advect") {
@@ -2425,6 +2590,26 @@ int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_d
 {
     ENGINE_OR_RETURN(s);
     return s->eng->force_log_fetch(rows, max_rows, n_rows, n_dropped);
+}
+
+int fs_solve_residual(fs_sim* s, int b, int field, int prev, double a, double c, double out[4], double* per_plane)
+{
+    ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
+    if (!out) return fail(FS_EINVAL, "null output");
+    return s->eng->solve_residual(b, field, prev, a, c, out, per_plane);
+}
+
+int fs_diffuse_residual(fs_sim* s, int b, int field, int prev, double out[4], double* per_plane)
+{
+    ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
+    if (!out) return fail(FS_EINVAL, "null output");
+    return s->eng->diffuse_residual(b, field, prev, out, per_plane);
+}
+
+int fs_residual_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->residual_log_fetch(rows, max_rows, n_rows, n_dropped);
 }
 
 int fs_comm_unique_id(void* id_out)

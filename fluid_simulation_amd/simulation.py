@@ -20,6 +20,38 @@ FORCE_LOG_DTYPE = np.dtype([("step", np.int64), ("s1x", np.float64), ("s1y", np.
                             ("frontal", np.int64), ("fx", np.float64), ("fy", np.float64), ("fz", np.float64),
                             ("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
 
+# Columns of Simulation.residual_log(): fs_residual_log's raw columns (step, then r0_sq_k, r_sq_k, r_max_k, rhs_sq_k,
+# cells_k for the step's six solves k = 0..5: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density), then
+# reduction_k = sqrt(r_sq_k / r0_sq_k)
+RESIDUAL_LOG_DTYPE = np.dtype(
+    [("step", np.int64)] +
+    [(name % k, np.int64 if name.startswith("cells") else np.float64) for k in range(_lib.RESIDUAL_LOG_SOLVES)
+     for name in ("r0_sq_%d", "r_sq_%d", "r_max_%d", "rhs_sq_%d", "cells_%d")] +
+    [("reduction_%d" % k, np.float64) for k in range(_lib.RESIDUAL_LOG_SOLVES)])
+
+
+def solve_reduction(rows):
+    """Reduction factor of each solve of each step, sqrt(r_sq / r0_sq): `rows` is a RESIDUAL_LOG_DTYPE array or raw
+    fs_residual_log rows (..., 31); returns (..., 6) in fp64.  NaN for a solve that did not run (its columns are NaN)
+    and where r0_sq is 0 (nothing to reduce)."""
+    if getattr(rows, "dtype", None) is not None and rows.dtype.names:
+        r0 = np.stack([rows["r0_sq_%d" % k] for k in range(_lib.RESIDUAL_LOG_SOLVES)], axis=-1).astype(np.float64)
+        r1 = np.stack([rows["r_sq_%d" % k] for k in range(_lib.RESIDUAL_LOG_SOLVES)], axis=-1).astype(np.float64)
+    else:
+        raw = np.asarray(rows, dtype=np.float64)
+        r0, r1 = raw[..., 1::5], raw[..., 2::5]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(r0 != 0.0, np.sqrt(r1 / np.where(r0 != 0.0, r0, 1.0)), np.nan)
+
+
+def _residual_dict(out, pp):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rel = float(np.sqrt(np.float64(out[0]) / np.float64(out[1])))
+    r = {"r_sq": float(out[0]), "rhs_sq": float(out[1]), "r_max": float(out[2]), "cells": int(out[3]), "relative": rel}
+    if pp is not None:
+        r["per_plane"] = pp
+    return r
+
 
 def pressure_force(s, frontal, dt, speed, width, height, depth):
     """Force and force coefficients of raw pressure sums (include/fluidsim.h, "pressure force on the obstacles"):
@@ -238,6 +270,45 @@ class Simulation:
         for k, a in enumerate("xyz"):
             rows["f" + a] = force[:, k]
             rows["c" + a] = coeff[:, k]
+        return (rows, dropped.value) if with_dropped else rows
+
+    def solve_residual(self, b, field, prev, a, c, per_plane=False):
+        """Residual of the linearSolver system (b, field, prev, a, c) for the state as it is now (fs_solve_residual;
+        collective on z-slabs; changes nothing): a dict with "r_sq" (sum of r^2 over the free cells), "rhs_sq" (sum of
+        prev^2), "r_max", "cells", "relative" = sqrt(r_sq / rhs_sq), and with per_plane=True "per_plane", (depth, 4)
+        records {r_sq, rhs_sq, r_max, cells} of the global planes 1..depth."""
+        out = np.zeros(_lib.RESIDUAL_COLS, dtype=np.float64)
+        pp = np.zeros((self.depth, _lib.RESIDUAL_COLS), dtype=np.float64) if per_plane else None
+        check(self._L.fs_solve_residual(self._h, b, field, prev, float(a), float(c), out.ctypes.data,
+                                        None if pp is None else pp.ctypes.data))
+        return _residual_dict(out, pp)
+
+    def diffuse_residual(self, b, field, prev, per_plane=False):
+        """The same for the diffusion system of this handle, a = dt * diff * w * h * d and c = 1 + 6 a in its own
+        precision (fs_diffuse_residual)."""
+        out = np.zeros(_lib.RESIDUAL_COLS, dtype=np.float64)
+        pp = np.zeros((self.depth, _lib.RESIDUAL_COLS), dtype=np.float64) if per_plane else None
+        check(self._L.fs_diffuse_residual(self._h, b, field, prev, out.ctypes.data, None if pp is None else pp.ctypes.data))
+        return _residual_dict(out, pp)
+
+    def pressure_residual(self, per_plane=False):
+        """The same for the pressure equation, (0, PRESSURE, DIVERGENCE, 1, 6): how far the last projection's solve got."""
+        return self.solve_residual(0, _lib.PRESSURE, _lib.DIVERGENCE, 1.0, 6.0, per_plane=per_plane)
+
+    def residual_log(self, with_dropped=False):
+        """Drains the per-step residual log (option residual_log=N; fs_residual_log, collective on z-slabs): one row per
+        retained step, oldest first, as a RESIDUAL_LOG_DTYPE structured array.  with_dropped=True returns
+        (rows, number of logged steps the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_residual_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        raw = np.zeros((n.value, _lib.RESIDUAL_LOG_COLS), dtype=np.float64)
+        check(self._L.fs_residual_log(self._h, raw.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        rows = np.zeros(n.value, dtype=RESIDUAL_LOG_DTYPE)
+        for k, name in enumerate(RESIDUAL_LOG_DTYPE.names[:_lib.RESIDUAL_LOG_COLS]):
+            rows[name] = raw[:, k]
+        red = solve_reduction(raw)
+        for k in range(_lib.RESIDUAL_LOG_SOLVES):
+            rows["reduction_%d" % k] = red[:, k]
         return (rows, dropped.value) if with_dropped else rows
 
     def time_sweeps(self, b, field, prev, a, c, reps):

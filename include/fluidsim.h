@@ -106,6 +106,9 @@ int fs_destroy(fs_sim* s);
  *   "force_log"   N >= 0: keep the obstacle pressure forces of the last N steps (fs_force_log); 0 (default) =
  *                 off, and the step launches nothing for it.  Setting it (re)allocates and clears the log.
  *                 May be changed at any time.
+ *   "residual_log" N >= 0 (at most 1048576): keep the residuals of the six linear solves of the last N steps, before and
+ *                 after each solve (fs_residual_log); 0 (default) = off, and the step launches and allocates nothing for
+ *                 it.  Setting it (re)allocates and clears the log.  May be changed at any time.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -208,7 +211,9 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "sweep_pair" (two iterations per launch) "sweep_triple" (three iterations per launch)
  * "divergence" "gradient" "advect" "bounds" "misc" "comm" (z-slab exchanges and gathers)
  * "multigrid" (the coarse-level work of solver "mg"; its level-0 smoothing passes count as
- * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records).  Events are recorded on the handle's own stream. */
+ * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records) "residual" (fs_solve_residual / fs_diffuse_residual and the
+ * "residual_log" records: one launch counted per record, i.e. per solve and point in time -- 12 per step with the log on,
+ * 10 where the dead density solve is elided, 0 with it off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -286,6 +291,48 @@ int fs_surface_case_table(int config, int* edges);
 #define FS_FORCE_LOG_COLS 9
 int fs_obstacle_force(fs_sim* s, double out[5], double* per_plane);
 int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+
+/* ---- residual of the linear solves (beyond the reference: it never evaluates one, no file:line counterpart) ----
+ *
+ * linearSolver(b, x, x0, a, c) (simulation.cpp:251-273) iterates on x = (x0 + a * (sum of the six neighbours)) / c and
+ * applies setBounds(b, x) after each sweep.  A cell is FREE where setBounds leaves it to the sweep: an interior cell with
+ * obs != 1 and, for b = 1, 2, 3, without an in-range solid 6-neighbour (those cells are zeroed, simulation.cpp:227-245).
+ * The inlet column is not special.  For a free cell
+ *     r = (x0 + a * (((((x[i+1] + x[i-1]) + x[j+1]) + x[j-1]) + x[l+1]) + x[l-1])) - c * x
+ * evaluated in fp64 from the stored values (fp32 fields, and the a and c the solve uses, widen exactly), in exactly this
+ * order, without contraction.  Neighbour values are whatever the arrays hold there: ghost cells as setBounds left them,
+ * solid neighbours 0 after a sweep.  Per global z-plane the record is
+ *     { sum r^2, sum x0^2, max |r|, free cells }        (fp64, FS_RESIDUAL_COLS numbers)
+ * over the plane's free cells; the whole-grid record adds the planes' sums in increasing z in fp64 and takes the maximum
+ * of their maxima.  A plane's record is a pure function of that plane, its two z neighbours and (width, height): launch
+ * tuning, slab split and timing cannot change a bit of it, and a z-slab run gives the single-GPU bits.
+ * sqrt(sum r^2 / sum x0^2) is the relative residual.
+ *
+ * fs_solve_residual: the record of the system (b, field, prev, a, c) -- arguments as fs_linear_solver, a and c as doubles
+ * (fp32 handles round them to float first, as their solve would) -- for the state as it is now; it changes nothing.
+ * out = {sum r^2, sum x0^2, max |r|, free cells}; per_plane (may be NULL) receives the record of each global z-plane
+ * 1..d (4 * d doubles).  field == prev is legal (the state a diffusion solve of fs_step starts from).  On z-slab
+ * handles every rank calls it and every rank gets the global result.
+ * fs_diffuse_residual: the same with the handle's own diffusion coefficients, a = dt * diff * w * h * d and c = 1 + 6 a
+ * in the handle's precision (simulation.cpp:282-283): to fs_solve_residual what fs_diffuse is to fs_linear_solver.
+ *
+ * fs_residual_log (option "residual_log" = N): inside fs_step the record of each of the step's six solves -- in step()'s
+ * order diffuse v_x, v_y, v_z (simulation.cpp:115-117), the first projection (:120), the second (:130), diffuse density
+ * (:135) -- is taken before its first sweep and after its last (for solver "mg": around the V-cycles), into a device
+ * ring without a host synchronisation and on the step's own stream.  The call drains the log:
+ * rows[FS_RESIDUAL_LOG_COLS * i + ...] = {step, then for each solve k = 0..5: r0_sq, r_sq, r_max, rhs_sq, cells},
+ * r0_sq = sum r^2 before the solve, the others after it; sqrt(r_sq / r0_sq) is the reduction factor of the solve.  A
+ * solve the step does not run ("elide_dead_density_solve") has NaN in its four real columns and 0 cells; a solve of zero
+ * sweeps has r_sq == r0_sq.  On z-slab handles the density solve is recorded where it begins and where it ends
+ * ("split_density_solve" runs other work in between).  step, oldest-first order, rows = NULL, max_rows and *n_dropped
+ * are as for fs_force_log.  Collective on z-slab handles.  All three need a transport that moves data (FSNULL: FS_EINVAL).
+ */
+#define FS_RESIDUAL_COLS 4
+int fs_solve_residual(fs_sim* s, int b, int field, int prev, double a, double c, double out[4], double* per_plane);
+int fs_diffuse_residual(fs_sim* s, int b, int field, int prev, double out[4], double* per_plane);
+#define FS_RESIDUAL_LOG_SOLVES 6
+#define FS_RESIDUAL_LOG_COLS 31
+int fs_residual_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

@@ -22,6 +22,9 @@
 //   --forces FILE  log the obstacle pressure force of every step (option "force_log") and write it to FILE as CSV:
 //                  fs_force_log's columns, then F = (S1 + S2) h^2 / dt and C = 2 (S1 + S2) / (dt speed^2 N_front)
 //                  (include/fluidsim.h)
+//   --residuals FILE  log the residual of the step's six linear solves before and after each (option "residual_log") and
+//                  write it to FILE as CSV: fs_residual_log's columns, then reduction_k = sqrt(r_sq_k / r0_sq_k);
+//                  may be combined with --forces
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <chrono>
 #include <cmath>
@@ -112,6 +115,37 @@ int write_forces(fs_sim* sim, const char* path, int w, int h, int d, float dt, i
     return ok ? 0 : 1;
 }
 
+// the per-step residual log of the run -> CSV (the columns of Simulation.residual_log() in the Python package)
+int write_residuals(fs_sim* sim, const char* path)
+{
+    long n = 0, dropped = 0;
+    if (fs_residual_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * FS_RESIDUAL_LOG_COLS);
+    if (fs_residual_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step");
+    for (int k = 0; k < FS_RESIDUAL_LOG_SOLVES; ++k) fprintf(fp, ",r0_sq_%d,r_sq_%d,r_max_%d,rhs_sq_%d,cells_%d", k, k, k, k, k);
+    for (int k = 0; k < FS_RESIDUAL_LOG_SOLVES; ++k) fprintf(fp, ",reduction_%d", k);
+    fprintf(fp, "\n");
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * FS_RESIDUAL_LOG_COLS];
+        fprintf(fp, "%ld", (long)r[0]);
+        for (int k = 0; k < FS_RESIDUAL_LOG_SOLVES; ++k) {
+            const double* q = r + 1 + 5 * k;
+            fprintf(fp, ",%.17g,%.17g,%.17g,%.17g,%ld", q[0], q[1], q[2], q[3], (long)q[4]);
+        }
+        for (int k = 0; k < FS_RESIDUAL_LOG_SOLVES; ++k) {
+            const double* q = r + 1 + 5 * k;
+            fprintf(fp, ",%.17g", q[0] != 0.0 ? std::sqrt(q[1] / q[0]) : (double)NAN);
+        }
+        fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "simulation.out: %s: %s\n", what, fs_last_error());
@@ -129,7 +163,7 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir, forces_path;
+    std::string resume_dir, forces_path, residuals_path;
     std::vector<std::pair<std::string, std::string>> options;
 
     auto apply = [&](const std::string& key, const char* val) -> bool {
@@ -149,10 +183,11 @@ int main(int argc, char** argv)
         if (key == "seed") { options.push_back({ "voxel_seed", val }); return true; }
         if (key == "resume") { resume_dir = val; return true; }
         if (key == "forces") { forces_path = val; return true; }
+        if (key == "residuals") { residuals_path = val; return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
-                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces" };
+                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -179,6 +214,7 @@ int main(int argc, char** argv)
     fs_sim* sim = fs_create(width, height, depth, iter, speed, dt, diff, visc, acc);   // simulation.cpp:438
     if (!sim) return die("fs_create");
     if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
+    if (!residuals_path.empty()) options.push_back({ "residual_log", std::to_string(iter) });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
     for (const Stl& s : stls) {
@@ -196,6 +232,7 @@ int main(int argc, char** argv)
     if (fs_sync(sim)) return die("fs_sync");
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
+    if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (json)
         printf("{\"grid\": [%d, %d, %d], \"steps\": %d, \"acc\": %d, \"seconds\": %.6f, \"cells_steps_per_sec\": %.6g}\n",
                width, height, depth, iter, acc, secs, (double)width * height * depth * iter / secs);

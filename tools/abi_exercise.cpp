@@ -27,6 +27,7 @@ static int slab_rank(int rank, const char* id, const char* ascii, const char* du
     char idbuf[FS_COMM_ID_BYTES] = {0};
     snprintf(idbuf, sizeof idbuf, "%s", id);
     CHECK(fs_comm_init(s, rank, 2, idbuf));
+    CHECK(fs_set_option(s, "residual_log", "2"));
     long added = 0;
     CHECK(fs_load_stl(s, ascii, 0.6f, 0.f, 0.f, 0.f, 5.f, 0.f, 0.f, &added));
     CHECK(fs_add_obstacle(s, 9, 7, 16));
@@ -49,6 +50,15 @@ static int slab_rank(int rank, const char* id, const char* ascii, const char* du
     const size_t n = fs_padded_size(s);
     std::vector<float> f(n);
     CHECK(fs_get_field(s, FS_PRESSURE, f.data(), n, 4));
+    {   // the residual log of the slab steps (collective drain) and the collective query with its per-plane records
+        long nr = 0, nd = 0;
+        CHECK(fs_residual_log(s, nullptr, 0, &nr, &nd));
+        std::vector<double> rows((size_t)nr * FS_RESIDUAL_LOG_COLS + 1), planes((size_t)FS_RESIDUAL_COLS * 32);
+        CHECK(fs_residual_log(s, rows.data(), nr, &nr, &nd));
+        double out[FS_RESIDUAL_COLS];
+        CHECK(fs_solve_residual(s, 0, FS_PRESSURE, FS_DIVERGENCE, 1.0, 6.0, out, planes.data()));
+        if (nr != 2 || !(out[3] > 0.0)) { fprintf(stderr, "rank %d: %ld residual rows, %g cells\n", rank, nr, out[3]); return 12; }
+    }
     CHECK(fs_sync(s));
     CHECK(fs_destroy(s));
     printf("slab rank %d ok: schedule %d, velocity x in [%g, %g]\n", rank, plan, mn, mx);
@@ -172,6 +182,24 @@ int main(int argc, char** argv)
         CHECK(fs_get_int(s, "mg_levels", &mgl));
         if (mgl != 3) return 9;
         if (fs_set_option(s, "mg_pre", "0") != FS_EINVAL) return 10;
+        {   // residual of the linear solves: the on-demand queries, then the per-step log through a wrap and a drain
+            double out[FS_RESIDUAL_COLS];
+            std::vector<double> planes((size_t)FS_RESIDUAL_COLS * 20);
+            CHECK(fs_solve_residual(s, 0, FS_PRESSURE, FS_DIVERGENCE, 1.0, 6.0, out, planes.data()));
+            if (!(out[0] >= 0.0) || !(out[3] > 0.0)) return 12;
+            CHECK(fs_diffuse_residual(s, 1, FS_VX, FS_VX, out, nullptr));
+            if (fs_solve_residual(s, 4, FS_DENS, FS_BUFFER, 1.0, 6.0, out, nullptr) != FS_EINVAL) return 13;
+            CHECK(fs_set_option(s, "residual_log", "2"));
+            for (int k = 0; k < 3; ++k) CHECK(fs_run_one(s));
+            long nr = 0, nd = 0;
+            CHECK(fs_residual_log(s, nullptr, 0, &nr, &nd));
+            if (nr != 2 || nd != 1) return 14;
+            std::vector<double> rows((size_t)nr * FS_RESIDUAL_LOG_COLS);
+            if (fs_residual_log(s, rows.data(), 1, &nr, &nd) != FS_EINVAL) return 15;
+            CHECK(fs_residual_log(s, rows.data(), nr, &nr, &nd));
+            if (!(rows[5] > 0.0)) return 16;
+            CHECK(fs_set_option(s, "residual_log", "0"));
+        }
         CHECK(fs_set_option(s, "solver", "gs_lex"));
         CHECK(fs_run_one(s));
         CHECK(fs_destroy(s));
