@@ -83,8 +83,8 @@ struct EngineBase {
     virtual int dump_frame() = 0;
     virtual int time_sweeps(int b, int field, int prev, float a, float c, int reps, double* ms) = 0;
     virtual int apply_solid_cells(const int* cells, long n) = 0;
-    virtual int tuned_shape() const = 0;
-    virtual int tuned_triple() const = 0;
+    virtual int tuned_two() const = 0;      // launch plan ids in use (launch_plan.h), -1 = none
+    virtual int tuned_three() const = 0;
     virtual int halo_depth() const = 0;
     virtual int streamlines(int density, double proximity, int max_length, double step_size, double threshold) = 0;
     virtual int obstacle_surface() = 0;
@@ -106,7 +106,7 @@ struct fs_sim {
     bool fp64 = false;
     int solver = FS_SOLVER_JACOBI;
     float omega = 1.0f;          // relaxation factor of solver=rbsor
-    int plan_two = -2, plan_three = -2;   // "launch_plans": replay these instead of timing (-2: not set)
+    int replay_two = -2, replay_three = -2;   // "launch_plans": replay these plan ids instead of timing (-2: not set)
     int mg_cycles = 4, mg_pre = 1, mg_post = 1, mg_coarse = 30;   // solver=mg: V-cycles per pressure solve, smoothing steps, coarsest-level iterations
     int mg_min_planes = 32;      // z-slabs: a coarse level stays distributed while every rank keeps at least this many of its planes
                                  // (measured, 512^3 as four slabs: 4 -> 203, 16 -> 186, 32 -> 175, 64 -> 152 ms per step; below 32 the
@@ -248,13 +248,15 @@ struct Engine : EngineBase {
     fs::Multigrid<T> mg;                // coarse levels of solver=mg; rebuilt when the flag bytes change
     bool mg_current = false;
     T* coltab = nullptr;                // clamp tables of the advection row kernels: 6 x (H+2)(D+2) (single GPU only)
-    static constexpr int FUSED2 = 64;   // pair_shape >= FUSED2: the two-sweep passes run jacobi_fused_kernel<NL = 2>, plan id - FUSED2
-    int pair_shape = -1;                // fastest two-sweep launch plan for this grid (timed once)
-    int pair_plan_rb = 0;               // fastest plan of jacobi_pair_kernel itself: its red-black / damped passes (rbsor, mg level 0)
+    // launch plan ids (launch_plan.h), chosen once per grid by choose_launch_plans
+    int plan_two = -1;                  // fastest two-sweep plan, of the pair or the fused kernel (-1: not chosen yet)
+    int plan_two_pair = 0;              // fastest plan of jacobi_pair_kernel itself: its red-black / damped passes (rbsor, mg level 0)
                                         // always run that kernel, also where the plain two-sweep passes went to the fused one
-    int tuned_plan_two = -3, tuned_plan_three = -3;   // "launch_plans" values the choices were made under
-    int tuned_fuse = -1, tuned_pair_shape_opt = -1;   // option values the two choices here were timed under
-    int triple_alt = -1;                // >= 0: three sweeps per pass beat two on this grid (launch plan id)
+    int plan_three = -1;                // >= 0: three sweeps per pass beat two on this grid
+    struct TunedFor {                   // what those choices were made under: options, and the "launch_plans" values
+        int fuse = -1, pair_shape = -1, two_kind = -1, replay_two = -3, replay_three = -3;
+        bool operator==(const TunedFor& o) const { return !memcmp(this, &o, sizeof o); }
+    } tuned_for;
     hipStream_t comm_stream = nullptr;  // z-slabs: EVERY transport call runs on this one stream (a communicator is never driven from
                                         // two streams); events order it against the compute stream
     hipEvent_t ev_edges = nullptr, ev_halo = nullptr, ev_int = nullptr, ev_c2x = nullptr;
@@ -389,7 +391,7 @@ struct Engine : EngineBase {
         S->stream = want;
         S->tune.cu_slots = on ? masked_cus : 256;
         S->cus_plan = on ? (S->comm_cus > 0 ? S->comm_cus : 8) : 0;
-        pair_shape = -1;                                 // the launch plans depend on how many CUs a launch can fill
+        plan_two = -1;                                   // the launch plans depend on how many CUs a launch can fill
         return FS_OK;
     }
 
@@ -427,6 +429,16 @@ struct Engine : EngineBase {
             if (i != not_a && i != not_b && !referenced(i)) { held[i] = true; return i; }
         return -1;   // cannot happen: NPOOL covers the worst case of a step
     }
+    // Scratch of a timing run: up to two pool arrays and an event pair, given back on every path out (error paths too).
+    struct Scratch {
+        bool* held; int a = -1, b = -1; hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipError_t events() { hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
+        ~Scratch() { if (a >= 0) held[a] = false; if (b >= 0) held[b] = false; if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+    };
+    // Timed choices: a later candidate has to win by 1.5 %, so that candidates within the noise of each other do not flip from
+    // run to run (the chosen launch plan is part of what profiles/sweep_traffic.json is stamped with)
+    template <class M>
+    static bool beats(M ms, M best) { return ms < best * (M)0.985; }
     bool shared_slot(int f) const
     {
         for (int k = 0; k < FS_NFIELDS; ++k)
@@ -536,32 +548,29 @@ struct Engine : EngineBase {
                      int zl, int second = -1, const fs::PeerPush* push = nullptr)
     {
         const T omega = rb ? rb_omega : (T)0;
+        const bool fused2 = fs::decode_plan(false, plan_two).kind == fs::SweepKernel::Fused2;
         if (levels == 3)
-            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, triple_alt, second, push,
+            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_three, second, push,
                                        &maskplan);
-        else if (levels == 2 && !rb && pair_shape >= FUSED2)
-            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 2, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, pair_shape - FUSED2, second, push);
+        else if (levels == 2 && !rb && fused2)
+            fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 2, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_two, second, push);
         else if (levels == 2)
             fs::launch_jacobi_pair<T>(st, S->tune, g, sc, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl,
-                                      pair_shape >= FUSED2 ? pair_plan_rb : pair_shape, second, omega, rb_damped, push);
+                                      fused2 ? plan_two_pair : plan_two, second, omega, rb_damped, push);
         else
             fs::launch_jacobi<T>(st, S->tune, g, sc, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, second, push);
     }
-    bool two_sweep_kernels() const
-    {
-        return fs::pair_supported<T>(S->tune, g, sc) || fs::fused_supported<T>(S->tune, g, sc, 2);
-    }
+    // what of this grid and the options the launch plans depend on (launch_plan.h)
+    fs::PlanGrid plan_grid() const { return {(int)sizeof(T), g.W, sc.lo_wall && sc.hi_wall, g.zh, S->tune.fuse}; }
+    bool has_kernel(fs::SweepKernel k) const { return fs::plan_supported(plan_grid(), k); }
+    bool two_sweep_kernels() const { return has_kernel(fs::SweepKernel::Pair) || has_kernel(fs::SweepKernel::Fused2); }
     int ensure_tuned(int cur, int rhs, int b, T a, T inv_c)
     {
-        if (two_sweep_kernels() || fs::fused_supported<T>(S->tune, g, sc, 3)) {
-            const int opt = S->tune.pair_shape + 16 * S->tune.two_kind;
-            if (!(pair_shape >= 0 && tuned_fuse == S->tune.fuse && tuned_pair_shape_opt == opt && tuned_plan_two == S->plan_two &&
-                  tuned_plan_three == S->plan_three)) {
-                tuned_fuse = S->tune.fuse;
-                tuned_pair_shape_opt = opt;
-                tuned_plan_two = S->plan_two;
-                tuned_plan_three = S->plan_three;
-                int rc = choose_pair_shape(cur, rhs, b, a, inv_c);
+        if (two_sweep_kernels() || has_kernel(fs::SweepKernel::Three)) {
+            const TunedFor now{S->tune.fuse, S->tune.pair_shape, S->tune.two_kind, S->replay_two, S->replay_three};
+            if (!(plan_two >= 0 && tuned_for == now)) {
+                tuned_for = now;
+                int rc = choose_launch_plans(cur, rhs, b, a, inv_c);
                 if (rc) return rc;
             }
         }
@@ -593,12 +602,12 @@ struct Engine : EngineBase {
     // "overlap" = "auto" (and "comm_cus" = "auto"): the communication schedules are chosen the way launch plans are -- by the
     // clock, once, on the transport the run really uses.  Every candidate runs a chain of the solver's deepest passes with
     // their exchanges between two barriers; what counts is the slowest rank's time (all-reduced, so that every rank takes
-    // the same decision: the schedule must not diverge).  A later candidate has to win by 1.5 %.  The bits do not depend on
+    // the same decision: the schedule must not diverge).  A later candidate has to win by a margin (beats).  The bits do not depend on
     // the choice (tests/test_gpu_slabs.py runs every candidate).
     int choose_overlap(int src, int rhs, int b, T a, T inv_c)
     {
         const bool auto_cus = S->comm_cus < 0 && S->stream_masked;
-        const bool can2 = two_sweep_kernels(), can3 = triple_alt >= 0;
+        const bool can2 = two_sweep_kernels(), can3 = plan_three >= 0;
         const int lv = can3 ? 3 : can2 ? 2 : 1;
         std::vector<int> modes;
         if (S->overlap >= 0) modes.push_back(S->overlap);
@@ -611,13 +620,9 @@ struct Engine : EngineBase {
             return FS_OK;
         }
         const int t0 = acquire(src, rhs), t1 = acquire(src, rhs);
-        struct Release {
-            bool* held; int a, b; hipEvent_t e0 = nullptr, e1 = nullptr;
-            ~Release() { if (a >= 0) held[a] = false; if (b >= 0) held[b] = false; if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-        } rel{held, t0, t1};
+        Scratch rel{held, t0, t1};
         if (t0 < 0 || t1 < 0) return fail(FS_ENOMEM, "array pool exhausted");
-        HIP_TRY(hipEventCreate(&rel.e0));
-        HIP_TRY(hipEventCreate(&rel.e1));
+        HIP_TRY(rel.events());
         const bool tune_log = getenv("FS_TUNE_LOG") != nullptr;
         const int NP = 6;
         double best = 1e300;
@@ -626,7 +631,7 @@ struct Engine : EngineBase {
         for (int mask = 0; mask < (auto_cus ? 2 : 1); ++mask) {
             if (auto_cus) {
                 if ((rc = use_masked_stream(mask == 1))) return rc;
-                if ((rc = choose_pair_shape(src, rhs, b, a, inv_c))) return rc;   // launch plans for that many CUs
+                if ((rc = choose_launch_plans(src, rhs, b, a, inv_c))) return rc;   // launch plans for that many CUs
             }
             for (int mode : modes) {
                 double ms = 0.0;
@@ -653,12 +658,12 @@ struct Engine : EngineBase {
                 if (tune_log)
                     fprintf(stderr, "fluidsim tune: rank %d overlap=%d cu mask %s: %.4f ms per pass here, %.4f on the slowest rank\n",
                             S->comm.rank, mode, mask ? "on" : "off", ms, worst);
-                if (worst < best * 0.985) { best = worst; best_mode = mode; best_mask = mask; }
+                if (beats(worst, best)) { best = worst; best_mode = mode; best_mask = mask; }
             }
         }
         if (auto_cus) {
             if ((rc = use_masked_stream(best_mask == 1))) return rc;
-            if ((rc = choose_pair_shape(src, rhs, b, a, inv_c))) return rc;
+            if ((rc = choose_launch_plans(src, rhs, b, a, inv_c))) return rc;
         }
         if (S->cus_plan < 0) S->cus_plan = 0;
         HIP_TRY(hipDeviceSynchronize());
@@ -747,14 +752,14 @@ struct Engine : EngineBase {
         r.rb = smoother || (S->solver == FS_SOLVER_RBSOR);
         r.omega = smoother ? (T)6 / (T)7 : (T)S->omega;
         r.damped = smoother;
-        if (r.rb && !fs::pair_supported<T>(S->tune, g, sc))
+        if (r.rb && !has_kernel(fs::SweepKernel::Pair))
             return fail(FS_EINVAL, "solver=rbsor / mg needs rows of at most 1024 cells and sweep_fuse >= 2");
         int rc = ensure_tuned(cur, rhs, b, a, r.inv_c);
         if (rc) return rc;
         // The passes of this solve: three sweeps per pass while at least three remain (where that kernel
         // exists and was found faster), then two, then one.  Under z-slabs every rank derives the same list
         // (it fixes the depth of every halo exchange).
-        const bool can2 = two_sweep_kernels(), can3 = triple_alt >= 0;
+        const bool can2 = two_sweep_kernels(), can3 = plan_three >= 0;
         for (int left = sweeps; left > 0;) {
             if (r.rb) { r.plan.push_back(2); left -= 1; continue; }      // an rbsor iteration runs as a two-level pass
             const int lv = (can3 && left >= 3) ? 3 : (can2 && left >= 2) ? 2 : 1;
@@ -847,60 +852,50 @@ struct Engine : EngineBase {
         return solve_end(r, result);
     }
 
-    // Times the candidate launch plans of the two-sweep kernels on this grid -- the pair kernel's workgroup
-    // shapes and the fused kernel's (ids FUSED2 + shape), each x the three best z-chunk counts of the
-    // launcher's model -- two launches each into a scratch array, the second one timed, and keeps the
-    // fastest; then the same for the three-sweep kernel, which is used where a sweep costs less that way.
-    // Every plan computes the same bits, so this only ever changes speed.
-    int choose_pair_shape(int src, int rhs, int b, T a, T inv_c)
+    // Times the candidate launch plans of the two-sweep kernels on this grid (launch_plan.h: the pair kernel's workgroup
+    // shapes and the fused kernel's, each x the three best z-chunk counts of the launcher's model) -- two launches each
+    // into a scratch array, the second one timed -- and keeps the fastest; then the same for the three-sweep kernel,
+    // which is used where a sweep costs less that way.  Every plan computes the same bits, so this only ever changes speed.
+    int choose_launch_plans(int src, int rhs, int b, T a, T inv_c)
     {
-        pair_shape = 0;
-        pair_plan_rb = 0;
-        triple_alt = -1;
+        plan_two = 0;
+        plan_two_pair = 0;
+        plan_three = -1;
+        const fs::PlanGrid G = plan_grid();
         // "launch_plans" = "<two-sweep id>,<three-sweep id>" (as fs_get_int "pair_shape" / "triple_plan" report them): replay
         // the plans of another run instead of timing (tools/make_profiles.sh: the counter passes must run the plans the
         // bench line ran, and the clock is different under counter collection); -1 = time as usual / no such kernel.
-        // An id that names a kernel or shape this grid does not have is refused, not run.
-        const bool replay = S->plan_two >= -1 && S->plan_three >= -1 && (S->plan_two >= 0 || S->plan_three >= 0);
-        if (replay) {
-            if (S->plan_two >= FUSED2) {
-                const int id = S->plan_two - FUSED2;
-                if (!fs::fused_supported<T>(S->tune, g, sc, 2) || (id & 7) >= fs::fused_shape_count<T>(g, 2) || (id >> 3) > 2)
-                    return fail(FS_EINVAL, "launch_plans: two-sweep plan %d names a fused-kernel shape this grid does not have", S->plan_two);
-            } else if (S->plan_two >= 0) {
-                if (!fs::pair_supported<T>(S->tune, g, sc) || (S->plan_two & 7) >= fs::pair_shape_count<T>(g) || (S->plan_two >> 3) > 2)
-                    return fail(FS_EINVAL, "launch_plans: two-sweep plan %d names a pair-kernel shape this grid does not have", S->plan_two);
-            }
-            if (S->plan_three >= 0 && fs::fused_supported<T>(S->tune, g, sc, 3) &&
-                ((S->plan_three & 7) >= fs::fused_shape_count<T>(g, 3) || (S->plan_three >> 3) > 2))
-                return fail(FS_EINVAL, "launch_plans: three-sweep plan %d names a shape this grid does not have", S->plan_three);
-            if (S->plan_two >= 0) pair_shape = S->plan_two;
-            if (pair_shape < FUSED2) pair_plan_rb = pair_shape;
-            triple_alt = (S->plan_three >= 0 && fs::fused_supported<T>(S->tune, g, sc, 3)) ? S->plan_three : -1;
+        if (S->replay_two >= -1 && S->replay_three >= -1 && (S->replay_two >= 0 || S->replay_three >= 0)) {
+            const fs::Replay two = fs::check_replay(G, false, S->replay_two), three = fs::check_replay(G, true, S->replay_three);
+            const bool fused2 = fs::decode_plan(false, S->replay_two).kind == fs::SweepKernel::Fused2;
+            if (two == fs::Replay::Refuse)
+                return fail(FS_EINVAL, "launch_plans: two-sweep plan %d names a %s-kernel shape this grid does not have", S->replay_two,
+                            fused2 ? "fused" : "pair");
+            if (three == fs::Replay::Refuse)
+                return fail(FS_EINVAL, "launch_plans: three-sweep plan %d names a shape this grid does not have", S->replay_three);
+            if (two == fs::Replay::Use) plan_two = S->replay_two;
+            if (!fused2) plan_two_pair = plan_two;
+            if (three == fs::Replay::Use) plan_three = S->replay_three;
             return FS_OK;
         }
-        int tmp = acquire(src, rhs);
+        Scratch rel{held, acquire(src, rhs)};
+        const int tmp = rel.a;
         if (tmp < 0) return fail(FS_ENOMEM, "array pool exhausted");
-        struct Release {                                   // error paths must not leak the scratch arrays or the events
-            bool* held; int id, id2 = -1; hipEvent_t e0 = nullptr, e1 = nullptr;
-            ~Release() { held[id] = false; if (id2 >= 0) held[id2] = false; if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-        } rel{held, tmp};
         if (src == rhs) {
             // the first solve of a step reads iterate and right-hand side from ONE array (the snapshot alias): a
             // third less HBM traffic than every later pass, which would rank the candidates for the wrong regime
-            const int copy = acquire(src, tmp);
-            if (copy < 0) return fail(FS_ENOMEM, "array pool exhausted");
-            rel.id2 = copy;
-            fs::launch_copy<T>(S->stream, g, arr[src], arr[copy]);
-            rhs = copy;
+            rel.b = acquire(src, tmp);
+            if (rel.b < 0) return fail(FS_ENOMEM, "array pool exhausted");
+            fs::launch_copy<T>(S->stream, g, arr[src], arr[rel.b]);
+            rhs = rel.b;
         }
-        HIP_TRY(hipEventCreate(&rel.e0));
-        HIP_TRY(hipEventCreate(&rel.e1));
+        HIP_TRY(rel.events());
         hipEvent_t e0 = rel.e0, e1 = rel.e1;
         const bool tune_log = getenv("FS_TUNE_LOG") != nullptr;   // development: print every candidate's time
         auto timed = [&](int levels, int cand, float* ms) -> int {
-            const int keep_pair = pair_shape, keep_triple = triple_alt;
-            if (levels == 3) triple_alt = cand; else pair_shape = cand;
+            int& plan = levels == 3 ? plan_three : plan_two;
+            const int keep = plan;
+            plan = cand;
             int rc = FS_OK;
             for (int rep = 0; rep < 2 && !rc; ++rep) {
                 if (hipEventRecord(e0, S->stream) != hipSuccess) { rc = fail(FS_EHIP, "hipEventRecord"); break; }
@@ -909,58 +904,34 @@ struct Engine : EngineBase {
                     hipEventElapsedTime(ms, e0, e1) != hipSuccess)
                     rc = fail(FS_EHIP, "timing a sweep launch plan failed: %s", hipGetErrorString(hipGetLastError()));
             }
-            pair_shape = keep_pair;
-            triple_alt = keep_triple;
+            plan = keep;
             if (tune_log && !rc)
                 fprintf(stderr, "fluidsim tune: %dx%dx%d %s levels=%d plan=%d  %.4f ms per pass\n", g.W, g.H, g.D,
                         sizeof(T) == 8 ? "fp64" : "fp32", levels, cand, *ms);
             return rc;
         };
-        float best = 1e30f, best_pair = 1e30f;
-        int best_cand = -1;
-        auto consider2 = [&](int cand) -> int {
-            float ms = 1e30f;
-            int rc = timed(2, cand, &ms);
-            if (rc) return rc;
-            // a later candidate has to win by 1.5 %: plans within the noise of each other must not flip from run to run
-            // (the chosen plan is part of what profiles/sweep_traffic.json is stamped with)
-            if (ms < best * 0.985f) { best = ms; best_cand = cand; }
-            if (cand < FUSED2 && ms < best_pair * 0.985f) { best_pair = ms; pair_plan_rb = cand; }
-            return FS_OK;
+        // the fastest two-sweep plan overall, the fastest of the pair kernel alone, the fastest three-sweep plan
+        float best2 = 1e30f, best2_pair = 1e30f, best3 = 1e30f;
+        int cand2 = -1, cand3 = -1, rc = FS_OK;
+        auto time_all = [&](int levels, const std::vector<int>& cands, float& best, int& pick) {
+            for (size_t i = 0; i < cands.size() && !rc; ++i) {
+                float ms = 1e30f;
+                if ((rc = timed(levels, cands[i], &ms))) return;
+                if (beats(ms, best)) { best = ms; pick = cands[i]; }
+                if (levels == 2 && fs::decode_plan(false, cands[i]).kind == fs::SweepKernel::Pair && beats(ms, best2_pair)) {
+                    best2_pair = ms;
+                    plan_two_pair = cands[i];
+                }
+            }
         };
-        // options: pair_shape > 0 forces a workgroup shape of the pair kernel, two_sweep_kernel one of the two kernels
-        const bool have_fused2 = fs::fused_supported<T>(S->tune, g, sc, 2);
-        const bool forced_pair = S->tune.pair_shape > 0 || S->tune.two_kind == 1 || !have_fused2;
-        const bool forced_fused = !forced_pair && S->tune.two_kind == 2;
-        if (fs::pair_supported<T>(S->tune, g, sc) && !forced_fused)
-            for (int shape = 0; shape < fs::pair_shape_count<T>(g); ++shape)
-                for (int alt = 0; alt < 3; ++alt) {      // candidate id = shape + 8 * (rank of the chunk count)
-                    int rc = consider2(shape + 8 * alt);
-                    if (rc) return rc;
-                }
-        if (have_fused2 && !forced_pair)
-            for (int shape = 0; shape < fs::fused_shape_count<T>(g, 2); ++shape)
-                for (int alt = 0; alt < 3; ++alt) {
-                    int rc = consider2(FUSED2 + shape + 8 * alt);
-                    if (rc) return rc;
-                }
-        if (best_cand >= 0) pair_shape = best_cand;
+        time_all(2, fs::two_sweep_candidates(G, S->tune.pair_shape, S->tune.two_kind), best2, cand2);
+        if (cand2 >= 0) plan_two = cand2;
         // three sweeps per pass, where the kernel exists for this grid: keep it if a sweep costs less
-        if (fs::fused_supported<T>(S->tune, g, sc, 3)) {
-            float best3 = 1e30f;
-            int alt3 = -1;
-            for (int shape = 0; shape < fs::fused_shape_count<T>(g, 3); ++shape)
-                for (int alt = 0; alt < 3; ++alt) {
-                    const int cand = shape + 8 * alt;
-                    float ms = 1e30f;
-                    int rc = timed(3, cand, &ms);
-                    if (rc) return rc;
-                    if (ms < best3 * 0.985f) { best3 = ms; alt3 = cand; }
-                }
-            // fuse 4 forces it (tests, tuning); z-slab ranks must all take the same decision (it fixes the
-            // exchange schedule), so there it is not left to each rank's clock
-            if (S->tune.fuse >= 4 || S->comm.active() || best_cand < 0 || best3 / 3.0f < best / 2.0f) triple_alt = alt3;
-        }
+        if (!rc) time_all(3, fs::kernel_candidates(G, fs::SweepKernel::Three), best3, cand3);
+        if (rc) return rc;
+        // fuse 4 forces it (tests, tuning); z-slab ranks must all take the same decision (it fixes the
+        // exchange schedule), so there it is not left to each rank's clock
+        if (S->tune.fuse >= 4 || S->comm.active() || cand2 < 0 || best3 / 3.0f < best2 / 2.0f) plan_three = cand3;
         return FS_OK;
     }
 
@@ -1051,7 +1022,7 @@ struct Engine : EngineBase {
     }
     int multigrid_solve(int field, int prev, int* result)
     {
-        if (S->mg_cycles > 0 && !fs::pair_supported<T>(S->tune, g, sc))
+        if (S->mg_cycles > 0 && !has_kernel(fs::SweepKernel::Pair))
             return fail(FS_EINVAL, "solver=mg needs rows of at most 1024 cells and sweep_fuse >= 2");
         const bool slabs = S->comm.active();
         fs::MgHooks<T> hooks;
@@ -1513,9 +1484,9 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int tuned_shape() const override { return pair_shape; }
+    int tuned_two() const override { return plan_two; }
     int halo_depth() const override { return g.zh; }
-    int tuned_triple() const override { return triple_alt; }
+    int tuned_three() const override { return plan_three; }
 
     // ---- the viewer's streamlines (GUI/utils.py:118-213) -------------------------------------
     // The device integrates every seed in both directions; what is left for the host is the
@@ -1787,19 +1758,15 @@ struct Engine : EngineBase {
         if (reps < 1) return fail(FS_EINVAL, "reps must be >= 1");
         int s1 = acquire(slot[field], slot[prev]);
         int s2 = acquire(slot[field], slot[prev]);
+        Scratch rel{held, s1, s2};
         if (s1 < 0 || s2 < 0) return fail(FS_ENOMEM, "array pool exhausted");
         const T inv_c = (T)1 / (T)c;
-        struct Release {                                   // error paths must not leak the scratch arrays or the events
-            bool* held; int a, b; hipEvent_t e0 = nullptr, e1 = nullptr;
-            ~Release() { held[a] = held[b] = false; if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-        } rel{held, s1, s2};
         {                                                  // same launch plans as solve(); tuned BEFORE the clock starts
             int rc2 = ensure_tuned(slot[field], slot[prev], b, (T)a, inv_c);
             if (rc2) return rc2;
         }
-        const bool can2 = two_sweep_kernels(), can3 = triple_alt >= 0;
-        HIP_TRY(hipEventCreate(&rel.e0));
-        HIP_TRY(hipEventCreate(&rel.e1));
+        const bool can2 = two_sweep_kernels(), can3 = plan_three >= 0;
+        HIP_TRY(rel.events());
         hipEvent_t e0 = rel.e0, e1 = rel.e1;
         // one untimed sweep to fault in code and scratch
         launch_pass(S->stream, 1, false, arr[slot[field]], arr[slot[prev]], arr[s1], b, (T)a, inv_c, 1, g.D);
@@ -2167,8 +2134,8 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         int two = -2, three = -2;
         if (sscanf(value, "%d,%d", &two, &three) != 2 || two < -1 || three < -1 || two > 127 || three > 31)
             return fail(FS_EINVAL, "launch_plans: \"<two-sweep plan id>,<three-sweep plan id>\" (-1 = none)");
-        s->plan_two = two;
-        s->plan_three = three;
+        s->replay_two = two;
+        s->replay_three = three;
     } else if (k == "sor_omega") {
         const float om = (float)atof(value);
         if (!(om > 0.0f && om < 2.0f)) return fail(FS_EINVAL, "sor_omega must lie in (0, 2)");
@@ -2283,9 +2250,10 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "local_depth") *out = s->comm.active() ? s->comm.local_depth(s->D) : s->D;
     else if (n == "z_offset") *out = s->comm.active() ? s->comm.z_offset(s->D) : 0;
     else if (n == "last_advect_reach") *out = s->last_reach;
-    else if (n == "pair_shape") *out = s->eng ? s->eng->tuned_shape() : -1;
-    else if (n == "triple_plan") *out = s->eng ? s->eng->tuned_triple() : -1;
-    else if (n == "two_sweep_fused") *out = (s->eng && s->eng->tuned_shape() >= 64) ? 1 : 0;   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
+    else if (n == "pair_shape") *out = s->eng ? s->eng->tuned_two() : -1;
+    else if (n == "triple_plan") *out = s->eng ? s->eng->tuned_three() : -1;
+    else if (n == "two_sweep_fused")   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
+        *out = (s->eng && fs::decode_plan(false, s->eng->tuned_two()).kind == fs::SweepKernel::Fused2) ? 1 : 0;
     else if (n == "halo_depth") *out = s->eng ? s->eng->halo_depth() : 0;
     else if (n == "mg_levels") *out = s->eng ? s->eng->multigrid_levels() : 0;          // levels of the last solver=mg solve, level 0 included
     else if (n == "mg_first_replicated") *out = s->eng ? s->eng->multigrid_first_replicated() : 0;   // ... the first held whole by every rank

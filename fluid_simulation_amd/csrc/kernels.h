@@ -2,6 +2,7 @@
 // kernels (kernels.hip, voxelize.hip).  Internal to libfluidsim.so.
 #pragma once
 #include "chunk_plan.h"
+#include "launch_plan.h"
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
@@ -104,32 +105,22 @@ void launch_jacobi(hipStream_t st, const SweepTune& tune, const GridDesc& g, con
 // second_first >= 0: ALSO compute the equally long range starting there, in the same launch (a
 // slab's two boundary regions); push: see PeerPush (plain Jacobi passes over one range only)
 
-// Two sweeps in one pass (temporal blocking); same result as two launch_jacobi calls.
-// Needs W <= 1024; on a z-slab additionally two halo planes per side (g.zh == 2), current in
-// `src`, and one current halo plane of `rhs` and `flags`.
-template <class T>
-bool pair_supported(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc);
+// Two sweeps in one pass (temporal blocking); same result as two launch_jacobi calls.  Which grids have the kernel, and the
+// halo planes a z-slab needs for it: launch_plan.h, plan_supported (current in `src`; one plane less of `rhs` and `flags`).
+// plan = a two-sweep id of the pair kernel (launch_plan.h).
 template <class T>
 void launch_jacobi_pair(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src, const T* rhs,
-                        T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int shape,
+                        T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
                         int second_first = -1, T omega = (T)0, bool damped = false, const PeerPush* push = nullptr);
 // omega != 0: one red-black SOR iteration instead; with `damped`, two Jacobi sweeps damped by omega (q + omega*(r - q))
-// NL = `levels` (2 or 3) sweeps per pass, register-centred (sweep_fused.hip): fp32 x 3 for rows up to 512
-// cells, fp32 x 2 for rows of 513..1024 cells, fp64 x 2 for rows up to 512 cells.  On a z-slab `src` needs
-// `levels` current halo planes per side, `rhs` and `flags` levels-1.  plan = workgroup shape
-// (0 .. fused_shape_count-1) + 8 * (which of the launcher's three best z-chunk counts); second_first as above.
-template <class T>
-bool fused_supported(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels);
-template <class T>
-int fused_shape_count(const GridDesc& g, int levels);
+// NL = `levels` (2 or 3) sweeps per pass, register-centred (sweep_fused.hip).  On a z-slab `src` needs `levels` current halo
+// planes per side, `rhs` and `flags` levels-1.  plan = the three-sweep id, or the two-sweep id of the fused kernel;
+// second_first as above.
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
                          int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr);
 // mp: the single-GPU clean table (fp32 three sweeps only; nullptr = no mask-free body)
-// number of workgroup shapes (0 .. count-1) worth timing for this grid; results do not depend on the shape
-template <class T>
-int pair_shape_count(const GridDesc& g);
 
 template <class T>
 void launch_gs_lex(hipStream_t st, const GridDesc& g, T* q, const T* rhs, const uint8_t* flags, int b, T a, T inv_c,

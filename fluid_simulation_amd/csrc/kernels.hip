@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "kernels_dev.h"
+#include <type_traits>
 
 namespace fs {
 
@@ -526,8 +527,8 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_pair_kernel(GridDesc g, 
 
 template <class T, int NXW, int NYW>
 static void launch_pair_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
-                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int alt,
-                          int second_first, T omega, bool damped, const PeerPush* push)
+                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last,
+                          const SweepShape& shape, int alt, int second_first, T omega, bool damped, const PeerPush* push)
 {
     // omega == 0: two Jacobi sweeps; otherwise one red-black SOR iteration with that relaxation factor, or (damped)
     // two Jacobi sweeps damped by it
@@ -536,10 +537,9 @@ static void launch_pair_v(hipStream_t st, const SweepTune& tune, const GridDesc&
     auto kernel = pushing ? jacobi_pair_kernel<T, NXW, NYW, 0, true>
                   : (omega == (T)0) ? jacobi_pair_kernel<T, NXW, NYW, 0, false>
                   : damped ? jacobi_pair_kernel<T, NXW, NYW, 2, false> : jacobi_pair_kernel<T, NXW, NYW, 1, false>;
-    constexpr int BY = NYW * 2;
     const int planes = z_last - z_first + 1;
     if (planes <= 0) return;
-    const int nbands = (g.H + (BY - 2) - 1) / (BY - 2);
+    const int nbands = plan_bands(g.H, shape);
     if (second_first >= 0) {
         // two equally long ranges (the slab's two boundary regions) as two chunks of one launch
         hipLaunchKernelGGL(kernel, dim3(nbands * 2), dim3(NXW * NYW * 64), 0, st, g, sc, src,
@@ -547,31 +547,9 @@ static void launch_pair_v(hipStream_t st, const SweepTune& tune, const GridDesc&
                            second_first - z_first, nbands, nbands * 2, omega, pp);
         return;
     }
-    // z chunks: each re-reads 4 level-0 planes and recomputes 2 level-1 planes, so keep them
-    // long; pick the count that fills the CUs most evenly (one workgroup per CU)
-    // model: fraction of CU slots filled x useful fraction of a chunk's planes; `alt` picks the
-    // alt-th best chunk count by that model (the host driver times alt = 0, 1, 2 once per grid,
-    // because how the block count falls against the 256 CUs matters more than the model knows)
-    int cand_nzc[3] = {1, 1, 1};
-    double cand_eff[3] = {-1.0, -1.0, -1.0};
+    // z chunks: each re-reads 4 level-0 planes and recomputes 2 level-1 planes (launch_plan.h: chunk_len)
     const int slots = tune.cu_slots > 0 ? tune.cu_slots : 256;
-    for (int nzc = 1; nzc <= 64 && (nzc == 1 || planes / nzc >= 12); ++nzc) {
-        const long blocks = (long)nbands * nzc;
-        const long rounds = (blocks + slots - 1) / slots;
-        const int len = (planes + nzc - 1) / nzc;
-        const double eff = (double)blocks / (double)(rounds * slots) * (double)len / (double)(len + 3);
-        for (int k = 0; k < 3; ++k)
-            if (eff > cand_eff[k] + 1e-9) {
-                for (int j = 2; j > k; --j) { cand_eff[j] = cand_eff[j - 1]; cand_nzc[j] = cand_nzc[j - 1]; }
-                cand_eff[k] = eff;
-                cand_nzc[k] = nzc;
-                break;
-            }
-    }
-    int pick = alt < 0 ? 0 : (alt > 2 ? 2 : alt);
-    while (pick > 0 && cand_eff[pick] < 0.0) --pick;
-    const int best_nzc = cand_nzc[pick];
-    int zc_len = (planes + best_nzc - 1) / best_nzc;
+    int zc_len = chunk_len(planes, nbands, alt, chunk_min_len(SweepKernel::Pair), chunk_overlap(SweepKernel::Pair, 2), slots);
     if (tune.pair_zc > 0) zc_len = tune.pair_zc < planes ? tune.pair_zc : planes;
     const int nzc = (planes + zc_len - 1) / zc_len;
     const int nblk = nbands * nzc;
@@ -579,52 +557,37 @@ static void launch_pair_v(hipStream_t st, const SweepTune& tune, const GridDesc&
                        dst, flags, b, a, inv_c, z_first, z_last, zc_len, zc_len, nbands, nblk, omega, pp);
 }
 
+// The builds of jacobi_pair_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them).
+using PairBuildsF32 = Builds<Build<2, 1, 12, 2>, Build<2, 1, 8, 2>, Build<2, 1, 10, 2>, Build<2, 1, 16, 2>, Build<2, 2, 6, 2>,
+                             Build<2, 2, 4, 2>, Build<2, 2, 5, 2>, Build<2, 2, 8, 2>, Build<2, 3, 4, 2>, Build<2, 4, 3, 2>>;
+using PairBuildsF64 = Builds<Build<2, 1, 8, 2>, Build<2, 2, 4, 2>, Build<2, 3, 3, 2>, Build<2, 4, 2, 2>>;
+static_assert(PairBuildsF32::covers(4, SweepKernel::Pair) && PairBuildsF64::covers(8, SweepKernel::Pair),
+              "a pair-kernel shape of SHAPE_TABLE has no build here");
+
+// plan = two-sweep id of the pair kernel (< 0: plan 0).  All plans give identical results; the host driver times them once
+// per grid and keeps the fastest.
 template <class T>
-bool pair_supported(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc)
+void launch_jacobi_pair(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src, const T* rhs,
+                        T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan, int second_first,
+                        T omega, bool damped, const PeerPush* push)
 {
-    const bool whole = sc.lo_wall && sc.hi_wall;
-    return (whole || g.zh >= 2) && g.W <= 1024 && tune.fuse >= 2;
+    PlanId p = decode_plan(false, plan);
+    if (sizeof(T) == 4 && tune.pair_shape > 0) p.shape = tune.pair_shape;   // forced shape: fp32 builds only
+    const SweepShape* shape = launch_shape(sizeof(T), SweepKernel::Pair, g.W, p.shape);
+    if (!shape) return;                                  // rows above 1024 cells: plan_supported is false
+    using List = std::conditional_t<sizeof(T) == 4, PairBuildsF32, PairBuildsF64>;
+    List::run(*shape, [&](auto build) {
+        using B = decltype(build);
+        launch_pair_v<T, B::NXW, B::NYW>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, *shape, p.alt,
+                                         second_first, omega, damped, push);
+    });
 }
-template bool pair_supported<float>(const SweepTune&, const GridDesc&, const SlabCtx&);
-template bool pair_supported<double>(const SweepTune&, const GridDesc&, const SlabCtx&);
-
-template <>
-int pair_shape_count<float>(const GridDesc& g) { return (g.W <= 512) ? 3 : 1; }
-template <>
-int pair_shape_count<double>(const GridDesc&) { return 1; }
-
-template <>
-void launch_jacobi_pair<float>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const float* src,
-                               const float* rhs, float* dst, const uint8_t* flags, int b, float a, float inv_c, int z_first,
-                               int z_last, int shape, int second_first, float omega, bool damped, const PeerPush* push)
-{
-    // shape: 0 = 12 waves (768 threads, <=168 VGPRs), 2 = 10 waves, 1 = 8 waves, 3 = 16 waves (spills;
-    // tuning tool only).  All shapes give identical results; the host driver times 0..count-1 once per
-    // grid and keeps the fastest (band count vs CU count decides, e.g. 10 waves at 512^3, 12 at 256^3).
-    const int nxw = (g.W + 255) / 256;
-    if (shape < 0) shape = 0;
-    const int alt = shape >> 3;                          // which of the three best chunk counts
-    shape &= 7;
-    if (tune.pair_shape > 0) shape = tune.pair_shape;
-#define FS_PAIR(NX, NY) launch_pair_v<float, NX, NY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, omega, damped, push)
-    if (nxw == 1) { if (shape == 1) FS_PAIR(1, 8); else if (shape == 2) FS_PAIR(1, 10); else if (shape == 3) FS_PAIR(1, 16); else FS_PAIR(1, 12); }
-    else if (nxw == 2) { if (shape == 1) FS_PAIR(2, 4); else if (shape == 2) FS_PAIR(2, 5); else if (shape == 3) FS_PAIR(2, 8); else FS_PAIR(2, 6); }
-    else if (nxw == 3) FS_PAIR(3, 4);
-    else FS_PAIR(4, 3);
-#undef FS_PAIR
-}
-template <>
-void launch_jacobi_pair<double>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const double* src,
-                                const double* rhs, double* dst, const uint8_t* flags, int b, double a, double inv_c,
-                                int z_first, int z_last, int shape, int second_first, double omega, bool damped, const PeerPush* push)
-{
-    const int alt = shape < 0 ? 0 : (shape >> 3);
-    const int nxw = (g.W + 255) / 256;   // LDS: 4 * BY * TW * 8 bytes must stay under 160 KB
-    if (nxw == 1) launch_pair_v<double, 1, 8>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, omega, damped, push);
-    else if (nxw == 2) launch_pair_v<double, 2, 4>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, omega, damped, push);
-    else if (nxw == 3) launch_pair_v<double, 3, 3>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, omega, damped, push);
-    else launch_pair_v<double, 4, 2>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, omega, damped, push);
-}
+template void launch_jacobi_pair<float>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const float*, const float*,
+                                        float*, const uint8_t*, int, float, float, int, int, int, int, float, bool,
+                                        const PeerPush*);
+template void launch_jacobi_pair<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const double*,
+                                         const double*, double*, const uint8_t*, int, double, double, int, int, int, int, double,
+                                         bool, const PeerPush*);
 
 // =====================================================================================
 // Reference-order in-place sweep (verification mode, single GPU).

@@ -45,6 +45,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "kernels_dev.h"
+#include <type_traits>
 
 namespace fs {
 
@@ -543,14 +544,6 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
 // ---------------------------------------------------------------------------------------------
 // launch plans
 // ---------------------------------------------------------------------------------------------
-template <int NL>
-static int fused_bands(int H, int BY)
-{
-    // band k outputs rows k (BY - 2 (NL-1)) + 1 .. (k + 1)(BY - 2 (NL-1)), the last band up to row H
-    const int step = BY - 2 * (NL - 1);
-    return (H + step - 1) / step;
-}
-
 // The mask-free build's per-workgroup table of one launch shape on the device: made and uploaded at its first launch after a mask
 // change (host work and one upload, no wait on the device), then reused.  z chunks balanced per band by `cost`, or equal ones of
 // zc_len planes when it is off.
@@ -593,14 +586,14 @@ void MaskPlan::release()
 
 template <class T, int NL, int NXW, int NYW, int RY>
 static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
-                           const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int alt,
-                           int second_first, const PeerPush* push, MaskPlan* mp)
+                           const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last,
+                           const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp)
 {
     const PeerPush pp = (push && second_first < 0) ? *push : PeerPush();
     constexpr int BY = NYW * RY, THREADS = NXW * NYW * 64;
     const int planes = z_last - z_first + 1;
     if (planes <= 0) return;
-    const int nbands = fused_bands<NL>(g.H, BY);
+    const int nbands = plan_bands(g.H, shape);
     const bool aligned = (g.W == NXW * 256);
     const bool whole = sc.lo_wall && sc.hi_wall && z_first == 1 && z_last == g.D && second_first < 0;
     int zc_len, z_stride, nblk;
@@ -611,28 +604,11 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
         z_last = second_first + planes - 1;
         nblk = nbands * 2;
     } else {
-        // z chunks re-read 2 NL level-0 planes and recompute the levels below the last on 2(NL-1) + ... planes:
-        // keep them long; pick the count that fills the CUs most evenly.  `alt` picks the alt-th best chunk
-        // count by this model (the host driver times alt = 0, 1, 2 once per grid).
-        int cand_nzc[3] = {1, 1, 1};
-        double cand_eff[3] = {-1.0, -1.0, -1.0};
+        // z chunks re-read 2 NL level-0 planes and recompute the levels below the last on 2(NL-1) + ... planes
+        // (launch_plan.h: chunk_len)
+        const SweepKernel kind = NL == 3 ? SweepKernel::Three : SweepKernel::Fused2;
         const int slots = tune.cu_slots > 0 ? tune.cu_slots : 256;
-        for (int nzc = 1; nzc <= 64 && (nzc == 1 || planes / nzc >= 16); ++nzc) {
-            const long blocks = (long)nbands * nzc;
-            const long rounds = (blocks + slots - 1) / slots;
-            const int len = (planes + nzc - 1) / nzc;
-            const double eff = (double)blocks / (double)(rounds * slots) * (double)len / (double)(len + 2 * NL - 1);
-            for (int k = 0; k < 3; ++k)
-                if (eff > cand_eff[k] + 1e-9) {
-                    for (int j = 2; j > k; --j) { cand_eff[j] = cand_eff[j - 1]; cand_nzc[j] = cand_nzc[j - 1]; }
-                    cand_eff[k] = eff;
-                    cand_nzc[k] = nzc;
-                    break;
-                }
-        }
-        int pick = alt < 0 ? 0 : (alt > 2 ? 2 : alt);
-        while (pick > 0 && cand_eff[pick] < 0.0) --pick;
-        zc_len = (planes + cand_nzc[pick] - 1) / cand_nzc[pick];
+        zc_len = chunk_len(planes, nbands, alt, chunk_min_len(kind), chunk_overlap(kind, NL), slots);
         if (tune.pair_zc > 0) zc_len = tune.pair_zc < planes ? tune.pair_zc : planes;
         const int nzc = (planes + zc_len - 1) / zc_len;
         z_stride = zc_len;
@@ -670,88 +646,48 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
 #undef FS_LAUNCH
 }
 
-// Which (T, NL) this file has a kernel for on this grid.  On a z-slab the halo must be NL planes deep.
-template <>
-bool fused_supported<float>(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels)
-{
-    const bool whole = sc.lo_wall && sc.hi_wall;
-    if (!whole && g.zh < levels) return false;
-    if (levels == 3) return g.W <= 512 && tune.fuse >= 3;
-    if (levels == 2) return g.W > 512 && g.W <= 1024 && tune.fuse >= 2;
-    return false;
-}
-template <>
-bool fused_supported<double>(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels)
-{
-    const bool whole = sc.lo_wall && sc.hi_wall;
-    if (!whole && g.zh < levels) return false;
-    return levels == 2 && g.W <= 512 && tune.fuse >= 2;
-}
+// The builds of jacobi_fused_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them).
+using FusedBuildsF32 = Builds<Build<3, 1, 10, 2>, Build<3, 1, 8, 2>, Build<3, 1, 6, 2>, Build<3, 2, 6, 2>, Build<3, 2, 5, 2>,
+                              Build<2, 3, 4, 2>, Build<2, 4, 4, 2>, Build<2, 4, 3, 3>>;
+using FusedBuildsF64 = Builds<Build<2, 1, 10, 2>, Build<2, 2, 5, 2>, Build<2, 2, 4, 2>>;
+static_assert(FusedBuildsF32::covers(4, SweepKernel::Three) && FusedBuildsF32::covers(4, SweepKernel::Fused2) &&
+                  FusedBuildsF64::covers(8, SweepKernel::Fused2) && FusedBuildsF64::covers(8, SweepKernel::Three),
+              "a fused-kernel shape of SHAPE_TABLE has no build here");
 
-template <>
-int fused_shape_count<float>(const GridDesc& g, int levels)
+// plan = the three-sweep id (levels == 3) or the two-sweep id of the fused kernel (levels == 2); < 0: plan 0.  All plans give
+// the same bits, the host driver times them once per grid.
+template <class T>
+void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
+                         const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
+                         int second_first, const PeerPush* push, MaskPlan* mp)
 {
-    if (levels == 3) return (g.W <= 256) ? 3 : 2;
-    return (g.W > 768) ? 2 : 1;
-}
-template <>
-int fused_shape_count<double>(const GridDesc& g, int) { return (g.W <= 256) ? 1 : 2; }
-
-// plan = workgroup shape + 8 * (which of the launcher's three best z-chunk counts); all plans give the same bits,
-// the host driver times them once per grid.
-template <>
-void launch_jacobi_fused<float>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels,
-                                const float* src, const float* rhs, float* dst, const uint8_t* flags, int b, float a,
-                                float inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push,
-                                MaskPlan* mp)
-{
-    if (plan < 0) plan = 0;
-    const int alt = plan >> 3, shape = plan & 7;
-#define FS_F(NL, NX, NY, RY) launch_fused_v<float, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push, mp)
-    if (levels == 3 && tune.abl == 16 && g.W == 512 && sc.lo_wall && sc.hi_wall && z_first == 1 && z_last == g.D && second_first < 0) {
-        // EXPERIMENT, timing only (wrong at the walls): every workgroup runs the lean interior body in 16-row bands
-        constexpr int BY = 16;
-        const int nbands = fused_bands<3>(g.H, BY);
-        const int nzc = alt == 0 ? 5 : alt == 1 ? 6 : 4;
-        const int zc_len = (g.D + nzc - 1) / nzc, nblk = nbands * nzc;
-        hipLaunchKernelGGL((jacobi_fused_kernel<float, 3, 2, 8, 2, true, false, 2>), dim3(nblk), dim3(1024), 0, st, g, sc, src, rhs, dst, flags,
-                           b, a, inv_c, z_first, z_last, zc_len, zc_len, nbands, nblk, PeerPush(), CleanArgs());
-        return;
-    }
-    if (levels == 3) {
-        // Two rows per wave throughout (three rows and 8 waves were slower: the instruction stream of a wave
-        // is what limits this kernel).  Rows up to 256 cells: bands of 20, 16 or 12 rows (the smaller ones trade
-        // recomputed rows for longer z chunks and, at 12 rows, two workgroups per CU); up to 512 cells: 12 or 10 rows.
-        if (g.W <= 256) {
-            if (shape == 1) FS_F(3, 1, 8, 2);
-            else if (shape == 2) FS_F(3, 1, 6, 2);
-            else FS_F(3, 1, 10, 2);
-        } else {
-            if (shape == 1) FS_F(3, 2, 5, 2);
-            else FS_F(3, 2, 6, 2);
+    const PlanId p = decode_plan(levels == 3, plan);
+    const SweepKernel kind = levels == 3 ? SweepKernel::Three : SweepKernel::Fused2;
+    if constexpr (sizeof(T) == 4) {
+        if (levels == 3 && tune.abl == 16 && g.W == 512 && sc.lo_wall && sc.hi_wall && z_first == 1 && z_last == g.D && second_first < 0) {
+            // EXPERIMENT, timing only (wrong at the walls): every workgroup runs the lean interior body in 16-row bands
+            const int nbands = plan_bands(g.H, SweepShape{3, 2, 8, 2});
+            const int nzc = p.alt == 0 ? 5 : p.alt == 1 ? 6 : 4;
+            const int zc_len = (g.D + nzc - 1) / nzc, nblk = nbands * nzc;
+            hipLaunchKernelGGL((jacobi_fused_kernel<float, 3, 2, 8, 2, true, false, 2>), dim3(nblk), dim3(1024), 0, st, g, sc, src, rhs, dst, flags,
+                               b, a, inv_c, z_first, z_last, zc_len, zc_len, nbands, nblk, PeerPush(), CleanArgs());
+            return;
         }
-    } else {
-        // rows of 513..1024 cells: 16 waves x two rows (8-row bands, <= 128 VGPRs) or 12 waves x three rows (9-row bands)
-        if (g.W <= 768) FS_F(2, 3, 4, 2);
-        else if (shape == 1) FS_F(2, 4, 3, 3);
-        else FS_F(2, 4, 4, 2);
     }
-#undef FS_F
+    const SweepShape* shape = launch_shape(sizeof(T), kind, g.W, p.shape);
+    if (!shape) return;                                  // no such kernel for this row width: plan_supported is false
+    using List = std::conditional_t<sizeof(T) == 4, FusedBuildsF32, FusedBuildsF64>;
+    List::run(*shape, [&](auto build) {
+        using B = decltype(build);
+        launch_fused_v<T, B::NL, B::NXW, B::NYW, B::RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, *shape,
+                                                        p.alt, second_first, push, sizeof(T) == 4 ? mp : nullptr);
+    });
 }
-template <>
-void launch_jacobi_fused<double>(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int,
-                                 const double* src, const double* rhs, double* dst, const uint8_t* flags, int b, double a,
-                                 double inv_c, int z_first, int z_last, int plan, int second_first, const PeerPush* push,
-                                 MaskPlan*)
-{
-    if (plan < 0) plan = 0;
-    const int alt = plan >> 3, shape = plan & 7;
-#define FS_F(NL, NX, NY, RY) launch_fused_v<double, NL, NX, NY, RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, alt, second_first, push, nullptr)
-    // fp64: two sweeps per pass; rows up to 256 cells: 20-row bands; up to 512: 10-row bands (10 waves) or 8 (8 waves, 256 VGPRs)
-    if (g.W <= 256) FS_F(2, 1, 10, 2);
-    else if (shape == 1) FS_F(2, 2, 4, 2);
-    else FS_F(2, 2, 5, 2);
-#undef FS_F
-}
+template void launch_jacobi_fused<float>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const float*,
+                                         const float*, float*, const uint8_t*, int, float, float, int, int, int, int,
+                                         const PeerPush*, MaskPlan*);
+template void launch_jacobi_fused<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const double*,
+                                          const double*, double*, const uint8_t*, int, double, double, int, int, int, int,
+                                          const PeerPush*, MaskPlan*);
 
 }  // namespace fs

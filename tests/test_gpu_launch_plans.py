@@ -2,7 +2,7 @@
 
 On each grid the host times the workgroup shapes of the two-sweep kernels (jacobi_pair_kernel, kernels.hip, and
 jacobi_fused_kernel<NL = 2>, sweep_fused.hip) and of the three-sweep kernel (jacobi_fused_kernel<NL = 3>), each with the
-three best z-chunk counts of its launcher's model, and keeps the fastest (fluidsim.cpp, choose_pair_shape).  Every plan
+three best z-chunk counts of its launcher's model, and keeps the fastest (fluidsim.cpp, choose_launch_plans).  Every plan
 must compute the same bits, but the suite's other tests only ever run the plan that won on the test box's clock.  Here
 each plan is replayed with launch_plans = "<two-sweep id>,<three-sweep id>":
 
@@ -10,40 +10,41 @@ each plan is replayed with launch_plans = "<two-sweep id>,<three-sweep id>":
     two-sweep fused kernel    id = 64 + shape + 8 alt
     three-sweep kernel        id = shape + 8 alt            (alt = 0, 1, 2: which of the three best chunk counts)
 
-The id table below is written out here, not read back from the library.  Which instantiation each id reaches, and the
-case that runs it (test ids are test_jacobi_plan[<grid>-<kernel><id>-acc<acc>]; a grid id is W x H x D and precision):
+The id table is written out in launch_plan_model.py, not read back from the library (test_launch_plan_cpu.py holds the
+library's table, csrc/launch_plan.h, to it).  Which instantiation each id reaches, and the case that runs it (test ids are
+test_jacobi_plan[<grid>-<kernel><id>-acc<acc>]; a grid id is W x H x D and precision):
 
-  instantiation (launch site)                 rows          shape ids    grids that run it
+  instantiation (SHAPE_TABLE entry)                 rows          shape ids    grids that run it
   kernels.hip launch_jacobi_pair<float>
-    FS_PAIR(1, 12)                            <= 256        0            200x40x48, 256x40x48, 256x1x5 (fp32)
-    FS_PAIR(1, 8)                             <= 256        1            same
-    FS_PAIR(1, 10)                            <= 256        2            same
-    FS_PAIR(1, 16)  (pair_shape = 3 only)     <= 256        0, 8, 16     test_pair_shape_16_waves[200]   
-    FS_PAIR(2, 6)                             257..512      0            300x40x48, 512x40x48, 300x2x9 (fp32)
-    FS_PAIR(2, 4)                             257..512      1            same
-    FS_PAIR(2, 5)                             257..512      2            same
-    FS_PAIR(2, 8)   (pair_shape = 3 only)     257..512      0, 8, 16     test_pair_shape_16_waves[300]   
-    FS_PAIR(3, 4)                             513..768      0            600x20x48, 768x20x48 (fp32)
-    FS_PAIR(4, 3)                             769..1024     0            800x20x48, 1024x20x48, 1000x3x7 (fp32)
+    Build<2, 1, 12, 2>                           <= 256        0            200x40x48, 256x40x48, 256x1x5 (fp32)
+    Build<2, 1, 8, 2>                            <= 256        1            same
+    Build<2, 1, 10, 2>                           <= 256        2            same
+    Build<2, 1, 16, 2> (pair_shape = 3 only)     <= 256        0, 8, 16     test_pair_shape_16_waves[200]   
+    Build<2, 2, 6, 2>                            257..512      0            300x40x48, 512x40x48, 300x2x9 (fp32)
+    Build<2, 2, 4, 2>                            257..512      1            same
+    Build<2, 2, 5, 2>                            257..512      2            same
+    Build<2, 2, 8, 2>  (pair_shape = 3 only)     257..512      0, 8, 16     test_pair_shape_16_waves[300]   
+    Build<2, 3, 4, 2>                            513..768      0            600x20x48, 768x20x48 (fp32)
+    Build<2, 4, 3, 2>                            769..1024     0            800x20x48, 1024x20x48, 1000x3x7 (fp32)
   kernels.hip launch_jacobi_pair<double>
-    <double, 1, 8>                            <= 256        0            200x40x48, 100x3x6 (fp64)
-    <double, 2, 4>                            257..512      0            300x30x48, 512x30x48 (fp64)
-    <double, 3, 3>                            513..768      0            700x16x48, 600x1x10 (fp64)
-    <double, 4, 2>                            769..1024     0            1024x16x48 (fp64)
+    Build<2, 1, 8, 2>                            <= 256        0            200x40x48, 100x3x6 (fp64)
+    Build<2, 2, 4, 2>                            257..512      0            300x30x48, 512x30x48 (fp64)
+    Build<2, 3, 3, 2>                            513..768      0            700x16x48, 600x1x10 (fp64)
+    Build<2, 4, 2, 2>                            769..1024     0            1024x16x48 (fp64)
   sweep_fused.hip launch_jacobi_fused<float>, three sweeps (the three-sweep id)
-    FS_F(3, 1, 10, 2)  20-row bands           <= 256        0            200x40x48, 256x40x48, 256x1x5 (fp32)
-    FS_F(3, 1, 8, 2)   16-row bands           <= 256        1            same
-    FS_F(3, 1, 6, 2)   12-row bands           <= 256        2            same
-    FS_F(3, 2, 6, 2)   12-row bands           257..512      0            300x40x48, 512x40x48, 300x2x9 (fp32)
-    FS_F(3, 2, 5, 2)   10-row bands           257..512      1            same
+    Build<3, 1, 10, 2>  20-row bands           <= 256        0            200x40x48, 256x40x48, 256x1x5 (fp32)
+    Build<3, 1, 8, 2>   16-row bands           <= 256        1            same
+    Build<3, 1, 6, 2>   12-row bands           <= 256        2            same
+    Build<3, 2, 6, 2>   12-row bands           257..512      0            300x40x48, 512x40x48, 300x2x9 (fp32)
+    Build<3, 2, 5, 2>   10-row bands           257..512      1            same
   sweep_fused.hip launch_jacobi_fused<float>, two sweeps (the two-sweep id, 64 + ...)
-    FS_F(2, 3, 4, 2)   8-row bands            513..768      0            600x20x48, 768x20x48 (fp32)
-    FS_F(2, 4, 4, 2)   8-row bands            769..1024     0            800x20x48, 1024x20x48, 1000x3x7 (fp32)
-    FS_F(2, 4, 3, 3)   9-row bands            769..1024     1            same
+    Build<2, 3, 4, 2>   8-row bands            513..768      0            600x20x48, 768x20x48 (fp32)
+    Build<2, 4, 4, 2>   8-row bands            769..1024     0            800x20x48, 1024x20x48, 1000x3x7 (fp32)
+    Build<2, 4, 3, 3>   9-row bands            769..1024     1            same
   sweep_fused.hip launch_jacobi_fused<double> (two sweeps, 64 + ...)
-    FS_F(2, 1, 10, 2)  20-row bands           <= 256        0            200x40x48, 100x3x6 (fp64)
-    FS_F(2, 2, 5, 2)   10-row bands           257..512      0            300x30x48, 512x30x48 (fp64)
-    FS_F(2, 2, 4, 2)   8-row bands            257..512      1            same
+    Build<2, 1, 10, 2>  20-row bands           <= 256        0            200x40x48, 100x3x6 (fp64)
+    Build<2, 2, 5, 2>   10-row bands           257..512      0            300x30x48, 512x30x48 (fp64)
+    Build<2, 2, 4, 2>   8-row bands            257..512      1            same
 
 (The timing-only ablation build of launch_jacobi_fused<float>, sweep_abl = 16, is wrong at the walls by design and left
 out.)  Each plan runs with acc 7 and 8: passes [3, 3, 1] and [3, 3, 2] of the three-sweep kernel, [2, 2, 2, 1] and
@@ -59,10 +60,10 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
+from launch_plan_model import FUSED2, GRIDS, RB_GRIDS, model_chunk_len, nbands, plan_list, three_shapes
 
 pytestmark = pytest.mark.gpu
 
-FUSED2 = 64
 JACOBI_ACCS = (7, 8)
 
 
@@ -70,79 +71,6 @@ JACOBI_ACCS = (7, 8)
 def F():
     import fluid_simulation_amd as F
     return F
-
-
-# ---- the plan table ------------------------------------------------------------------------------------------------------
-# (shape id, NL, band height BY) per kernel, by precision and row width: kernels.hip launch_jacobi_pair (BY = 2 NY) and
-# sweep_fused.hip launch_jacobi_fused (BY = NY RY)
-def pair_shapes(W, fp64):
-    nxw = (W + 255) // 256
-    if fp64:
-        return [(0, {1: 16, 2: 8, 3: 6, 4: 4}[nxw])]
-    return {1: [(0, 24), (1, 16), (2, 20)], 2: [(0, 12), (1, 8), (2, 10)], 3: [(0, 8)], 4: [(0, 6)]}[nxw]
-
-
-def fused2_shapes(W, fp64):
-    if fp64:
-        return [(0, 20)] if W <= 256 else [(0, 10), (1, 8)] if W <= 512 else []
-    return [] if W <= 512 else [(0, 8)] if W <= 768 else [(0, 8), (1, 9)]
-
-
-def three_shapes(W, fp64):
-    if fp64 or W > 512:
-        return []
-    return [(0, 20), (1, 16), (2, 12)] if W <= 256 else [(0, 12), (1, 10)]
-
-
-def plan_list(W, fp64):
-    """(kind, launch_plans value, expected pair_shape, triple_plan, two_sweep_fused, NL, BY, alt) of every plan of a grid."""
-    out = []
-    for shape, by in pair_shapes(W, fp64):
-        for alt in range(3):
-            pid = shape + 8 * alt
-            out.append(("pair", "%d,-1" % pid, pid, -1, 0, 2, by, alt))
-    for shape, by in fused2_shapes(W, fp64):
-        for alt in range(3):
-            pid = FUSED2 + shape + 8 * alt
-            out.append(("fused", "%d,-1" % pid, pid, -1, 1, 2, by, alt))
-    for shape, by in three_shapes(W, fp64):
-        for alt in range(3):
-            tid = shape + 8 * alt
-            out.append(("three", "0,%d" % tid, 0, tid, 0, 3, by, alt))
-    return out
-
-
-# ---- the launchers' z-chunk models (kernels.hip launch_pair_v, sweep_fused.hip launch_fused_v) --------------------------------
-def chunk_len(planes, nbands, alt, min_len, extra, slots=256):
-    """Planes per z chunk the launcher picks for `alt`: the alt-th best chunk count by filled CU slots x useful planes."""
-    eff, cnt = [-1.0] * 3, [1] * 3
-    nzc = 1
-    while nzc <= 64 and (nzc == 1 or planes // nzc >= min_len):
-        blocks = nbands * nzc
-        rounds = (blocks + slots - 1) // slots
-        ln = (planes + nzc - 1) // nzc
-        e = blocks / (rounds * slots) * ln / (ln + extra)
-        for k in range(3):
-            if e > eff[k] + 1e-9:
-                eff[k + 1:], cnt[k + 1:] = eff[k:2], cnt[k:2]
-                eff[k], cnt[k] = e, nzc
-                break
-        nzc += 1
-    pick = alt
-    while pick > 0 and eff[pick] < 0.0:
-        pick -= 1
-    return (planes + cnt[pick] - 1) // cnt[pick]
-
-
-def nbands(H, BY, NL):
-    step = BY - 2 * (NL - 1)
-    return (H + step - 1) // step
-
-
-def model_chunk_len(kind, H, D, NL, BY, alt):
-    if kind == "pair":
-        return chunk_len(D, nbands(H, BY, 2), alt, 12, 3)
-    return chunk_len(D, nbands(H, BY, NL), alt, 16, 2 * NL - 1)
 
 
 # ---- masks from the plans' geometry ----------------------------------------------------------------------------------------
@@ -233,18 +161,6 @@ def assert_same(F, got, want, what):
 
 
 # ---- part 1: every plan of every kernel -----------------------------------------------------------------------------------
-GRIDS = [
-    # three-sweep fp32: ragged <= 256, exactly 256, ragged 257..511, exactly 512 (and the pair kernel's nxw = 1, 2)
-    (200, 40, 48, False), (256, 40, 48, False), (300, 40, 48, False), (512, 40, 48, False),
-    # two-sweep fused fp32: 513..768, 769..1024 (pair nxw = 3, 4)
-    (600, 20, 48, False), (768, 20, 48, False), (800, 20, 48, False), (1024, 20, 48, False),
-    # fp64: fused <= 256, 257..512 (ragged and aligned); pair nxw = 1..4
-    (200, 40, 48, True), (300, 30, 48, True), (512, 30, 48, True), (700, 16, 48, True), (1024, 16, 48, True),
-    # degenerate: H = 1..3, D shorter than one chunk
-    (256, 1, 5, False), (300, 2, 9, False), (1000, 3, 7, False), (100, 3, 6, True), (600, 1, 10, True),
-]
-
-
 def _grid_id(W, H, D, fp64):
     return "%dx%dx%d-%s" % (W, H, D, "fp64" if fp64 else "fp32")
 
@@ -257,29 +173,6 @@ def _jacobi_cases():
                 cases.append(pytest.param(W, H, D, fp64, p, acc, id="%s-%s%s-acc%d" % (
                     _grid_id(W, H, D, fp64), p[0], p[1].split(",")[0 if p[0] != "three" else 1], acc)))
     return cases
-
-
-def test_plan_table_and_chunk_models():
-    """The grids reach every instantiation of the table above, and on every grid 48 planes deep each kernel's three alts give
-    at least two (here: three) different chunk counts, so that alt 1 and 2 are not alt 0 again."""
-    reached = set()
-    for W, H, D, fp64 in GRIDS:
-        for kind, _, _, _, _, NL, BY, alt in plan_list(W, fp64):
-            reached.add((kind, fp64, (W + 255) // 256 if kind == "pair" else W <= 256 if kind != "fused" or fp64 else W <= 768, BY))
-        if D >= 48:
-            for kind, _, _, _, _, NL, BY, _ in plan_list(W, fp64):
-                counts = {(D + model_chunk_len(kind, H, D, NL, BY, a) - 1) // model_chunk_len(kind, H, D, NL, BY, a) for a in range(3)}
-                assert len(counts) >= 2, (W, H, D, kind, BY, counts)
-    pair32 = {(n, by) for k, f, n, by in reached if k == "pair" and not f}
-    assert pair32 == {(1, 24), (1, 16), (1, 20), (2, 12), (2, 8), (2, 10), (3, 8), (4, 6)}
-    assert {(n, by) for k, f, n, by in reached if k == "pair" and f} == {(1, 16), (2, 8), (3, 6), (4, 4)}
-    assert {(s, by) for k, f, s, by in reached if k == "three"} == {(True, 20), (True, 16), (True, 12), (False, 12), (False, 10)}
-    assert {(s, by) for k, f, s, by in reached if k == "fused" and not f} == {(True, 8), (False, 8), (False, 9)}
-    assert {(s, by) for k, f, s, by in reached if k == "fused" and f} == {(True, 20), (False, 10), (False, 8)}
-    # a few values of the models, worked by hand: 48 planes, one band, 256 slots -> as many chunks as allowed, then fewer
-    assert [chunk_len(48, 1, a, 16, 5) for a in range(3)] == [16, 24, 48]
-    assert [chunk_len(48, 1, a, 12, 3) for a in range(3)] == [12, 16, 24]
-    assert [chunk_len(10, 3, a, 16, 5) for a in range(3)] == [10, 10, 10]
 
 
 @pytest.mark.parametrize("W,H,D,fp64,plan,acc", _jacobi_cases())
@@ -359,10 +252,6 @@ def test_three_sweep_plans_switched_on_one_handle(F, W, mask_free):
 
 
 # ---- part 3: rbsor and multigrid under every pair plan ---------------------------------------------------------------------------
-RB_GRIDS = [(100, 30, 48, False), (300, 20, 48, False), (700, 12, 36, False), (1000, 9, 36, False), (100, 30, 48, True),
-            (300, 20, 36, True)]
-
-
 @pytest.mark.parametrize("W,H,D,fp64", RB_GRIDS, ids=[_grid_id(*g) for g in RB_GRIDS])
 def test_rbsor_under_every_pair_plan(F, oracle_mod, W, H, D, fp64):
     acc, omega = 5, 1.6
@@ -376,7 +265,7 @@ def test_rbsor_under_every_pair_plan(F, oracle_mod, W, H, D, fp64):
 
 
 def test_multigrid_under_every_pair_plan(F, oracle_mod):
-    """solver=mg: the damped level-0 passes run the pair plan (pair_plan_rb); 128x64x64 has four levels."""
+    """solver=mg: the damped level-0 passes run the pair plan (plan_two_pair); 128x64x64 has four levels."""
     W, H, D, acc, mg = 128, 64, 64, 5, (2, 1, 1, 30)
     plans = [p for p in plan_list(W, False) if p[0] == "pair"]
     m = _geometry_mask(W, H, D, plans)
@@ -427,7 +316,7 @@ def test_project_kernels_march_and_cell(F, oracle_mod, W, H, D, fp64):
 
 @pytest.mark.parametrize("W", [200, 300])
 def test_pair_shape_16_waves(F, oracle_mod, W):
-    """pair_shape = 3, the 16-wave pair build (FS_PAIR(1, 16) / (2, 8)), with each of its chunk counts."""
+    """pair_shape = 3, the 16-wave pair build (Build<2, 1, 16, 2> / <2, 2, 8, 2>), with each of its chunk counts."""
     H, D, acc = 40, 48, 8
     plans = plan_list(W, False)
     m = _masks(W, H, D, plans)["geometry"]
