@@ -4,11 +4,14 @@
 when the first `Simulation` is created and there is no CPU fallback.
 """
 from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_PREV, VY, VY_PREV, VZ, VZ_PREV,
-                   FluidsimError)
+                   STAT_MEAN_DENS, STAT_MEAN_P, STAT_MEAN_VX, STAT_MEAN_VY, STAT_MEAN_VZ, STAT_NAMES, STAT_PP, STAT_RAW, STAT_TKE,
+                   STAT_UU, STAT_UV, STAT_UW, STAT_VV, STAT_VW, STAT_WW, FluidsimError)
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
                          solve_reduction)
 
 __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_force", "FORCE_LOG_DTYPE", "FluidsimError",
            "RESIDUAL_LOG_DTYPE", "solve_reduction",
-           "FIELD_NAMES",
+           "FIELD_NAMES", "STAT_NAMES",
+           "STAT_MEAN_DENS", "STAT_MEAN_VX", "STAT_MEAN_VY", "STAT_MEAN_VZ", "STAT_MEAN_P", "STAT_UU", "STAT_VV", "STAT_WW",
+           "STAT_UV", "STAT_UW", "STAT_VW", "STAT_PP", "STAT_TKE", "STAT_RAW",
            "DENS", "VX", "VY", "VZ", "OBS", "PRESSURE", "DIVERGENCE", "VX_PREV", "VY_PREV", "VZ_PREV", "BUFFER"]

@@ -20,6 +20,12 @@ FORCE_LOG_COLS = 9      # FS_FORCE_LOG_COLS: step, S1x, S1y, S1z, S2x, S2y, S2z,
 RESIDUAL_COLS = 4       # FS_RESIDUAL_COLS: sum r^2, sum x0^2, max |r|, free cells
 RESIDUAL_LOG_SOLVES = 6     # FS_RESIDUAL_LOG_SOLVES: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density
 RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, r_sq, r_max, rhs_sq, cells
+# FS_STAT_*: selectors of fs_flow_stats_field -- the five means, the seven (co)variances, the turbulence kinetic energy;
+# STAT_RAW or-ed in returns the raw sum instead
+(STAT_MEAN_DENS, STAT_MEAN_VX, STAT_MEAN_VY, STAT_MEAN_VZ, STAT_MEAN_P,
+ STAT_UU, STAT_VV, STAT_WW, STAT_UV, STAT_UW, STAT_VW, STAT_PP, STAT_TKE) = range(13)
+STAT_RAW = 256
+STAT_NAMES = ["mean_dens", "mean_vx", "mean_vy", "mean_vz", "mean_p", "uu", "vv", "ww", "uv", "uw", "vw", "pp", "tke"]
 
 
 class FluidsimError(RuntimeError):
@@ -72,6 +78,10 @@ _SIGNATURES = {
     "fs_solve_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "fs_diffuse_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fs_residual_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_flow_stats_sample": (C.c_int, [C.c_void_p]),
+    "fs_flow_stats_reset": (C.c_int, [C.c_void_p]),
+    "fs_flow_stats_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
+    "fs_flow_stats_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

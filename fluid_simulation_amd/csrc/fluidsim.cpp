@@ -17,6 +17,7 @@
 #include "multigrid.h"
 #include "forces.h"
 #include "residual.h"
+#include "flow_stats.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -52,8 +53,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -96,6 +97,10 @@ struct EngineBase {
     virtual int solve_residual(int b, int field, int prev, double a, double c, double* out4, double* per_plane) = 0;
     virtual int diffuse_residual(int b, int field, int prev, double* out4, double* per_plane) = 0;
     virtual int residual_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
+    virtual int flow_stats_config() = 0;       // apply fs_set_option("flow_stats"): allocate or free, clear
+    virtual int flow_stats_sample() = 0;
+    virtual int flow_stats_field(int which, void* dst, size_t n, int elem) = 0;
+    virtual int flow_stats_dump(const char* dir) = 0;
 };
 
 struct fs_sim {
@@ -157,6 +162,10 @@ struct fs_sim {
     long force_log_gen = 0;      // bumped by every fs_set_option("force_log"): the ring is reallocated and cleared
     int residual_log = 0;        // "residual_log": steps the per-step residual log keeps, 0 = off
     long residual_log_gen = 0;   // bumped by every fs_set_option("residual_log")
+    int flow_stats = 0;          // "flow_stats": accumulators per cell, 0 = off, 5 = "mean", 12 = "moments" (flow_stats.h)
+    long flow_stats_gen = 0;     // bumped by every fs_set_option("flow_stats"): the accumulators are (re)allocated and cleared
+    long flow_stats_every = 1, flow_stats_start = 0;   // fs_step samples when steps_total > start and (steps_total - start - 1) % every == 0
+    long flow_stats_n = 0;       // samples taken since the last reset
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -287,6 +296,10 @@ struct Engine : EngineBase {
     std::vector<long> res_step;         // step number held by each ring slot
     std::vector<unsigned> res_ran;      // bit k: solve k of that step ran (an elided solve leaves no record)
     unsigned res_ran_now = 0;           // the same for the step that is running
+    // time-averaged flow statistics (flow_stats.h): private allocations, one per accumulator, never exported to slab neighbours
+    fs::FlowStatsAcc stat_acc = {};
+    int stat_nacc = 0;                  // accumulators allocated: 0, 5 or 12
+    long stat_gen = -1;                 // S->flow_stats_gen they were set up for
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -409,6 +422,7 @@ struct Engine : EngineBase {
         if (res_ring) hipFree(res_ring);
         if (res_scratch) hipFree(res_scratch);
         if (res_partial) hipFree(res_partial);
+        for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1321,6 +1335,7 @@ struct Engine : EngineBase {
         if (rc) return rc;
         if ((rc = ensure_force_ring())) return rc;
         if ((rc = ensure_residual_ring())) return rc;
+        if ((rc = flow_stats_config())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1395,6 +1410,10 @@ struct Engine : EngineBase {
             res_ran[(size_t)(res_logged % res_cap)] = res_ran_now;
             res_step[(size_t)(res_logged++ % res_cap)] = S->steps_total;
         }
+        // "flow_stats": the state as :136 left it is a sample (no host synchronisation, the step's own stream)
+        if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
+            (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
+            return rc;
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -1786,6 +1805,128 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- time-averaged flow statistics (flow_stats.h; beyond the reference) ---------------------------
+    size_t stat_bytes() const { return (size_t)fs::flow_stats_groups(g.sz, g.D) * 4 * sizeof(double); }
+
+    // allocate, free and clear after fs_set_option("flow_stats"); a reset needs no pass over memory (the first sample overwrites)
+    int flow_stats_config() override
+    {
+        if (stat_gen == S->flow_stats_gen) return FS_OK;
+        stat_gen = S->flow_stats_gen;
+        S->flow_stats_n = 0;
+        if (stat_nacc == S->flow_stats) return FS_OK;
+        HIP_TRY(hipStreamSynchronize(S->stream));        // a queued sample may still write what is freed here
+        for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
+        stat_acc = fs::FlowStatsAcc{};
+        stat_nacc = 0;
+        for (int k = 0; k < S->flow_stats; ++k) {
+            const hipError_t e = hipMalloc((void**)&stat_acc.a[k], stat_bytes());
+            if (e != hipSuccess) {
+                for (int j = 0; j < k; ++j) hipFree(stat_acc.a[j]);
+                stat_acc = fs::FlowStatsAcc{};
+                const int want = S->flow_stats;
+                S->flow_stats = 0;
+                return fail(FS_ENOMEM, "flow_stats: %d accumulator arrays of %zu bytes: %s (the feature is off now)", want, stat_bytes(),
+                            hipGetErrorString(e));
+            }
+        }
+        stat_nacc = S->flow_stats;
+        return FS_OK;
+    }
+
+    int flow_stats_sample() override
+    {
+        int rc = flow_stats_config();
+        if (rc) return rc;
+        if (stat_nacc == 0) return fail(FS_EINVAL, "fs_flow_stats_sample: option \"flow_stats\" is off");
+        ScopedSpan sp(S, FAM_FLOWSTATS);
+        fs::launch_flow_stats<T>(S->stream, g, stat_nacc, S->flow_stats_n == 0, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]],
+                                 arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], stat_acc);
+        S->flow_stats_n++;
+        return FS_OK;
+    }
+
+    // which: selector without FS_STAT_RAW
+    int flow_stats_check(const char* who, int sel)
+    {
+        const int which = sel & ~FS_STAT_RAW;
+        const bool raw = (sel & FS_STAT_RAW) != 0;
+        if (which < 0 || which > FS_STAT_TKE) return fail(FS_EINVAL, "%s: unknown selector %d", who, sel);
+        if (stat_nacc == 0) return fail(FS_EINVAL, "%s: option \"flow_stats\" is off", who);
+        if (raw && which == FS_STAT_TKE) return fail(FS_EINVAL, "%s: FS_STAT_TKE has no raw sum", who);
+        if (which >= fs::ST_NMEAN && stat_nacc < fs::ST_NMOMENTS)
+            return fail(FS_EINVAL, "%s: selector %d needs \"flow_stats\" = \"moments\" (the mode is \"mean\")", who, which);
+        if (!raw && S->flow_stats_n == 0) return fail(FS_EINVAL, "%s: no samples taken yet (n = 0)", who);
+        return FS_OK;
+    }
+
+    // The derived field goes into the staging buffer in the accumulators' layout, and from there through launch_pack into
+    // the dense layout behind it.
+    int flow_stats_field(int sel, void* dst, size_t n, int elem) override
+    {
+        int rc = flow_stats_config();
+        if (rc) return rc;
+        if ((rc = flow_stats_check("fs_flow_stats_field", sel))) return rc;
+        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_flow_stats_field: expected %ld elements, got %zu", dense_cells(), n);
+        if (elem != 4 && elem != 8) return fail(FS_EINVAL, "elem_size must be 4 or 8");
+        if ((rc = need_dense(stat_bytes() + n * (size_t)elem))) return rc;
+        double* pitched = (double*)dense;
+        void* packed = (char*)dense + stat_bytes();
+        if (S->flow_stats_n == 0) {                      // a raw sum before the first sample: +0.0 (the arrays hold nothing yet)
+            HIP_TRY(hipMemsetAsync(packed, 0, n * (size_t)elem, S->stream));
+        } else {
+            fs::launch_flow_stats_finalize(S->stream, g, stat_acc, sel & ~FS_STAT_RAW, (sel & FS_STAT_RAW) != 0, S->flow_stats_n,
+                                           !sc.lo_wall, !sc.hi_wall, pitched);
+            if (elem == 4) fs::launch_pack<double, float>(S->stream, g, pitched + fs::LEAD, (float*)packed, 0, g.D + 1);
+            else fs::launch_pack<double, double>(S->stream, g, pitched + fs::LEAD, (double*)packed, 0, g.D + 1);
+        }
+        HIP_TRY(hipMemcpyAsync(dst, packed, n * elem, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int flow_stats_dump(const char* dir) override
+    {
+        int rc = flow_stats_config();
+        if (rc) return rc;
+        static const char* const names[7] = { "data.bin", "obs.bin", "v_x.bin", "v_y.bin", "v_z.bin", "p.bin", "tke.bin" };
+        static const int sel[7] = { FS_STAT_MEAN_DENS, -1, FS_STAT_MEAN_VX, FS_STAT_MEAN_VY, FS_STAT_MEAN_VZ, FS_STAT_MEAN_P, FS_STAT_TKE };
+        const int nfiles = stat_nacc >= fs::ST_NMOMENTS ? 7 : 6;
+        if ((rc = flow_stats_check("fs_flow_stats_dump", FS_STAT_MEAN_DENS))) return rc;
+        // rank 0 truncates; the other slab ranks open the files for update once they exist (as dump_frame does)
+        const bool lead = !S->comm.active() || S->comm.rank == 0;
+        FILE* fp[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool ok = true;
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((pass == 0) == lead)
+                for (int k = 0; k < nfiles; ++k) {
+                    fp[k] = fopen((std::string(dir) + "/" + names[k]).c_str(), lead ? "wb" : "r+b");
+                    if (!fp[k]) ok = false;
+                }
+            if (pass == 0 && S->comm.active()) {
+                if (S->comm.shm && S->comm.shm_ready(g, S->D)) return fail(FS_ECOMM, "%s", S->comm.last_error());
+                if ((rc = slab_barrier())) return rc;
+            }
+        }
+        // local planes written by this rank: its interior planes, plus the physical ghost planes
+        const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
+        const size_t plane = (size_t)(g.W + 2) * (g.H + 2);
+        std::vector<float> h((size_t)dense_cells());
+        for (int k = 0; k < nfiles && ok && !rc; ++k) {
+            rc = sel[k] < 0 ? get_field(FS_OBS, h.data(), h.size(), 4) : flow_stats_field(sel[k], h.data(), h.size(), 4);
+            if (rc) break;
+            if (fseek(fp[k], (long)(plane * (size_t)(sc.zoff + zlo) * sizeof(float)), SEEK_SET) != 0 ||
+                fwrite(h.data() + plane * (size_t)zlo, sizeof(float), plane * (size_t)(zhi - zlo + 1), fp[k]) != plane * (size_t)(zhi - zlo + 1))
+                ok = false;
+        }
+        for (int k = 0; k < nfiles; ++k)
+            if (fp[k] && fclose(fp[k]) != 0) ok = false;
+        if (S->comm.active() && !rc) rc = slab_barrier();     // every rank's planes are in the files
+        if (rc) return rc;
+        if (!ok) return fail(FS_EIO, "fs_flow_stats_dump: cannot write the mean-flow frames under '%s'", dir);
+        return FS_OK;
+    }
+
     // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
     // ring slot k, projection j: g.D plane records
     double* force_slot(long k, int j) const { return force_ring + ((size_t)k * 2 + (size_t)j) * plane_doubles(); }
@@ -2164,6 +2305,24 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "residual_log: steps kept, 0 (off) .. 1048576");
         s->residual_log = (int)n;
         s->residual_log_gen++;
+    } else if (k == "flow_stats") {
+        if (v == "off") s->flow_stats = 0;
+        else if (v == "mean") s->flow_stats = fs::ST_NMEAN;
+        else if (v == "moments") s->flow_stats = fs::ST_NMOMENTS;
+        else return fail(FS_EINVAL, "flow_stats: off | mean | moments");
+        s->flow_stats_gen++;
+        s->flow_stats_n = 0;
+        if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
+            hipSetDevice(s->device);
+            return s->eng->flow_stats_config();
+        }
+    } else if (k == "flow_stats_every" || k == "flow_stats_start") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        const bool every = (k == "flow_stats_every");
+        if (end == value || *end || n < (every ? 1 : 0) || n > (1L << 30))
+            return fail(FS_EINVAL, every ? "flow_stats_every: N >= 1" : "flow_stats_start: S >= 0");
+        (every ? s->flow_stats_every : s->flow_stats_start) = n;
     } else if (k == "dump_async") {
         s->dump_async = (v != "0");
     } else if (k == "fuse_advect") {
@@ -2266,6 +2425,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "reach_wait_us") *out = (int)(s->reach_wait_ms * 1e3);  // host time spent blocked in them
     else if (n == "reach_hidden") *out = (int)s->n_reach_hidden;          // advections queued while the device still had the work placed before them ...
     else if (n == "reach_exposed") *out = (int)s->n_reach_exposed;        // ... and after it had run dry (a bubble on the device)
+    else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
 }
@@ -2578,6 +2738,26 @@ int fs_residual_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* 
 {
     ENGINE_OR_RETURN(s);
     return s->eng->residual_log_fetch(rows, max_rows, n_rows, n_dropped);
+}
+
+int fs_flow_stats_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->flow_stats_sample(); }
+int fs_flow_stats_reset(fs_sim* s)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    s->flow_stats_n = 0;
+    return FS_OK;
+}
+int fs_flow_stats_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dst) return fail(FS_EINVAL, "null buffer");
+    return s->eng->flow_stats_field(which, dst, n_elems, elem_size);
+}
+int fs_flow_stats_dump(fs_sim* s, const char* dir)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dir) return fail(FS_EINVAL, "null directory");
+    return s->eng->flow_stats_dump(dir);
 }
 
 int fs_comm_unique_id(void* id_out)

@@ -183,4 +183,18 @@ void launch_stats(hipStream_t st, const GridDesc& g, const T* field, double* out
 template <class T>
 void launch_point_add(hipStream_t st, T* p, long idx, T amount, int set_instead);
 
+// Time-averaged flow statistics (flow_stats.h has the arithmetic and the array layout; flow_stats.hip the kernels).
+struct FlowStatsAcc {
+    double* a[12];                   // allocation bases (cell index -LEAD) of the mode's accumulators, in flow_stats.h's order
+};
+// One sample: every accumulator of the mode (nacc = 5 or 12) takes the five fields' values, cell by cell.  q, u, v, w, p are
+// LEAD-shifted field pointers (local plane 0 at index 0); first = the first sample after a reset (nothing is read).
+template <class T>
+void launch_flow_stats(hipStream_t st, const GridDesc& g, int nacc, bool first, const T* q, const T* u, const T* v, const T* w,
+                       const T* p, const FlowStatsAcc& acc);
+// One derived field (`which` = flow_stats.h's ST_Q .. ST_TKE; raw: the sum itself) of `n` samples into `out`, an fp64 array
+// of the accumulators' layout (allocation base).  zero_lo / zero_hi: local plane 0 / D + 1 is an inter-slab halo, written 0.
+void launch_flow_stats_finalize(hipStream_t st, const GridDesc& g, const FlowStatsAcc& acc, int which, bool raw, long n,
+                                bool zero_lo, bool zero_hi, double* out);
+
 }  // namespace fs

@@ -311,6 +311,33 @@ class Simulation:
             rows["reduction_%d" % k] = red[:, k]
         return (rows, dropped.value) if with_dropped else rows
 
+    def flow_stats(self, which, raw=False, dtype=None):
+        """One field of the time-averaged flow statistics (options flow_stats="mean" | "moments", flow_stats_every,
+        flow_stats_start; fs_flow_stats_field): `which` is STAT_MEAN_DENS .. STAT_MEAN_P, STAT_UU .. STAT_PP (covariances)
+        or STAT_TKE; raw=True returns the raw fp64 sum instead.  Shaped like get(); float64 unless dtype says float32.  On
+        z-slab handles the local slab, inter-slab halo planes 0."""
+        dtype = np.dtype(dtype or np.float64)
+        n = self._L.fs_padded_size(self._h)
+        out = np.empty(n, dtype=dtype)
+        check(self._L.fs_flow_stats_field(self._h, int(which) | (_lib.STAT_RAW if raw else 0), out.ctypes.data_as(C.c_void_p),
+                                          n, dtype.itemsize))
+        return out.reshape(self.shape)
+
+    def flow_stats_sample(self):
+        """Takes one sample of the state as it is now (fs_step does so by itself under the flow_stats options)."""
+        check(self._L.fs_flow_stats_sample(self._h))
+
+    def flow_stats_reset(self):
+        """Forgets the samples taken so far; the next one starts the sums anew."""
+        check(self._L.fs_flow_stats_reset(self._h))
+
+    flow_stats_samples = property(lambda s: s._geti("flow_stats_samples"))
+
+    def flow_stats_dump(self, dir):
+        """Writes the mean flow as one float32 frame per file under `dir`, in the frame-dump layout the reference's
+        viewers read: data, obs, v_x, v_y, v_z, p and (mode "moments") tke .bin (fs_flow_stats_dump; collective on z-slabs)."""
+        check(self._L.fs_flow_stats_dump(self._h, os.fsencode(dir)))
+
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()
         check(self._L.fs_time_sweeps(self._h, b, field, prev, a, c, reps, C.byref(ms)))

@@ -109,6 +109,8 @@ int fs_destroy(fs_sim* s);
  *   "residual_log" N >= 0 (at most 1048576): keep the residuals of the six linear solves of the last N steps, before and
  *                 after each solve (fs_residual_log); 0 (default) = off, and the step launches and allocates nothing for
  *                 it.  Setting it (re)allocates and clears the log.  May be changed at any time.
+ *   "flow_stats"  "off" (default) | "mean" | "moments", "flow_stats_every" N >= 1, "flow_stats_start" S >= 0: time-averaged
+ *                 flow statistics on the device, see fs_flow_stats_field below.  May be changed at any time.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -144,7 +146,7 @@ int fs_destroy(fs_sim* s);
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
  * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
- * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed".
+ * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples".
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -213,7 +215,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "multigrid" (the coarse-level work of solver "mg"; its level-0 smoothing passes count as
  * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records) "residual" (fs_solve_residual / fs_diffuse_residual and the
  * "residual_log" records: one launch counted per record, i.e. per solve and point in time -- 12 per step with the log on,
- * 10 where the dead density solve is elided, 0 with it off).  Events are recorded on the handle's own stream. */
+ * 10 where the dead density solve is elided, 0 with it off) "flow_stats" (one launch per sample of the time-averaged flow
+ * statistics, 0 with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -333,6 +336,54 @@ int fs_diffuse_residual(fs_sim* s, int b, int field, int prev, double out[4], do
 #define FS_RESIDUAL_LOG_SOLVES 6
 #define FS_RESIDUAL_LOG_COLS 31
 int fs_residual_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+
+/* ---- time-averaged flow statistics (beyond the reference: it has no averaging, no file:line counterpart) ----
+ *
+ * A SAMPLE is the state at the end of a step, after advect(0, dens, buffer) (simulation.cpp:136) and before the frame
+ * dump: u = v_x, v = v_y, w = v_z, q = dens, and p = FS_PRESSURE as the step's second projection left it.  Every cell of
+ * the padded array takes part, ghost faces included, with whatever value the array holds.
+ * Each cell has fp64 accumulators that start at +0.0; each sample adds to them, in sample order, one rounding per addition:
+ *     mode "mean":     S_q, S_u, S_v, S_w, S_p                                  (5 arrays)
+ *     mode "moments":  those, and S_uu, S_vv, S_ww, S_uv, S_uw, S_vw, S_pp      (12 arrays)
+ * A product is (double)a * (double)b, taken before the add: exact on fp32 handles (24 + 24 bits; contraction cannot change a
+ * bit there), rounded once on fp64 handles with the add rounded separately (the library is built with -ffp-contract=off).
+ * n is the number of samples taken since the last reset.  The derived fields, in fp64, every operation rounded, no contraction:
+ *     mean_a = S_a / n        cov_ab = S_ab / n - mean_a * mean_b        tke = ((cov_uu + cov_vv) + cov_ww) * 0.5
+ * LIMIT: these are raw power sums, not Welford updates, so that every bit is defined by the sampled values and their order;
+ * the covariance is a difference of two large numbers.  In fp64 with fp32 inputs at speed 30 it resolves variances down to
+ * roughly 1e-10 of the squared mean over 1e4 samples; smaller fluctuations drown in the rounding of the sums.
+ * A cell's accumulators depend on that cell's sampled values and the order of the samples only: launch shape, tuning and slab
+ * split cannot change a bit, and a z-slab run gives the single-GPU bits on the planes a rank owns.
+ *
+ * Options (fs_set_option, any time): "flow_stats" = "off" (default: the step launches and allocates nothing for it) | "mean"
+ * | "moments" -- setting it allocates or frees the accumulators (fp64 arrays of the padded local slab: 1.10 GB each at 512^3,
+ * 13.2 GB for "moments") and clears them; "flow_stats_every" = N >= 1 (default 1) and "flow_stats_start" = S >= 0 (default 0):
+ * fs_step samples when the handle has completed steps_total steps with this one, steps_total > S and
+ * (steps_total - S - 1) % N == 0, on the step's own stream, without a host synchronisation.
+ * fs_flow_stats_sample takes one sample of the state as it is now (for callers that drive the passes themselves);
+ * fs_flow_stats_reset sets n = 0 (no pass over memory: the next sample overwrites); fs_get_int "flow_stats_samples" reports n.
+ *
+ * fs_flow_stats_field: one derived field, with the semantics of fs_get_field (dense padded layout, the local slab on slab
+ * handles, elem_size 4 or 8, converted on the device).  `which` | FS_STAT_RAW returns the sum S itself (exact values, and what
+ * merges two averaging windows); not with FS_STAT_TKE.  FS_EINVAL when the feature is off, for a second-moment selector in
+ * mode "mean", and for a derived field while n == 0.  On z-slab handles each rank accumulates its own slab and nothing is
+ * exchanged: a rank's interior planes and its physical ghost planes are defined, an inter-slab halo plane (local plane 0 on
+ * ranks > 0, local plane D + 1 on ranks < last) is written as 0.
+ * fs_flow_stats_dump: writes ONE frame per file, truncating, to <dir>/{data,obs,v_x,v_y,v_z}.bin in the frame-dump layout
+ * (simulation.cpp:140-148) with the means in place of the fields and obs as it is, and p.bin, and tke.bin in mode "moments";
+ * float32 whatever the handle's precision, so the reference's viewers show the mean flow unchanged.  Synchronous.  On slab
+ * handles collective: every rank writes its planes at its offset, as fs_dump_frame does.
+ */
+enum {
+    FS_STAT_MEAN_DENS = 0, FS_STAT_MEAN_VX = 1, FS_STAT_MEAN_VY = 2, FS_STAT_MEAN_VZ = 3, FS_STAT_MEAN_P = 4,
+    FS_STAT_UU = 5, FS_STAT_VV = 6, FS_STAT_WW = 7, FS_STAT_UV = 8, FS_STAT_UW = 9, FS_STAT_VW = 10, FS_STAT_PP = 11,
+    FS_STAT_TKE = 12,
+    FS_STAT_RAW = 256    /* or-ed into a selector: the raw sum */
+};
+int fs_flow_stats_sample(fs_sim* s);
+int fs_flow_stats_reset(fs_sim* s);
+int fs_flow_stats_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size);
+int fs_flow_stats_dump(fs_sim* s, const char* dir);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

@@ -25,6 +25,10 @@
 //   --residuals FILE  log the residual of the step's six linear solves before and after each (option "residual_log") and
 //                  write it to FILE as CSV: fs_residual_log's columns, then reduction_k = sqrt(r_sq_k / r0_sq_k);
 //                  may be combined with --forces
+//   --mean-flow DIR  time-average the flow on the device (option "flow_stats") and, at the end of the run, write the mean
+//                  fields to DIR as one frame per file in the frame-dump layout (fs_flow_stats_dump: the viewers show it
+//                  unchanged); --mean-from S skips the first S steps, --mean-every N samples every Nth step after them,
+//                  --mean-moments (no value) also keeps the second moments and writes DIR/tke.bin
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <chrono>
 #include <cmath>
@@ -163,7 +167,8 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir, forces_path, residuals_path;
+    std::string resume_dir, forces_path, residuals_path, mean_dir;
+    bool mean_moments = false;
     std::vector<std::pair<std::string, std::string>> options;
 
     auto apply = [&](const std::string& key, const char* val) -> bool {
@@ -184,10 +189,14 @@ int main(int argc, char** argv)
         if (key == "resume") { resume_dir = val; return true; }
         if (key == "forces") { forces_path = val; return true; }
         if (key == "residuals") { residuals_path = val; return true; }
+        if (key == "mean-flow") { mean_dir = val; return true; }
+        if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
+        if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
-                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals" };
+                                        "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
+                                        "mean-every" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -195,10 +204,12 @@ int main(int argc, char** argv)
             if (!apply(k, v)) { fprintf(stderr, "simulation.out: bad value for %s\n", env.c_str()); return 2; }
     }
     if (getenv("FS_QUIET")) options.push_back({ "quiet", "1" });
+    if (getenv("FS_MEAN_MOMENTS")) mean_moments = true;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--quiet") { options.push_back({ "quiet", "1" }); continue; }
         if (a == "--json") { json = true; continue; }
+        if (a == "--mean-moments") { mean_moments = true; continue; }
         if (a.rfind("--", 0) != 0 || i + 1 >= argc || !apply(a.substr(2), argv[i + 1])) {
             fprintf(stderr, "simulation.out: unknown or malformed argument '%s' (see src/main.cpp)\n", argv[i]);
             return 2;
@@ -215,6 +226,7 @@ int main(int argc, char** argv)
     if (!sim) return die("fs_create");
     if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
     if (!residuals_path.empty()) options.push_back({ "residual_log", std::to_string(iter) });
+    if (!mean_dir.empty()) options.push_back({ "flow_stats", mean_moments ? "moments" : "mean" });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
     for (const Stl& s : stls) {
@@ -233,9 +245,15 @@ int main(int argc, char** argv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
+    int mean_samples = 0;
+    if (!mean_dir.empty()) {
+        if (fs_get_int(sim, "flow_stats_samples", &mean_samples)) return die("flow_stats_samples");
+        if (fs_flow_stats_dump(sim, mean_dir.c_str())) return die("fs_flow_stats_dump");
+    }
     if (json)
-        printf("{\"grid\": [%d, %d, %d], \"steps\": %d, \"acc\": %d, \"seconds\": %.6f, \"cells_steps_per_sec\": %.6g}\n",
-               width, height, depth, iter, acc, secs, (double)width * height * depth * iter / secs);
+        printf("{\"grid\": [%d, %d, %d], \"steps\": %d, \"acc\": %d, \"seconds\": %.6f, \"cells_steps_per_sec\": %.6g, "
+               "\"mean_flow_samples\": %d}\n",
+               width, height, depth, iter, acc, secs, (double)width * height * depth * iter / secs, mean_samples);
     fs_destroy(sim);
     return 0;
 }

@@ -200,6 +200,34 @@ int main(int argc, char** argv)
             if (!(rows[5] > 0.0)) return 16;
             CHECK(fs_set_option(s, "residual_log", "0"));
         }
+        {   // time-averaged flow statistics: samples inside steps and on demand, every selector, the error cases, off again
+            const size_t np = fs_padded_size(s);
+            std::vector<double> d(np);
+            std::vector<float> f4(np);
+            if (fs_flow_stats_field(s, FS_STAT_MEAN_VX, d.data(), np, 8) != FS_EINVAL) return 17;
+            CHECK(fs_set_option(s, "flow_stats", "mean"));
+            if (fs_flow_stats_field(s, FS_STAT_MEAN_VX, d.data(), np, 8) != FS_EINVAL) return 18;
+            CHECK(fs_flow_stats_field(s, FS_STAT_MEAN_VX | FS_STAT_RAW, d.data(), np, 8));
+            CHECK(fs_run_one(s));
+            if (fs_flow_stats_field(s, FS_STAT_UU, d.data(), np, 8) != FS_EINVAL) return 19;
+            CHECK(fs_set_option(s, "flow_stats", "moments"));
+            CHECK(fs_set_option(s, "flow_stats_every", "2"));
+            for (int k = 0; k < 3; ++k) CHECK(fs_run_one(s));
+            CHECK(fs_flow_stats_sample(s));
+            int ns = 0;
+            CHECK(fs_get_int(s, "flow_stats_samples", &ns));
+            if (ns < 2 || ns > 3) return 20;      // one or two of the three steps (every second one), and the one on demand
+            for (int which = 0; which <= FS_STAT_TKE; ++which) {
+                CHECK(fs_flow_stats_field(s, which, d.data(), np, 8));
+                CHECK(fs_flow_stats_field(s, which, f4.data(), np, 4));
+                if (which != FS_STAT_TKE) CHECK(fs_flow_stats_field(s, which | FS_STAT_RAW, d.data(), np, 8));
+            }
+            if (fs_flow_stats_field(s, FS_STAT_TKE | FS_STAT_RAW, d.data(), np, 8) != FS_EINVAL) return 21;
+            if (fs_flow_stats_field(s, FS_STAT_TKE, d.data(), np - 1, 8) != FS_EINVAL) return 22;
+            CHECK(fs_flow_stats_reset(s));
+            CHECK(fs_set_option(s, "flow_stats", "off"));
+            if (fs_flow_stats_sample(s) != FS_EINVAL) return 23;
+        }
         CHECK(fs_set_option(s, "solver", "gs_lex"));
         CHECK(fs_run_one(s));
         CHECK(fs_destroy(s));
