@@ -5,7 +5,8 @@ when the first `Simulation` is created and there is no CPU fallback.
 """
 from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_PREV, VY, VY_PREV, VZ, VZ_PREV,
                    STAT_MEAN_DENS, STAT_MEAN_P, STAT_MEAN_VX, STAT_MEAN_VY, STAT_MEAN_VZ, STAT_NAMES, STAT_PP, STAT_RAW, STAT_TKE,
-                   STAT_UU, STAT_UV, STAT_UW, STAT_VV, STAT_VW, STAT_WW, FluidsimError)
+                   STAT_UU, STAT_UV, STAT_UW, STAT_VV, STAT_VW, STAT_WW, ISO_VORTEX, VORTEX_NAMES, VORTEX_Q, VORTEX_W2, VORTEX_WX,
+                   VORTEX_WY, VORTEX_WZ, FluidsimError)
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
                          solve_reduction)
 
@@ -14,4 +15,5 @@ __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_for
            "FIELD_NAMES", "STAT_NAMES",
            "STAT_MEAN_DENS", "STAT_MEAN_VX", "STAT_MEAN_VY", "STAT_MEAN_VZ", "STAT_MEAN_P", "STAT_UU", "STAT_VV", "STAT_WW",
            "STAT_UV", "STAT_UW", "STAT_VW", "STAT_PP", "STAT_TKE", "STAT_RAW",
+           "VORTEX_WX", "VORTEX_WY", "VORTEX_WZ", "VORTEX_W2", "VORTEX_Q", "VORTEX_NAMES", "ISO_VORTEX",
            "DENS", "VX", "VY", "VZ", "OBS", "PRESSURE", "DIVERGENCE", "VX_PREV", "VY_PREV", "VZ_PREV", "BUFFER"]

@@ -26,6 +26,12 @@ RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, 
  STAT_UU, STAT_VV, STAT_WW, STAT_UV, STAT_UW, STAT_VW, STAT_PP, STAT_TKE) = range(13)
 STAT_RAW = 256
 STAT_NAMES = ["mean_dens", "mean_vx", "mean_vy", "mean_vz", "mean_p", "uu", "vv", "ww", "uv", "uw", "vw", "pp", "tke"]
+# FS_VORTEX_*: selectors of fs_vortex_field -- the three vorticity components, |omega|^2, Q; ISO_VORTEX or-ed in makes one
+# of them a source of fs_isosurface.  VORTEX_NAMES: the file stems of fs_vortex_dump
+VORTEX_WX, VORTEX_WY, VORTEX_WZ, VORTEX_W2, VORTEX_Q = range(5)
+VORTEX_NFIELDS = 5
+ISO_VORTEX = 512
+VORTEX_NAMES = ["vort_x", "vort_y", "vort_z", "vort_sq", "q"]
 
 
 class FluidsimError(RuntimeError):
@@ -82,6 +88,10 @@ _SIGNATURES = {
     "fs_flow_stats_reset": (C.c_int, [C.c_void_p]),
     "fs_flow_stats_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_flow_stats_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fs_vortex_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
+    "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fs_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_isosurface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

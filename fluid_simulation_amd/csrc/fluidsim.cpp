@@ -18,6 +18,7 @@
 #include "forces.h"
 #include "residual.h"
 #include "flow_stats.h"
+#include "vortex.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -53,8 +54,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -101,6 +102,9 @@ struct EngineBase {
     virtual int flow_stats_sample() = 0;
     virtual int flow_stats_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int flow_stats_dump(const char* dir) = 0;
+    virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
+    virtual int vortex_dump(const char* dir) = 0;
+    virtual int isosurface(int source, double level) = 0;
 };
 
 struct fs_sim {
@@ -175,6 +179,10 @@ struct fs_sim {
     std::vector<float> surf_verts;
     std::vector<int> surf_tris;
     bool surf_valid = false;
+    // result of the last fs_isosurface call (a slot of its own)
+    std::vector<float> iso_verts;
+    std::vector<int> iso_tris;
+    bool iso_valid = false;
     bool dump_async = true;
     fs::SweepTune tune;          // launch tunables of this handle (fs_set_option sweep_* / pair_* / project_kernels)
 
@@ -300,6 +308,9 @@ struct Engine : EngineBase {
     fs::FlowStatsAcc stat_acc = {};
     int stat_nacc = 0;                  // accumulators allocated: 0, 5 or 12
     long stat_gen = -1;                 // S->flow_stats_gen they were set up for
+    // vortex identification (vortex.h): the one field a call computes, in the fields' layout (LEAD-shifted like them); private,
+    // allocated at the first call.  Only the kernel writes it, and only cells of interior rows: its ghosts stay +0.0.
+    T* vort = nullptr;
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -423,6 +434,7 @@ struct Engine : EngineBase {
         if (res_scratch) hipFree(res_scratch);
         if (res_partial) hipFree(res_partial);
         for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
+        if (vort) hipFree(vort - g.lead);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1639,28 +1651,129 @@ struct Engine : EngineBase {
     }
 
     // ---- the viewer's obstacle mesh (GUI/utils.py:10-38) ------------------------------------------
-    int obstacle_surface() override
+    // the mesh of `field` > `level` into one of the handle's two result slots
+    int surface_into(const T* field, T level, std::vector<float>& verts, std::vector<int>& tris, bool& valid)
     {
-        S->surf_verts.clear();
-        S->surf_tris.clear();
-        S->surf_valid = false;
-        if (S->comm.active()) return fail(FS_EINVAL, "the obstacle surface is extracted on a single-GPU handle");
+        verts.clear();
+        tris.clear();
+        valid = false;
         fs::SurfaceResult r;
         const char* msg = "";
-        int rc = fs::extract_surface<T>(S->stream, g, arr[slot[FS_OBS]], &r, &msg);
+        int rc = fs::extract_surface<T>(S->stream, g, field, level, &r, &msg);
         if (rc) return fail(rc, "%s", msg);
-        S->surf_verts.resize((size_t)r.nverts * 3);
-        S->surf_tris.resize((size_t)r.ntris * 3);
+        verts.resize((size_t)r.nverts * 3);
+        tris.resize((size_t)r.ntris * 3);
         hipError_t e = hipSuccess;
         if (r.nverts > 0) {
-            e = hipMemcpyAsync(S->surf_verts.data(), r.d_verts, S->surf_verts.size() * sizeof(float), hipMemcpyDeviceToHost, S->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(S->surf_tris.data(), r.d_tris, S->surf_tris.size() * sizeof(int), hipMemcpyDeviceToHost, S->stream);
+            e = hipMemcpyAsync(verts.data(), r.d_verts, verts.size() * sizeof(float), hipMemcpyDeviceToHost, S->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(tris.data(), r.d_tris, tris.size() * sizeof(int), hipMemcpyDeviceToHost, S->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(S->stream);
         }
         fs::surface_free(&r);
-        if (e != hipSuccess) return fail(FS_EHIP, "copying the obstacle surface: %s", hipGetErrorString(e));
-        S->surf_valid = true;
+        if (e != hipSuccess) return fail(FS_EHIP, "copying the surface: %s", hipGetErrorString(e));
+        valid = true;
         return FS_OK;
+    }
+
+    int obstacle_surface() override
+    {
+        S->surf_valid = false;
+        if (S->comm.active()) return fail(FS_EINVAL, "the obstacle surface is extracted on a single-GPU handle");
+        return surface_into(arr[slot[FS_OBS]], (T)0.5, S->surf_verts, S->surf_tris, S->surf_valid);
+    }
+
+    // ---- vortex identification (vortex.h; beyond the reference) and iso-surfaces of any field -------------
+    // One field into `vort`.  Collective on slab handles: the stencil reads one plane of each neighbour.
+    int vortex_compute(const char* who, int which)
+    {
+        if (which < 0 || which >= FS_VORTEX_NFIELDS) return fail(FS_EINVAL, "%s: unknown vortex selector %d (0..%d)", who, which, FS_VORTEX_NFIELDS - 1);
+        if (S->comm.active() && S->comm.null_transport)
+            return fail(FS_EINVAL, "%s: vortex fields need the other slabs' planes; the FSNULL transport carries none", who);
+        int rc = ensure_flags();
+        if (rc) return rc;
+        for (int f : { FS_VX, FS_VY, FS_VZ })
+            if ((rc = halo(arr[slot[f]]))) return rc;
+        if (!vort) {
+            T* base = nullptr;
+            const hipError_t e = hipMalloc((void**)&base, (size_t)g.n * sizeof(T));
+            if (e != hipSuccess) return fail(FS_ENOMEM, "%s: scratch array of %zu bytes: %s", who, (size_t)g.n * sizeof(T), hipGetErrorString(e));
+            vort = base + g.lead;
+            HIP_TRY(hipMemsetAsync(base, 0, (size_t)g.n * sizeof(T), S->stream));
+        }
+        ScopedSpan sp(S, FAM_VORTEX);
+        fs::launch_vortex<T>(S->stream, S->tune, g, sc, which, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], flags, vort);
+        return FS_OK;
+    }
+
+    int vortex_field(int which, void* dst, size_t n, int elem) override
+    {
+        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_vortex_field: expected %ld elements, got %zu", dense_cells(), n);
+        if (elem != 4 && elem != 8) return fail(FS_EINVAL, "fs_vortex_field: elem_size must be 4 or 8");
+        int rc = vortex_compute("fs_vortex_field", which);
+        if (rc) return rc;
+        if ((rc = need_dense(n * (size_t)elem))) return rc;
+        if (elem == 4) fs::launch_pack<T, float>(S->stream, g, vort, (float*)dense, 0, g.D + 1);
+        else fs::launch_pack<T, double>(S->stream, g, vort, (double*)dense, 0, g.D + 1);
+        HIP_TRY(hipMemcpyAsync(dst, dense, n * elem, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int vortex_dump(const char* dir) override
+    {
+        static const char* const names[FS_VORTEX_NFIELDS] = { "vort_x.bin", "vort_y.bin", "vort_z.bin", "vort_sq.bin", "q.bin" };
+        if (S->comm.active() && S->comm.null_transport)
+            return fail(FS_EINVAL, "fs_vortex_dump: vortex fields need the other slabs' planes; the FSNULL transport carries none");
+        int rc = FS_OK;
+        // rank 0 truncates; the other slab ranks open the files for update once they exist (as fs_flow_stats_dump does)
+        const bool lead = !S->comm.active() || S->comm.rank == 0;
+        FILE* fp[FS_VORTEX_NFIELDS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool ok = true;
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((pass == 0) == lead)
+                for (int k = 0; k < FS_VORTEX_NFIELDS; ++k) {
+                    fp[k] = fopen((std::string(dir) + "/" + names[k]).c_str(), lead ? "wb" : "r+b");
+                    if (!fp[k]) ok = false;
+                }
+            if (pass == 0 && S->comm.active()) {
+                if (S->comm.shm && S->comm.shm_ready(g, S->D)) return fail(FS_ECOMM, "%s", S->comm.last_error());
+                if ((rc = slab_barrier())) return rc;
+            }
+        }
+        // local planes written by this rank: its interior planes, plus the physical ghost planes
+        const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
+        const size_t plane = (size_t)(g.W + 2) * (g.H + 2);
+        std::vector<float> h((size_t)dense_cells());
+        for (int k = 0; k < FS_VORTEX_NFIELDS && !rc; ++k) {     // every rank computes all five (collective), whatever its files do
+            rc = vortex_field(k, h.data(), h.size(), 4);
+            if (rc || !ok || !fp[k]) continue;
+            if (fseek(fp[k], (long)(plane * (size_t)(sc.zoff + zlo) * sizeof(float)), SEEK_SET) != 0 ||
+                fwrite(h.data() + plane * (size_t)zlo, sizeof(float), plane * (size_t)(zhi - zlo + 1), fp[k]) != plane * (size_t)(zhi - zlo + 1))
+                ok = false;
+        }
+        for (int k = 0; k < FS_VORTEX_NFIELDS; ++k)
+            if (fp[k] && fclose(fp[k]) != 0) ok = false;
+        if (S->comm.active() && !rc) rc = slab_barrier();     // every rank's planes are in the files
+        if (rc) return rc;
+        if (!ok) return fail(FS_EIO, "fs_vortex_dump: cannot write the vortex frames under '%s'", dir);
+        return FS_OK;
+    }
+
+    int isosurface(int source, double level) override
+    {
+        S->iso_valid = false;
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_isosurface: iso-surfaces are extracted on a single-GPU handle");
+        const T* field = nullptr;
+        if (source >= 0 && source < FS_NFIELDS) {
+            field = arr[slot[source]];
+        } else if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS) {
+            int rc = vortex_compute("fs_isosurface", source & (FS_ISO_VORTEX - 1));
+            if (rc) return rc;
+            field = vort;
+        } else {
+            return fail(FS_EINVAL, "fs_isosurface: unknown source %d (a field selector, or FS_ISO_VORTEX | FS_VORTEX_*)", source);
+        }
+        return surface_into(field, (T)level, S->iso_verts, S->iso_tris, S->iso_valid);
     }
 
     int apply_solid_cells(const int* cells, long n) override
@@ -2354,6 +2467,10 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         int f = atoi(value);
         if (f < 1 || f > 4) return fail(FS_EINVAL, "sweep_fuse: 1 | 2 | 3 | 4");
         s->tune.fuse = f;
+    } else if (k == "vortex_ry") {
+        int r = atoi(value);
+        if (r != 1 && r != 2) return fail(FS_EINVAL, "vortex_ry: 1 | 2");
+        s->tune.vortex_ry = r;
     } else if (k == "project_kernels") {
         if (v == "cell") s->tune.project_cell = 1;
         else if (v == "march") s->tune.project_cell = 0;
@@ -2699,6 +2816,25 @@ int fs_obstacle_surface_fetch(fs_sim* s, float* vertices, int* triangles)
     return FS_OK;
 }
 
+int fs_isosurface(fs_sim* s, int source, double level, long* n_vertices, long* n_triangles)
+{
+    ENGINE_OR_RETURN(s);
+    int rc = s->eng->isosurface(source, level);
+    if (rc) return rc;
+    if (n_vertices) *n_vertices = (long)(s->iso_verts.size() / 3);
+    if (n_triangles) *n_triangles = (long)(s->iso_tris.size() / 3);
+    return FS_OK;
+}
+
+int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (!s->iso_valid) return fail(FS_EINVAL, "fs_isosurface has not been called");
+    if (vertices && !s->iso_verts.empty()) memcpy(vertices, s->iso_verts.data(), s->iso_verts.size() * sizeof(float));
+    if (triangles && !s->iso_tris.empty()) memcpy(triangles, s->iso_tris.data(), s->iso_tris.size() * sizeof(int));
+    return FS_OK;
+}
+
 int fs_surface_case_table(int config, int* edges)
 {
     if (!edges) return fail(FS_EINVAL, "null buffer");
@@ -2758,6 +2894,19 @@ int fs_flow_stats_dump(fs_sim* s, const char* dir)
     ENGINE_OR_RETURN(s);
     if (!dir) return fail(FS_EINVAL, "null directory");
     return s->eng->flow_stats_dump(dir);
+}
+
+int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dst) return fail(FS_EINVAL, "null buffer");
+    return s->eng->vortex_field(which, dst, n_elems, elem_size);
+}
+int fs_vortex_dump(fs_sim* s, const char* dir)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dir) return fail(FS_EINVAL, "null directory");
+    return s->eng->vortex_dump(dir);
 }
 
 int fs_comm_unique_id(void* id_out)

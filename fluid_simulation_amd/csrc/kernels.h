@@ -53,6 +53,7 @@ struct SweepTune {
                               // three-sweep kernel per grid and use it where a sweep costs less, 4 use it wherever it exists
     int pair_zc = 0;          // planes per z chunk of the pair kernel; 0 = automatic
     int project_cell = 0;     // 1 = per-cell divergence/gradient kernels instead of the z-marching ones
+    int vortex_ry = 2;        // rows per wave of the vortex kernel (vortex.hip): 1 or 2; speed only, every bit is the same
     int pair_shape = 0;       // >0 forces a pair-kernel workgroup shape (1 = 8, 2 = 10, 3 = 16 waves); 0 = timed choice
     int advect_cell = 1;      // 1 (default) = per-cell advection kernels; 2 = the same with clamp tables; 3 = the tile kernels (clamp
                               // tables staged in LDS, for rough flows; single GPU, else as 2); 0 = the row kernels (four
@@ -196,5 +197,13 @@ void launch_flow_stats(hipStream_t st, const GridDesc& g, int nacc, bool first, 
 // of the accumulators' layout (allocation base).  zero_lo / zero_hi: local plane 0 / D + 1 is an inter-slab halo, written 0.
 void launch_flow_stats_finalize(hipStream_t st, const GridDesc& g, const FlowStatsAcc& acc, int which, bool raw, long n,
                                 bool zero_lo, bool zero_hi, double* out);
+
+// Vortex identification (vortex.h has the arithmetic, vortex.hip the z-marching kernel).  One field, `which` = VORTEX_WX ..
+// VORTEX_Q, of the velocities vx, vy, vz into `out`, an array of the fields' layout (LEAD-shifted like them): rows 1..H of
+// planes 1..D are written whole -- target cells (flags without F_SOLID) the value, the others +0.0 -- and nothing else is,
+// so `out` must hold +0.0 in its ghost column, rows and planes beforehand.  Reads planes 0..D+1 of the velocities.
+template <class T>
+void launch_vortex(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int which, const T* vx,
+                   const T* vy, const T* vz, const uint8_t* flags, T* out);
 
 }  // namespace fs

@@ -740,39 +740,7 @@ __device__ __forceinline__ T one_sided_grad(bool fp, bool fm, T pp, T pc, T pm, 
 // HBM once.  Arithmetic and pass order are those of the per-cell kernels below, which remain
 // as the plain statement (and serve fs_set_option "project_kernels"="cell").
 // =====================================================================================
-template <class T>
-struct MarchTile {
-    int lane, x0, y0, zbeg, zend;
-    bool lane_on, full_group, edge_l, edge_r, live;
-    long row0;
-};
-template <class T, int RY>
-__device__ __forceinline__ MarchTile<T> march_tile(const GridDesc& g, int zc_len, int nxw, int nybg, int nblk)
-{
-    MarchTile<T> t;
-    const int v = xcd_contiguous(blockIdx.x, nblk);
-    const int xw = v % nxw, ybg = (v / nxw) % nybg, zc = v / (nxw * nybg);
-    t.lane = threadIdx.x & 63;
-    t.y0 = 1 + (ybg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RY;   // wave-uniform row: scalar tests and row pointers
-    t.x0 = 1 + xw * 256 + t.lane * 4;
-    t.lane_on = t.x0 <= g.W;
-    t.zbeg = 1 + zc * zc_len;
-    t.zend = min(g.D, t.zbeg + zc_len - 1);
-    t.full_group = (t.x0 + 3 <= g.W);
-    t.edge_l = t.lane_on && (t.lane == 0);
-    t.edge_r = t.lane_on && t.full_group && ((t.lane == 63) || (t.x0 + 4 > g.W));
-    t.live = (t.y0 <= g.H) && (t.zbeg <= t.zend);
-    t.row0 = cell(g, t.x0, t.y0, 0);
-    return t;
-}
-template <class T>
-__device__ __forceinline__ void ld_row(const T* ptr, bool on, T (&out)[4])
-{
-    V4<T> q = {{(T)0, (T)0, (T)0, (T)0}};
-    if (on) q = *reinterpret_cast<const V4<T>*>(ptr);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) out[e] = q.e[e];
-}
+// (MarchTile, march_tile and ld_row live in kernels_dev.h: vortex.hip marches the same way)
 // Store the lane's four cells of an interior row of a field with boundary code b, the way
 // setBounds leaves them (simulation.cpp:183-246): `u` un-zeroed values, `killmask` bit e set =>
 // cell e is zeroed; ghost faces determined by this row are written from the un-zeroed values.
@@ -949,24 +917,7 @@ __global__ __launch_bounds__(256) void gradient_march_kernel(GridDesc g, SlabCtx
     }
 }
 
-struct MarchLaunch {
-    int zc_len, nxw, nybg, nblk;
-};
-static MarchLaunch march_launch(const GridDesc& g, int RY)
-{
-    MarchLaunch m;
-    m.nxw = (g.W + 255) / 256;
-    const int nyb = (g.H + RY - 1) / RY;
-    m.nybg = (nyb + 3) / 4;
-    const long per_layer = (long)m.nxw * m.nybg;
-    long want = (2048 + per_layer - 1) / per_layer;
-    if (want < 1) want = 1;
-    m.zc_len = (int)((g.D + want - 1) / want);
-    if (m.zc_len < 8) m.zc_len = g.D < 8 ? g.D : 8;
-    const int nzc = (g.D + m.zc_len - 1) / m.zc_len;
-    m.nblk = (int)(per_layer * nzc);
-    return m;
-}
+// (MarchLaunch / march_launch: kernels_dev.h)
 
 // =====================================================================================
 // Stand-alone setBounds (simulation.cpp:183-246): faces first, then the zeroing passes.

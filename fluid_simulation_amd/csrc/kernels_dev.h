@@ -51,4 +51,61 @@ __device__ __forceinline__ int xcd_contiguous(int b, int nblk)
     return k * q + (k < r ? k : r) + (b >> 3);
 }
 
+// The tile of a z-marching kernel (the two projection passes in kernels.hip, the vortex fields in vortex.hip): a wave owns
+// 256 x-consecutive cells x RY rows, a lane four x-consecutive cells of each (one 16-byte access per row), and walks planes
+// zbeg..zend; workgroup = four waves = 4 * RY rows.
+template <class T>
+struct MarchTile {
+    int lane, x0, y0, zbeg, zend;
+    bool lane_on, full_group, edge_l, edge_r, live;
+    long row0;
+};
+template <class T, int RY>
+__device__ __forceinline__ MarchTile<T> march_tile(const GridDesc& g, int zc_len, int nxw, int nybg, int nblk)
+{
+    MarchTile<T> t;
+    const int v = xcd_contiguous(blockIdx.x, nblk);
+    const int xw = v % nxw, ybg = (v / nxw) % nybg, zc = v / (nxw * nybg);
+    t.lane = threadIdx.x & 63;
+    t.y0 = 1 + (ybg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RY;   // wave-uniform row: scalar tests and row pointers
+    t.x0 = 1 + xw * 256 + t.lane * 4;
+    t.lane_on = t.x0 <= g.W;
+    t.zbeg = 1 + zc * zc_len;
+    t.zend = min(g.D, t.zbeg + zc_len - 1);
+    t.full_group = (t.x0 + 3 <= g.W);
+    t.edge_l = t.lane_on && (t.lane == 0);
+    t.edge_r = t.lane_on && t.full_group && ((t.lane == 63) || (t.x0 + 4 > g.W));
+    t.live = (t.y0 <= g.H) && (t.zbeg <= t.zend);
+    t.row0 = cell(g, t.x0, t.y0, 0);
+    return t;
+}
+template <class T>
+__device__ __forceinline__ void ld_row(const T* ptr, bool on, T (&out)[4])
+{
+    V4<T> q = {{(T)0, (T)0, (T)0, (T)0}};
+    if (on) q = *reinterpret_cast<const V4<T>*>(ptr);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) out[e] = q.e[e];
+}
+
+// the launch shape of those kernels: about 2048 workgroups, z chunks of at least 8 planes
+struct MarchLaunch {
+    int zc_len, nxw, nybg, nblk;
+};
+inline MarchLaunch march_launch(const GridDesc& g, int RY)
+{
+    MarchLaunch m;
+    m.nxw = (g.W + 255) / 256;
+    const int nyb = (g.H + RY - 1) / RY;
+    m.nybg = (nyb + 3) / 4;
+    const long per_layer = (long)m.nxw * m.nybg;
+    long want = (2048 + per_layer - 1) / per_layer;
+    if (want < 1) want = 1;
+    m.zc_len = (int)((g.D + want - 1) / want);
+    if (m.zc_len < 8) m.zc_len = g.D < 8 ? g.D : 8;
+    const int nzc = (g.D + m.zc_len - 1) / m.zc_len;
+    m.nblk = (int)(per_layer * nzc);
+    return m;
+}
+
 }  // namespace fs

@@ -34,11 +34,12 @@ struct SurfaceResult {
     int* d_tris = nullptr;      // 3 * ntris vertex indices
 };
 
-// Iso-surface of obs at 0.5 over the padded box (0..W+1) x (0..H+1) x (0..D+1).  Synchronises the
-// stream (the host needs the counts to size the output).  Returns 0, or a negative FS_* code with
-// `err` set.  Free the result with surface_free.
+// Iso-surface of a field (`obs` at 0.5 for the obstacle mesh; fs_isosurface passes any field and level): the mesh of
+// value > level over the padded box (0..W+1) x (0..H+1) x (0..D+1), NaN outside, the vertex on a crossing edge at
+// t = (level - v0) / (v1 - v0) computed in T.  Synchronises the stream (the host needs the counts to size the
+// output).  Returns 0, or a negative FS_* code with `err` set.  Free the result with surface_free.
 template <class T>
-int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, SurfaceResult* out, const char** err);
+int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, T level, SurfaceResult* out, const char** err);
 void surface_free(SurfaceResult* r);
 
 }  // namespace fs

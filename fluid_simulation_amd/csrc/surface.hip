@@ -1,6 +1,8 @@
-// surface.hip -- see surface.h.  Marching cubes over the padded obstacle array at level 0.5:
-// one vertex per grid edge whose end points lie on different sides of 0.5 (placed by linear
-// interpolation; obs is 0/1, so at the edge's midpoint), triangles from a 256-entry case table.
+// surface.hip -- see surface.h.  Marching cubes over a padded field array at a level (the obstacle
+// array at 0.5, or any field at any level): one vertex per grid edge whose end points lie on
+// different sides of the level (placed by linear interpolation; obs is 0/1, so at the edge's
+// midpoint), triangles from a 256-entry case table.  "Inside" (the text below says solid) = value > level;
+// NaN is outside.
 //
 // The table is not copied from anywhere: it is constructed at first use (build_table) from the
 // geometry of the cube -- on every cube face the crossing points are joined by segments, the
@@ -163,29 +165,29 @@ __constant__ unsigned char c_ntri[256];
 __constant__ unsigned char c_edges[256][3 * SURF_MAX_TRIS];
 
 template <class T>
-__device__ __forceinline__ bool solid(T v) { return v > (T)0.5; }
+__device__ __forceinline__ bool solid(T v, T level) { return v > level; }
 
 constexpr int VB_SHIFT = 28;                             // vbase word: first vertex index | (owned-edge mask << 28)
 constexpr int VB_MASK = (1 << VB_SHIFT) - 1;
 
-// crossing edges owned by grid point (x, y, z): bit a set <=> the edge towards +axis a crosses 0.5
+// crossing edges owned by grid point (x, y, z): bit a set <=> the edge towards +axis a crosses the level
 template <class T>
-__device__ __forceinline__ unsigned owned_edges(const GridDesc& g, const T* __restrict__ obs, int x, int y, int z, long c)
+__device__ __forceinline__ unsigned owned_edges(const GridDesc& g, const T* __restrict__ obs, T level, int x, int y, int z, long c)
 {
-    const bool in0 = solid(obs[c]);
+    const bool in0 = solid(obs[c], level);
     unsigned m = 0;
-    if (x <= g.W && solid(obs[c + 1]) != in0) m |= 1u;
-    if (y <= g.H && solid(obs[c + g.sy]) != in0) m |= 2u;
-    if (z <= g.D && solid(obs[c + g.sz]) != in0) m |= 4u;
+    if (x <= g.W && solid(obs[c + 1], level) != in0) m |= 1u;
+    if (y <= g.H && solid(obs[c + g.sy], level) != in0) m |= 2u;
+    if (z <= g.D && solid(obs[c + g.sz], level) != in0) m |= 4u;
     return m;
 }
 template <class T>
-__device__ __forceinline__ unsigned cube_config(const GridDesc& g, const T* __restrict__ obs, long c)
+__device__ __forceinline__ unsigned cube_config(const GridDesc& g, const T* __restrict__ obs, T level, long c)
 {
     unsigned cfg = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-        if (solid(obs[c + (i & 1) + ((i >> 1) & 1) * g.sy + ((i >> 2) & 1) * g.sz])) cfg |= 1u << i;
+        if (solid(obs[c + (i & 1) + ((i >> 1) & 1) * g.sy + ((i >> 2) & 1) * g.sz], level)) cfg |= 1u << i;
     return cfg;
 }
 
@@ -214,15 +216,15 @@ __device__ __forceinline__ int block_scan256(int v, int* total)
 
 // pass 1: vertices and triangles per grid row (y, z)
 template <class T>
-__global__ __launch_bounds__(256) void surf_count_kernel(GridDesc g, const T* __restrict__ obs, int* __restrict__ rowV,
+__global__ __launch_bounds__(256) void surf_count_kernel(GridDesc g, const T* __restrict__ obs, T level, int* __restrict__ rowV,
                                                           int* __restrict__ rowT)
 {
     const int row = blockIdx.x, y = row % (g.H + 2), z = row / (g.H + 2);
     int nv = 0, nt = 0;
     for (int x = threadIdx.x; x <= g.W + 1; x += 256) {
         const long c = cell(g, x, y, z);
-        nv += __popc(owned_edges(g, obs, x, y, z, c));
-        if (x <= g.W && y <= g.H && z <= g.D) nt += c_ntri[cube_config(g, obs, c)];
+        nv += __popc(owned_edges(g, obs, level, x, y, z, c));
+        if (x <= g.W && y <= g.H && z <= g.D) nt += c_ntri[cube_config(g, obs, level, c)];
     }
     int tv, tt;
     block_scan256(nv, &tv);
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(256) void surf_scan_kernel(const int* __restrict__ 
 
 // pass 3: vertices, and per grid point the index of its first vertex + which of its three edges cross
 template <class T>
-__global__ __launch_bounds__(256) void surf_vertex_kernel(GridDesc g, const T* __restrict__ obs, const int* __restrict__ rowVoff,
+__global__ __launch_bounds__(256) void surf_vertex_kernel(GridDesc g, const T* __restrict__ obs, T level, const int* __restrict__ rowVoff,
                                                            int* __restrict__ vbase, float* __restrict__ verts)
 {
     const int row = blockIdx.x, y = row % (g.H + 2), z = row / (g.H + 2);
@@ -262,19 +264,19 @@ __global__ __launch_bounds__(256) void surf_vertex_kernel(GridDesc g, const T* _
         const int x = x0 + threadIdx.x;
         const bool on = x <= g.W + 1;
         const long c = cell(g, on ? x : 0, y, z);
-        const unsigned m = on ? owned_edges(g, obs, x, y, z, c) : 0u;
+        const unsigned m = on ? owned_edges(g, obs, level, x, y, z, c) : 0u;
         int tot;
         const int first = running + block_scan256(__popc(m), &tot);
         running += tot;
         if (!on) continue;
         vbase[dense_row + x] = first | (int)(m << VB_SHIFT);
-        const float v0 = (float)obs[c];
+        const T v0 = obs[c];
         int k = first;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             if (!(m & (1u << a))) continue;
-            const float v1 = (float)obs[c + (a == 0 ? 1 : a == 1 ? g.sy : g.sz)];
-            const float t = (0.5f - v0) / (v1 - v0);         // linear interpolation to the 0.5 level
+            const T v1 = obs[c + (a == 0 ? 1 : a == 1 ? g.sy : g.sz)];
+            const float t = (float)((level - v0) / (v1 - v0));   // linear interpolation to the level, in T: in [0, 1] as v0, v1 straddle it
             verts[3 * (long)k + 0] = (float)x + (a == 0 ? t : 0.0f);
             verts[3 * (long)k + 1] = (float)y + (a == 1 ? t : 0.0f);
             verts[3 * (long)k + 2] = (float)z + (a == 2 ? t : 0.0f);
@@ -285,7 +287,7 @@ __global__ __launch_bounds__(256) void surf_vertex_kernel(GridDesc g, const T* _
 
 // pass 4: triangles of every cube, vertex indices through vbase of the grid point that owns the edge
 template <class T>
-__global__ __launch_bounds__(256) void surf_triangle_kernel(GridDesc g, const T* __restrict__ obs, const int* __restrict__ rowToff,
+__global__ __launch_bounds__(256) void surf_triangle_kernel(GridDesc g, const T* __restrict__ obs, T level, const int* __restrict__ rowToff,
                                                              const int* __restrict__ vbase, int* __restrict__ tris)
 {
     const int row = blockIdx.x, y = row % (g.H + 2), z = row / (g.H + 2);
@@ -296,7 +298,7 @@ __global__ __launch_bounds__(256) void surf_triangle_kernel(GridDesc g, const T*
     for (int x0 = 0; x0 <= g.W; x0 += 256) {
         const int x = x0 + threadIdx.x;
         const bool on = x <= g.W;
-        const unsigned cfg = on ? cube_config(g, obs, cell(g, x, y, z)) : 0u;
+        const unsigned cfg = on ? cube_config(g, obs, level, cell(g, x, y, z)) : 0u;
         const int nt = c_ntri[cfg];
         int tot;
         int k = running + block_scan256(nt, &tot);
@@ -352,11 +354,11 @@ void surface_free(SurfaceResult* r)
 }
 
 template <class T>
-int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, SurfaceResult* out, const char** err)
+int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, T level, SurfaceResult* out, const char** err)
 {
     static const char* msg_table = "the marching-cubes case table failed its construction checks";
     static const char* msg_hip = "HIP call failed during surface extraction";
-    static const char* msg_big = "obstacle surface too large (more than 2^28 vertices or 2^30 triangles)";
+    static const char* msg_big = "surface too large (more than 2^28 vertices or 2^30 triangles)";
     *out = SurfaceResult();
     if (!table().ok) { *err = msg_table; return FS_EINVAL; }
     if (upload_table() != hipSuccess) { *err = msg_hip; return FS_EHIP; }
@@ -370,7 +372,7 @@ int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, SurfaceResu
             hipMalloc((void**)&vbase, sizeof(int) * (size_t)npoints) != hipSuccess) { *err = msg_hip; rc = FS_ENOMEM; break; }
         int *rowV = rows, *rowT = rows + nrows, *offV = rows + 2 * nrows, *offT = offV + nrows + 1, *ovf = offT + nrows + 1;
         if (hipMemsetAsync(ovf, 0, sizeof(int), st) != hipSuccess) { *err = msg_hip; rc = FS_EHIP; break; }
-        hipLaunchKernelGGL((surf_count_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, rowV, rowT);
+        hipLaunchKernelGGL((surf_count_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, level, rowV, rowT);
         hipLaunchKernelGGL(surf_scan_kernel, dim3(1), dim3(256), 0, st, rowV, offV, nrows, VB_MASK, ovf);
         hipLaunchKernelGGL(surf_scan_kernel, dim3(1), dim3(256), 0, st, rowT, offT, nrows, 1 << 30, ovf);
         if (hipMemcpyAsync(&totals[0], offV + nrows, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -383,8 +385,8 @@ int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, SurfaceResu
         if (out->nverts == 0 || out->ntris == 0) { out->nverts = out->ntris = 0; break; }
         if (hipMalloc((void**)&out->d_verts, sizeof(float) * 3 * (size_t)out->nverts) != hipSuccess ||
             hipMalloc((void**)&out->d_tris, sizeof(int) * 3 * (size_t)out->ntris) != hipSuccess) { *err = msg_hip; rc = FS_ENOMEM; break; }
-        hipLaunchKernelGGL((surf_vertex_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, offV, vbase, out->d_verts);
-        hipLaunchKernelGGL((surf_triangle_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, offT, vbase, out->d_tris);
+        hipLaunchKernelGGL((surf_vertex_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, level, offV, vbase, out->d_verts);
+        hipLaunchKernelGGL((surf_triangle_kernel<T>), dim3(nrows), dim3(256), 0, st, g, obs, level, offT, vbase, out->d_tris);
         if (hipStreamSynchronize(st) != hipSuccess) { *err = msg_hip; rc = FS_EHIP; break; }
     } while (0);
     if (rows) hipFree(rows);
@@ -392,7 +394,7 @@ int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, SurfaceResu
     if (rc) surface_free(out);
     return rc;
 }
-template int extract_surface<float>(hipStream_t, const GridDesc&, const float*, SurfaceResult*, const char**);
-template int extract_surface<double>(hipStream_t, const GridDesc&, const double*, SurfaceResult*, const char**);
+template int extract_surface<float>(hipStream_t, const GridDesc&, const float*, float, SurfaceResult*, const char**);
+template int extract_surface<double>(hipStream_t, const GridDesc&, const double*, double, SurfaceResult*, const char**);
 
 }  // namespace fs

@@ -338,6 +338,32 @@ class Simulation:
         viewers read: data, obs, v_x, v_y, v_z, p and (mode "moments") tke .bin (fs_flow_stats_dump; collective on z-slabs)."""
         check(self._L.fs_flow_stats_dump(self._h, os.fsencode(dir)))
 
+    def vortex(self, which, dtype=None):
+        """One vortex-identification field of the velocities as they are now (fs_vortex_field; collective on z-slabs):
+        `which` is VORTEX_WX, VORTEX_WY, VORTEX_WZ (vorticity components), VORTEX_W2 (|omega|^2) or VORTEX_Q (the
+        Q-criterion), per cell; 0 in solid and ghost cells.  Shaped like get(); float64 unless dtype says float32."""
+        dtype = np.dtype(dtype or np.float64)
+        n = self._L.fs_padded_size(self._h)
+        out = np.empty(n, dtype=dtype)
+        check(self._L.fs_vortex_field(self._h, int(which), out.ctypes.data_as(C.c_void_p), n, dtype.itemsize))
+        return out.reshape(self.shape)
+
+    def vortex_dump(self, dir):
+        """Writes the five vortex fields as one float32 frame per file under `dir`, in the frame-dump layout:
+        vort_x, vort_y, vort_z, vort_sq and q .bin (fs_vortex_dump; collective on z-slabs)."""
+        check(self._L.fs_vortex_dump(self._h, os.fsencode(dir)))
+
+    def isosurface(self, source, level):
+        """The triangle mesh of {source > level} over the padded box (fs_isosurface; single-GPU handles): `source` is a
+        field selector (DENS .. BUFFER) or ISO_VORTEX | VORTEX_*.  Returns (vertices (n, 3) float32 in the viewer's
+        padded (x, y, z) index space, faces (m, 3) int32), normals pointing from inside to outside."""
+        nv, nt = C.c_long(), C.c_long()
+        check(self._L.fs_isosurface(self._h, int(source), float(level), C.byref(nv), C.byref(nt)))
+        verts = np.zeros((nv.value, 3), dtype=np.float32)
+        faces = np.zeros((nt.value, 3), dtype=np.int32)
+        check(self._L.fs_isosurface_fetch(self._h, verts.ctypes.data, faces.ctypes.data))
+        return verts, faces
+
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()
         check(self._L.fs_time_sweeps(self._h, b, field, prev, a, c, reps, C.byref(ms)))

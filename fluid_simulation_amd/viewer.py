@@ -52,9 +52,20 @@ def generate_obstacle_mesh(obs_data):
     if sim is None:
         sim = _handles[shape] = Simulation(shape[0], shape[1], shape[2], 1, quiet=1, dump_every=0)
     sim.set(_lib.OBS, np.ascontiguousarray(np.transpose(obs_data, (2, 1, 0)), dtype=np.float32))
-    verts, faces = sim.obstacle_surface()
+    return _mesh_dict(*sim.obstacle_surface())
+
+
+def _mesh_dict(verts, faces):
     if verts.shape[0] == 0:
         return {"vertexes": np.array([]), "faces": np.array([]), "vertex_colors": np.array([])}
     colors = np.ones((verts.shape[0], 4))
     colors[:, :3] = 0.5
     return {"vertexes": verts.astype(np.float64), "faces": faces, "vertex_colors": colors}
+
+
+def generate_isosurface_mesh(sim, source, level):
+    """The iso-surface {source > level} of a live `Simulation` as the dictionary generate_obstacle_mesh returns
+    ('vertexes', 'faces', 'vertex_colors'): `source` is a field selector or ISO_VORTEX | VORTEX_* (for example
+    ISO_VORTEX | VORTEX_Q at a positive level: the vortex cores).  The mesh never leaves the device's index space:
+    padded (x, y, z) coordinates, as the obstacle mesh."""
+    return _mesh_dict(*sim.isosurface(source, level))

@@ -385,6 +385,57 @@ int fs_flow_stats_reset(fs_sim* s);
 int fs_flow_stats_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size);
 int fs_flow_stats_dump(fs_sim* s, const char* dir);
 
+/* ---- vortex identification (beyond the reference: it has no vorticity, no Q-criterion, no file:line counterpart) ----
+ *
+ * Let u = v_x, v = v_y, w = v_z be the stored values as they are now.  A cell is a TARGET when it is an interior cell
+ * (1..w, 1..h, 1..d; global z on slab handles) with obs != 1.  For a target cell and an axis b,
+ *     D_b f = f[+1 along b] - f[-1 along b]
+ * with neighbour values as the arrays hold them: ghost cells as setBounds left them, solid cells 0 after a step.  The
+ * velocity gradient in index units is g_ab = 0.5 * D_b a (the factor is exact).  All arithmetic is fp64 on the stored values
+ * widened, one rounding per written operation, in exactly this order, without contraction (the library is built with
+ * -ffp-contract=off):
+ *     WX = 0.5 * (D_y w - D_z v)      WY = 0.5 * (D_z u - D_x w)      WZ = 0.5 * (D_x v - D_y u)
+ *     W2 = (WX*WX + WY*WY) + WZ*WZ                  (|omega|^2; no square root on purpose: callers take it)
+ *     Q  = -0.5 * ((g_xx*g_xx + g_yy*g_yy) + g_zz*g_zz) - ((g_xy*g_yx + g_xz*g_zx) + g_yz*g_zy)
+ * Q is -1/2 g_ij g_ji = (|Omega|^2 - |S|^2) / 2, valid without assuming a divergence-free field; Q > 0 marks a vortex.
+ * Every other cell of the padded array -- solid cells, all ghost cells, and on slab handles the inter-slab halo planes -- is
+ * +0.0.  The fp64 result is rounded once to the handle's precision; elem_size then converts exactly as fs_get_field does.
+ * UNITS: the values are per cell.  With h = 1 / cbrt(w * h * d) (simulation.cpp:295) the physical vorticity is W* / h (W2 / h^2)
+ * and the physical Q is Q / h^2.
+ * A cell's value is a pure function of its 18 neighbour values and its obs: launch shape, tuning (option "vortex_ry" = 1 | 2,
+ * the rows a wave of the kernel owns) and slab split cannot change a bit.
+ *
+ * fs_vortex_field: one field, with the semantics of fs_get_field (dense padded layout, the local slab on slab handles,
+ * elem_size 4 or 8).  It changes no field.  One z-marching HIP kernel per call into a private array of the handle, allocated
+ * at the first call; without a call a step launches and allocates nothing for it.  On z-slab handles it is collective: each
+ * rank first exchanges one halo plane of v_x, v_y, v_z; a rank's owned planes and its physical ghost planes carry the
+ * single-GPU bits, the inter-slab halo planes are 0.  It needs a transport that moves data (FSNULL: FS_EINVAL).  A bad
+ * selector, size or elem_size is FS_EINVAL.
+ * fs_vortex_dump: writes ONE frame per file, truncating, to <dir>/{vort_x,vort_y,vort_z,vort_sq,q}.bin in the frame-dump
+ * layout (simulation.cpp:140-148), float32 whatever the handle's precision.  Synchronous; five passes.  On slab handles
+ * collective: every rank writes its planes at its offset, as fs_flow_stats_dump does.
+ *
+ * fs_isosurface: the triangle mesh of {value > level} of a source over the padded box, by the marching-cubes extractor of
+ * fs_obstacle_surface: the same cube cases, vertex ownership, orientation (normals point from inside to outside) and
+ * int-range check.  `source` is a field selector 0 .. FS_NFIELDS - 1, or FS_ISO_VORTEX | FS_VORTEX_* (the field is computed
+ * first).  The level is rounded to the handle's precision, L.  NaN counts as outside.  A vertex on the grid edge from point c
+ * towards +axis lies at (float)coord + (float)t, t = (L - v0) / (v1 - v0) computed in the handle's precision (finite and in
+ * [0, 1], because the end points straddle L).  The mesh is closed when no cell on the padded boundary is inside; for
+ * vortex sources with level >= 0 that always holds.  The handle keeps the result in a slot of its own: a later
+ * fs_obstacle_surface does not replace it, nor the reverse.  fs_isosurface(FS_OBS, 0.5) is fs_obstacle_surface's mesh, byte
+ * for byte.  Single-GPU handles only (slab handles: FS_EINVAL).
+ * fs_isosurface_fetch: copies the last result, as fs_obstacle_surface_fetch does.
+ */
+enum {
+    FS_VORTEX_WX = 0, FS_VORTEX_WY = 1, FS_VORTEX_WZ = 2, FS_VORTEX_W2 = 3, FS_VORTEX_Q = 4,
+    FS_VORTEX_NFIELDS = 5,
+    FS_ISO_VORTEX = 512    /* or-ed with an FS_VORTEX_* selector: a source of fs_isosurface */
+};
+int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size);
+int fs_vortex_dump(fs_sim* s, const char* dir);
+int fs_isosurface(fs_sim* s, int source, double level, long* n_vertices, long* n_triangles);
+int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles);
+
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 
 /* Size of the opaque RCCL unique id; rank 0 fills it with fs_comm_unique_id and the

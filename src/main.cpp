@@ -29,6 +29,9 @@
 //                  fields to DIR as one frame per file in the frame-dump layout (fs_flow_stats_dump: the viewers show it
 //                  unchanged); --mean-from S skips the first S steps, --mean-every N samples every Nth step after them,
 //                  --mean-moments (no value) also keeps the second moments and writes DIR/tke.bin
+//   --vortex DIR   at the end of the run, write the vorticity components, |omega|^2 and the Q-criterion of the final
+//                  velocities to DIR/{vort_x,vort_y,vort_z,vort_sq,q}.bin, one frame per file in the frame-dump layout
+//                  (fs_vortex_dump); may be combined with the logs and --mean-flow
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <chrono>
 #include <cmath>
@@ -167,7 +170,7 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir, forces_path, residuals_path, mean_dir;
+    std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir;
     bool mean_moments = false;
     std::vector<std::pair<std::string, std::string>> options;
 
@@ -190,13 +193,14 @@ int main(int argc, char** argv)
         if (key == "forces") { forces_path = val; return true; }
         if (key == "residuals") { residuals_path = val; return true; }
         if (key == "mean-flow") { mean_dir = val; return true; }
+        if (key == "vortex") { vortex_dir = val; return true; }
         if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
-                                        "mean-every" };
+                                        "mean-every", "vortex" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -250,6 +254,7 @@ int main(int argc, char** argv)
         if (fs_get_int(sim, "flow_stats_samples", &mean_samples)) return die("flow_stats_samples");
         if (fs_flow_stats_dump(sim, mean_dir.c_str())) return die("fs_flow_stats_dump");
     }
+    if (!vortex_dir.empty() && fs_vortex_dump(sim, vortex_dir.c_str())) return die("fs_vortex_dump");
     if (json)
         printf("{\"grid\": [%d, %d, %d], \"steps\": %d, \"acc\": %d, \"seconds\": %.6f, \"cells_steps_per_sec\": %.6g, "
                "\"mean_flow_samples\": %d}\n",

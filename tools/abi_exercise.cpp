@@ -228,6 +228,32 @@ int main(int argc, char** argv)
             CHECK(fs_set_option(s, "flow_stats", "off"));
             if (fs_flow_stats_sample(s) != FS_EINVAL) return 23;
         }
+        {   // vortex identification and iso-surfaces: every selector in both element sizes, the dump, the two result slots, the error cases
+            const size_t np = fs_padded_size(s);
+            std::vector<double> d(np);
+            std::vector<float> f4(np);
+            for (int which = 0; which < FS_VORTEX_NFIELDS; ++which) {
+                CHECK(fs_vortex_field(s, which, d.data(), np, 8));
+                CHECK(fs_vortex_field(s, which, f4.data(), np, 4));
+            }
+            if (fs_vortex_field(s, FS_VORTEX_NFIELDS, d.data(), np, 8) != FS_EINVAL) return 24;
+            if (fs_vortex_field(s, FS_VORTEX_Q, d.data(), np - 1, 8) != FS_EINVAL) return 25;
+            if (fs_vortex_field(s, FS_VORTEX_Q, d.data(), np, 2) != FS_EINVAL) return 26;
+            CHECK(fs_vortex_dump(s, dumpdir));
+            long nv = 0, nt = 0, ov = 0, ot = 0;
+            if (fs_isosurface_fetch(s, nullptr, nullptr) != FS_EINVAL) return 27;
+            CHECK(fs_isosurface(s, FS_ISO_VORTEX | FS_VORTEX_W2, 0.0, &nv, &nt));
+            CHECK(fs_obstacle_surface(s, &ov, &ot));
+            std::vector<float> verts(3 * (size_t)nv + 1);
+            std::vector<int> tris(3 * (size_t)nt + 1);
+            CHECK(fs_isosurface_fetch(s, verts.data(), tris.data()));
+            for (long i = 0; i < 3 * nt; ++i)
+                if (tris[(size_t)i] < 0 || tris[(size_t)i] >= nv) return 28;
+            CHECK(fs_isosurface(s, FS_OBS, 0.5, &nv, &nt));
+            if (nv != ov || nt != ot) return 29;
+            if (fs_isosurface(s, FS_ISO_VORTEX | 7, 0.0, &nv, &nt) != FS_EINVAL) return 30;
+            if (fs_isosurface(s, FS_NFIELDS, 0.0, &nv, &nt) != FS_EINVAL) return 31;
+        }
         CHECK(fs_set_option(s, "solver", "gs_lex"));
         CHECK(fs_run_one(s));
         CHECK(fs_destroy(s));
