@@ -32,6 +32,13 @@ VORTEX_WX, VORTEX_WY, VORTEX_WZ, VORTEX_W2, VORTEX_Q = range(5)
 VORTEX_NFIELDS = 5
 ISO_VORTEX = 512
 VORTEX_NAMES = ["vort_x", "vort_y", "vort_z", "vort_sq", "q"]
+# FS_SAMPLE_*: modes of fs_sample; SAMPLE_STAT or-ed with a STAT_* selector (and STAT_RAW) makes it a source of fs_sample
+SAMPLE_NEAREST, SAMPLE_LINEAR, SAMPLE_FLUID = range(3)
+SAMPLE_MODES = {"nearest": SAMPLE_NEAREST, "linear": SAMPLE_LINEAR, "fluid": SAMPLE_FLUID}
+SAMPLE_STAT = 1024
+PROBE_MAX = 4096        # FS_PROBE_MAX: probes fs_set_probes takes
+PROBE_VALUES = 5        # FS_PROBE_VALUES: dens, v_x, v_y, v_z, pressure per probe and record
+PROBE_NAMES = ["dens", "v_x", "v_y", "v_z", "pressure"]
 
 
 class FluidsimError(RuntimeError):
@@ -92,6 +99,11 @@ _SIGNATURES = {
     "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_isosurface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fs_sample_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
+    "fs_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]),
+    "fs_set_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
+    "fs_probe_sample": (C.c_int, [C.c_void_p]),
+    "fs_probe_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

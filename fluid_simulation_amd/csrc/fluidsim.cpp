@@ -19,6 +19,7 @@
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
+#include "sample.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -54,8 +55,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -105,6 +106,10 @@ struct EngineBase {
     virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int vortex_dump(const char* dir) = 0;
     virtual int isosurface(int source, double level) = 0;
+    virtual int sample_points(const double* xyz, long n) = 0;
+    virtual int sample(int source, int mode, double* out, long n) = 0;
+    virtual int probe_sample() = 0;
+    virtual int probe_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
 };
 
 struct fs_sim {
@@ -170,6 +175,9 @@ struct fs_sim {
     long flow_stats_gen = 0;     // bumped by every fs_set_option("flow_stats"): the accumulators are (re)allocated and cleared
     long flow_stats_every = 1, flow_stats_start = 0;   // fs_step samples when steps_total > start and (steps_total - start - 1) % every == 0
     long flow_stats_n = 0;       // samples taken since the last reset
+    std::vector<int> probes;     // fs_set_probes: x, y, z per probe, padded global coordinates
+    int probe_log = 0;           // "probe_log": records the probe log keeps, 0 = off
+    long probe_gen = 0;          // bumped by fs_set_probes and fs_set_option("probe_log"): list and ring are set up anew, the log is cleared
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -311,6 +319,17 @@ struct Engine : EngineBase {
     // vortex identification (vortex.h): the one field a call computes, in the fields' layout (LEAD-shifted like them); private,
     // allocated at the first call.  Only the kernel writes it, and only cells of interior rows: its ghosts stay +0.0.
     T* vort = nullptr;
+    // field sampling (sample.h): the point set of fs_sample_points and the values of the last fs_sample, on the device
+    double* samp_pts = nullptr;
+    double* samp_out = nullptr;
+    long samp_n = 0, samp_room = 0;     // points kept / points the two arrays have room for
+    // point probes (sample.h): the per-step log is a device ring of probe_cap records x probe_n probes x {q, u, v, w, p}
+    long* probe_idx = nullptr;          // each probe's cell index in this slab's arrays, -1 = a plane another rank owns
+    double* probe_ring = nullptr;
+    int probe_n = 0, probe_cap = 0;     // probe_cap > 0 only with probe_n > 0
+    long probe_gen = -1;                // S->probe_gen they were set up for
+    long probe_logged = 0;              // records taken since the ring was cleared or last drained
+    std::vector<long> probe_step;       // step number held by each ring slot
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -435,6 +454,10 @@ struct Engine : EngineBase {
         if (res_partial) hipFree(res_partial);
         for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
         if (vort) hipFree(vort - g.lead);
+        if (samp_pts) hipFree(samp_pts);
+        if (samp_out) hipFree(samp_out);
+        if (probe_idx) hipFree(probe_idx);
+        if (probe_ring) hipFree(probe_ring);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1348,6 +1371,7 @@ struct Engine : EngineBase {
         if ((rc = ensure_force_ring())) return rc;
         if ((rc = ensure_residual_ring())) return rc;
         if ((rc = flow_stats_config())) return rc;
+        if ((rc = ensure_probe_ring())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1426,6 +1450,8 @@ struct Engine : EngineBase {
         if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
             (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
             return rc;
+        // "probe_log": the same state is a record of the probes (one launch, no host synchronisation, the step's own stream)
+        if (probe_cap > 0) probe_record();
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -2040,6 +2066,172 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- field sampling and point probes (sample.h; beyond the reference) -------------------------------
+    int sample_points(const double* xyz, long n) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample_points: fields are sampled on a single-GPU handle");
+        if (n > samp_room) {
+            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued sample may still use what is freed here
+            if (samp_pts) hipFree(samp_pts);
+            if (samp_out) hipFree(samp_out);
+            samp_pts = samp_out = nullptr;
+            samp_n = samp_room = 0;
+            hipError_t e = hipMalloc((void**)&samp_pts, (size_t)n * 3 * sizeof(double));
+            if (e == hipSuccess && (e = hipMalloc((void**)&samp_out, (size_t)n * sizeof(double))) != hipSuccess) {
+                hipFree(samp_pts);
+                samp_pts = nullptr;
+            }
+            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_sample_points: %ld points: %s", n, hipGetErrorString(e));
+            samp_room = n;
+        }
+        samp_n = n;
+        if (n > 0) {
+            HIP_TRY(hipMemcpyAsync(samp_pts, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
+            HIP_TRY(hipStreamSynchronize(S->stream));    // `xyz` may be freed by the caller
+        }
+        return FS_OK;
+    }
+
+    int sample(int source, int mode, double* out, long n) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
+        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "fs_sample: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", mode);
+        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
+        const T* field = nullptr;
+        const double* stat = nullptr;
+        int rc;
+        if (source >= 0 && source < FS_NFIELDS) {
+            field = arr[slot[source]];
+        } else if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS) {
+            if ((rc = vortex_compute("fs_sample", source & (FS_ISO_VORTEX - 1)))) return rc;
+            field = vort;
+        } else if ((source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
+            // the derived field goes into the staging buffer in the accumulators' layout, which is the fields' pitched one
+            const int sel = source & (FS_SAMPLE_STAT - 1);
+            if ((rc = flow_stats_config())) return rc;
+            if ((rc = flow_stats_check("fs_sample", sel))) return rc;
+            if ((rc = need_dense(stat_bytes()))) return rc;
+            if (S->flow_stats_n == 0)                    // a raw sum before the first sample: +0.0
+                HIP_TRY(hipMemsetAsync(dense, 0, stat_bytes(), S->stream));
+            else
+                fs::launch_flow_stats_finalize(S->stream, g, stat_acc, sel & ~FS_STAT_RAW, (sel & FS_STAT_RAW) != 0, S->flow_stats_n,
+                                               false, false, (double*)dense);
+            stat = (const double*)dense + fs::LEAD;
+        } else {
+            return fail(FS_EINVAL, "fs_sample: unknown source %d (a field selector, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", source);
+        }
+        if (n == 0) return FS_OK;
+        if (!out) return fail(FS_EINVAL, "fs_sample: null output");
+        const T* obs = arr[slot[FS_OBS]];
+        {
+            ScopedSpan sp(S, FAM_MISC);
+            if (stat) fs::launch_sample<double, T>(S->stream, g, mode, n, samp_pts, stat, obs, samp_out);
+            else fs::launch_sample<T, T>(S->stream, g, mode, n, samp_pts, field, obs, samp_out);
+        }
+        HIP_TRY(hipMemcpyAsync(out, samp_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    double* probe_slot(long k) const { return probe_ring + (size_t)k * (size_t)probe_n * fs::PROBE_VALUES; }
+
+    // set up the probe list and (re)allocate and clear the ring after fs_set_probes / fs_set_option("probe_log")
+    int ensure_probe_ring()
+    {
+        if (probe_gen == S->probe_gen) return FS_OK;
+        if (probe_idx || probe_ring) HIP_TRY(hipStreamSynchronize(S->stream));   // a queued record may still use what is freed here
+        if (probe_idx) HIP_TRY(hipFree(probe_idx));
+        if (probe_ring) HIP_TRY(hipFree(probe_ring));
+        probe_idx = nullptr;
+        probe_ring = nullptr;
+        probe_n = probe_cap = 0;
+        probe_logged = 0;
+        probe_step.clear();
+        probe_gen = S->probe_gen;
+        const int n = (int)(S->probes.size() / 3);
+        if (n == 0 || S->probe_log <= 0) return FS_OK;
+        // the owner of a probe is the rank that owns its global plane (z = 0: the first, z = D + 1: the last)
+        std::vector<long> idx((size_t)n);
+        for (int k = 0; k < n; ++k) {
+            const int x = S->probes[3 * (size_t)k], y = S->probes[3 * (size_t)k + 1], z = S->probes[3 * (size_t)k + 2];
+            const int zl = z - sc.zoff;
+            const bool mine = (zl >= 1 && zl <= g.D) || (z == 0 && sc.lo_wall) || (z == sc.Dglobal + 1 && sc.hi_wall);
+            idx[(size_t)k] = mine ? (long)x + (long)y * g.sy + (long)zl * g.sz : -1;
+        }
+        const size_t bytes = (size_t)S->probe_log * (size_t)n * fs::PROBE_VALUES * sizeof(double);
+        HIP_TRY(hipMalloc((void**)&probe_idx, idx.size() * sizeof(long)));
+        HIP_TRY(hipMalloc((void**)&probe_ring, bytes));
+        HIP_TRY(hipMemcpyAsync(probe_idx, idx.data(), idx.size() * sizeof(long), hipMemcpyHostToDevice, S->stream));
+        HIP_TRY(hipMemsetAsync(probe_ring, 0, bytes, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));        // `idx` goes out of scope
+        probe_n = n;
+        probe_cap = S->probe_log;
+        probe_step.assign((size_t)probe_cap, 0);
+        return FS_OK;
+    }
+
+    // one record of the state as it is now into the next ring slot
+    void probe_record()
+    {
+        {
+            ScopedSpan sp(S, FAM_PROBES);
+            fs::launch_probe_record<T>(S->stream, probe_n, probe_idx, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]],
+                                       arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], probe_slot(probe_logged % probe_cap));
+        }
+        probe_step[(size_t)(probe_logged++ % probe_cap)] = S->steps_total;
+    }
+
+    int probe_sample() override
+    {
+        int rc = ensure_probe_ring();
+        if (rc) return rc;
+        if (probe_cap == 0) return fail(FS_EINVAL, "fs_probe_sample: no probes are set (fs_set_probes), or option \"probe_log\" is 0");
+        probe_record();
+        return FS_OK;
+    }
+
+    int probe_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        int rc = ensure_probe_ring();
+        if (rc) return rc;
+        const long n = probe_cap > 0 ? std::min<long>(probe_logged, probe_cap) : 0;
+        if (n_rows) *n_rows = n;
+        if (n_dropped) *n_dropped = probe_logged - n;
+        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
+        if (max_rows < n) return fail(FS_EINVAL, "fs_probe_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "probe records need the other slabs' planes; the FSNULL transport carries none");
+        const size_t per = (size_t)probe_n * fs::PROBE_VALUES;   // one record
+        const long first = probe_logged - n;
+        std::vector<double> mine((size_t)n * per), all;
+        if (n > 0) {                                     // the retained records are one run of ring slots, or two where it wraps
+            const long start = first % probe_cap, run = std::min<long>(n, probe_cap - start);
+            HIP_TRY(hipMemcpyAsync(mine.data(), probe_slot(start), (size_t)run * per * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+            if (run < n)
+                HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)run * per, probe_slot(0), (size_t)(n - run) * per * sizeof(double),
+                                       hipMemcpyDeviceToHost, S->stream));
+            HIP_TRY(hipStreamSynchronize(S->stream));
+        }
+        if ((rc = gather_plane_records(mine, all, "probe records"))) return rc;
+        const size_t blob = mine.size();
+        const int nr = S->comm.active() ? S->comm.nranks : 1, ld = S->D / nr;
+        std::vector<size_t> owner_off((size_t)probe_n);  // only the owner's value is used
+        for (int k = 0; k < probe_n; ++k) {
+            const int z = S->probes[3 * (size_t)k + 2];
+            const int r = z <= 0 ? 0 : z > S->D ? nr - 1 : (z - 1) / ld;
+            owner_off[(size_t)k] = (size_t)r * blob + (size_t)k * fs::PROBE_VALUES;
+        }
+        const size_t cols = 1 + per;
+        for (long i = 0; i < n; ++i) {
+            double* o = rows + (size_t)i * cols;
+            o[0] = (double)probe_step[(size_t)((first + i) % probe_cap)];
+            for (int k = 0; k < probe_n; ++k)
+                for (int j = 0; j < fs::PROBE_VALUES; ++j)
+                    o[1 + (size_t)k * fs::PROBE_VALUES + j] = all[owner_off[(size_t)k] + (size_t)i * per + j];
+        }
+        probe_logged = 0;                                // drained
+        return FS_OK;
+    }
+
     // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
     // ring slot k, projection j: g.D plane records
     double* force_slot(long k, int j) const { return force_ring + ((size_t)k * 2 + (size_t)j) * plane_doubles(); }
@@ -2418,6 +2610,14 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "residual_log: steps kept, 0 (off) .. 1048576");
         s->residual_log = (int)n;
         s->residual_log_gen++;
+    } else if (k == "probe_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "probe_log: records kept, 0 (off) .. 1048576");
+        if ((size_t)n * (s->probes.size() / 3) * FS_PROBE_VALUES * sizeof(double) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "probe_log: %ld records of %zu probes exceed 1 GiB", n, s->probes.size() / 3);
+        s->probe_log = (int)n;
+        s->probe_gen++;
     } else if (k == "flow_stats") {
         if (v == "off") s->flow_stats = 0;
         else if (v == "mean") s->flow_stats = fs::ST_NMEAN;
@@ -2542,6 +2742,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "reach_wait_us") *out = (int)(s->reach_wait_ms * 1e3);  // host time spent blocked in them
     else if (n == "reach_hidden") *out = (int)s->n_reach_hidden;          // advections queued while the device still had the work placed before them ...
     else if (n == "reach_exposed") *out = (int)s->n_reach_exposed;        // ... and after it had run dry (a bubble on the device)
+    else if (n == "probe_count") *out = (int)(s->probes.size() / 3);      // probes set by fs_set_probes
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -2907,6 +3108,41 @@ int fs_vortex_dump(fs_sim* s, const char* dir)
     ENGINE_OR_RETURN(s);
     if (!dir) return fail(FS_EINVAL, "null directory");
     return s->eng->vortex_dump(dir);
+}
+
+int fs_sample_points(fs_sim* s, const double* xyz, long n)
+{
+    ENGINE_OR_RETURN(s);
+    if (n < 0 || n > (1L << 24)) return fail(FS_EINVAL, "fs_sample_points: 0 .. 16777216 points, got %ld", n);
+    if (n > 0 && !xyz) return fail(FS_EINVAL, "fs_sample_points: null points");
+    return s->eng->sample_points(xyz, n);
+}
+int fs_sample(fs_sim* s, int source, int mode, double* out, long n)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->sample(source, mode, out, n);
+}
+int fs_set_probes(fs_sim* s, const int* cells_xyz, long n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (n < 0 || n > FS_PROBE_MAX) return fail(FS_EINVAL, "fs_set_probes: 0 .. %d probes, got %ld", FS_PROBE_MAX, n);
+    if (n > 0 && !cells_xyz) return fail(FS_EINVAL, "fs_set_probes: null cells");
+    for (long k = 0; k < n; ++k) {
+        const int x = cells_xyz[3 * k], y = cells_xyz[3 * k + 1], z = cells_xyz[3 * k + 2];
+        if (x < 0 || x > s->W + 1 || y < 0 || y > s->H + 1 || z < 0 || z > s->D + 1)
+            return fail(FS_EINVAL, "fs_set_probes: cell %ld (%d,%d,%d) outside 0..%dx0..%dx0..%d", k, x, y, z, s->W + 1, s->H + 1, s->D + 1);
+    }
+    if ((size_t)s->probe_log * (size_t)n * FS_PROBE_VALUES * sizeof(double) > ((size_t)1 << 30))
+        return fail(FS_EINVAL, "fs_set_probes: %d records (\"probe_log\") of %ld probes exceed 1 GiB", s->probe_log, n);
+    s->probes.assign(cells_xyz, cells_xyz + 3 * n);
+    s->probe_gen++;
+    return FS_OK;
+}
+int fs_probe_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->probe_sample(); }
+int fs_probe_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->probe_log_fetch(rows, max_rows, n_rows, n_dropped);
 }
 
 int fs_comm_unique_id(void* id_out)

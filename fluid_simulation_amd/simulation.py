@@ -364,6 +364,49 @@ class Simulation:
         check(self._L.fs_isosurface_fetch(self._h, verts.ctypes.data, faces.ctypes.data))
         return verts, faces
 
+    def sample_points(self, points):
+        """Keeps the points at which sample() evaluates (fs_sample_points; single-GPU handles): `points` is (n, 3), x, y, z
+        in the viewer's padded index space, a cell's value sitting at its integer coordinates.  Replaces the earlier set."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        check(self._L.fs_sample_points(self._h, p.ctypes.data_as(C.c_void_p), p.shape[0]))
+        self._sample_n = p.shape[0]
+
+    def sample(self, source, mode="linear"):
+        """The value of `source` at the kept points (fs_sample), (n,) float64; NaN outside the padded box.  `source` is a
+        field selector (DENS .. BUFFER), ISO_VORTEX | VORTEX_*, or SAMPLE_STAT | STAT_* (| STAT_RAW); `mode` is "nearest"
+        (the stored value of the nearest cell), "linear" (the reference's trilinear form) or "fluid" (the weighted mean of
+        the corners that are not solid: the mode for points on an obstacle's surface), or a SAMPLE_* constant."""
+        m = _lib.SAMPLE_MODES[mode] if isinstance(mode, str) else int(mode)
+        n = getattr(self, "_sample_n", 0)
+        out = np.empty(n, dtype=np.float64)
+        check(self._L.fs_sample(self._h, int(source), m, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def set_probes(self, cells):
+        """Sets the probe cells of the per-step probe log (fs_set_probes): `cells` is (n, 3) integers x, y, z in padded
+        global coordinates (ghost cells allowed), n up to PROBE_MAX; an empty list turns the probes off.  Clears the log."""
+        c = np.ascontiguousarray(cells, dtype=np.intc).reshape(-1, 3)
+        check(self._L.fs_set_probes(self._h, c.ctypes.data_as(C.c_void_p), c.shape[0]))
+
+    probe_count = property(lambda s: s._geti("probe_count"))
+
+    def probe_sample(self):
+        """Takes one record of the probes from the state as it is now (fs_step does so by itself with probe_log=N)."""
+        check(self._L.fs_probe_sample(self._h))
+
+    def probe_log(self, with_dropped=False):
+        """Drains the per-step probe log (option probe_log=N; fs_probe_log, collective on z-slabs): {"step": (R,) int64,
+        "values": (R, n, 5) float64 -- dens, v_x, v_y, v_z, pressure of each probe}, oldest record first.
+        with_dropped=True returns (that, number of records the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        count = self.probe_count
+        cols = 1 + _lib.PROBE_VALUES * count
+        check(self._L.fs_probe_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        raw = np.zeros((n.value, cols), dtype=np.float64)
+        check(self._L.fs_probe_log(self._h, raw.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(dropped)))
+        log = {"step": raw[:, 0].astype(np.int64), "values": raw[:, 1:].reshape(n.value, count, _lib.PROBE_VALUES).copy()}
+        return (log, dropped.value) if with_dropped else log
+
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()
         check(self._L.fs_time_sweeps(self._h, b, field, prev, a, c, reps, C.byref(ms)))

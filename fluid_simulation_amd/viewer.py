@@ -69,3 +69,28 @@ def generate_isosurface_mesh(sim, source, level):
     ISO_VORTEX | VORTEX_Q at a positive level: the vortex cores).  The mesh never leaves the device's index space:
     padded (x, y, z) coordinates, as the obstacle mesh."""
     return _mesh_dict(*sim.isosurface(source, level))
+
+
+def rake(p0, p1, n):
+    """`n` points on the segment from p0 to p1, end points included, as an (n, 3) float64 array for
+    `Simulation.sample_points`: a wake rake, or one row of a cut plane."""
+    p0 = np.asarray(p0, dtype=np.float64).reshape(3)
+    p1 = np.asarray(p1, dtype=np.float64).reshape(3)
+    t = np.linspace(0.0, 1.0, int(n)).reshape(-1, 1) if int(n) > 1 else np.zeros((int(n), 1))
+    return p0 + t * (p1 - p0)
+
+
+def surface_pressure(sim, source=_lib.PRESSURE, p_ref=0.0):
+    """The pressure distribution on the body of a live `Simulation`: the obstacle mesh (generate_obstacle_mesh's
+    dictionary) plus 'p', `source` at every vertex in mode "fluid" -- a vertex sits on the edge between a solid and a
+    fluid cell, and the solid cell holds 0 -- and 'cp' = 2 (p - p_ref) / (dt * speed^2), the scaling of the force
+    coefficients (include/fluidsim.h, "pressure force on the obstacles").  Replaces the handle's sample points."""
+    verts, faces = sim.obstacle_surface()
+    mesh = _mesh_dict(verts, faces)
+    sim.sample_points(verts.astype(np.float64))
+    p = sim.sample(source, "fluid")
+    denom = float(sim.dt) * (float(sim.speed) * float(sim.speed))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mesh["p"] = p
+        mesh["cp"] = 2.0 * (p - float(p_ref)) / denom
+    return mesh

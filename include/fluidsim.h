@@ -111,6 +111,9 @@ int fs_destroy(fs_sim* s);
  *                 it.  Setting it (re)allocates and clears the log.  May be changed at any time.
  *   "flow_stats"  "off" (default) | "mean" | "moments", "flow_stats_every" N >= 1, "flow_stats_start" S >= 0: time-averaged
  *                 flow statistics on the device, see fs_flow_stats_field below.  May be changed at any time.
+ *   "probe_log"   N >= 0 (at most 1048576): keep the last N records of the point probes (fs_set_probes, fs_probe_log); 0 (default) =
+ *                 off, and the step launches and allocates nothing for it.  Setting it (re)allocates and clears the log.  May be
+ *                 changed at any time.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -146,7 +149,7 @@ int fs_destroy(fs_sim* s);
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
  * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
- * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples".
+ * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count".
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -216,7 +219,7 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records) "residual" (fs_solve_residual / fs_diffuse_residual and the
  * "residual_log" records: one launch counted per record, i.e. per solve and point in time -- 12 per step with the log on,
  * 10 where the dead density solve is elided, 0 with it off) "flow_stats" (one launch per sample of the time-averaged flow
- * statistics, 0 with the feature off).  Events are recorded on the handle's own stream. */
+ * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -435,6 +438,60 @@ int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_si
 int fs_vortex_dump(fs_sim* s, const char* dir);
 int fs_isosurface(fs_sim* s, int source, double level, long* n_vertices, long* n_triangles);
 int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles);
+
+/* ---- point probes and field sampling (beyond the reference: it evaluates a field off the grid only inside advect) ----
+ *
+ * COORDINATES are the viewer's, as for fs_streamlines and fs_obstacle_surface: indices into the padded array, x first.  A cell's
+ * value sits at its integer coordinates; the box is [0, w+1] x [0, h+1] x [0, d+1].
+ * THE VALUE AT A POINT (x, y, z), in fp64; every written operation is rounded once, in exactly this order, without contraction
+ * (the library is built with -ffp-contract=off):
+ *     NaN (all modes) if a coordinate is NaN, below 0, or above w+1 / h+1 / d+1;
+ *     i0 = min(floor(x), w), sx = x - i0 (exact), tx = 1.0 - sx; likewise j0, sy, ty with h and l0, sz, tz with d;
+ *     v_abc = the stored value at (i0+a, j0+b, l0+c), widened to double.
+ * FS_SAMPLE_NEAREST: v_abc with a = (sx >= 0.5), b = (sy >= 0.5), c = (sz >= 0.5): the exact stored value.
+ * FS_SAMPLE_LINEAR: the reference's lerp form (simulation.cpp:412-420), x, then y, then z:
+ *     c_bc = v_0bc*tx + v_1bc*sx        d_c = c_0c*ty + c_1c*sy        r = d_0*tz + d_1*sz
+ * Every corner is multiplied: a NaN or infinite corner gives NaN even where its weight is 0.
+ * FS_SAMPLE_FLUID: w_abc = ((a ? sx : tx) * (b ? sy : ty)) * (c ? sz : tz); a corner COUNTS when w_abc > 0 and obs(corner) != 1
+ * (FS_OBS as it is now); num = sum of w*v and den = sum of w over the counting corners in memory order (c outer, b, a inner),
+ * both starting from +0.0; r = num / den, or NaN if no corner counts.  The mode for points on an obstacle's surface, where solid
+ * cells hold p = 0 and carry half of the trilinear weight: at the midpoint of an edge between a solid and a fluid cell it returns
+ * exactly the fluid cell's value (0.5 v / 0.5).
+ * SOURCES: a field selector 0 .. FS_NFIELDS - 1; FS_ISO_VORTEX | FS_VORTEX_* (the field is computed first, exactly as
+ * fs_isosurface does); FS_SAMPLE_STAT | sel, sel with the selectors, FS_STAT_RAW and the errors of fs_flow_stats_field (the fp64
+ * derived field is sampled as it is, not rounded to the handle's precision).  The output is always fp64.
+ *
+ * fs_sample_points: keeps n points (xyz[3 * k + ..] = x, y, z) on the device until they are replaced; n = 0 .. 2^24, else FS_EINVAL.
+ * fs_sample: evaluates the source at the kept points into out[n]; n must equal the kept count.  One HIP kernel, one thread per
+ * point; it changes no field.  Both are for single-GPU handles only (slab handles: FS_EINVAL).
+ *
+ * PROBES are cells, not points, so that ownership and bits are unambiguous.  fs_set_probes sets the probe list to n cells
+ * (cells_xyz[3 * k + ..] = x, y, z), n = 0 (off) .. FS_PROBE_MAX, in integer padded global coordinates -- the numbers the
+ * mutators use, ghost cells 0 and N+1 allowed, anything else FS_EINVAL; it replaces the list and clears the log.  Option
+ * "probe_log" = N (0 .. 1048576) keeps the last N records; setting it (re)allocates and clears the ring.  Either is legal at any
+ * time, and either is FS_EINVAL if N * n * 40 bytes would exceed 1 GiB.  With no probes or N = 0 a step launches and allocates
+ * nothing for it.
+ * A RECORD holds, per probe, {q, u, v, w, p} = dens, v_x, v_y, v_z, FS_PRESSURE: the stored values widened to fp64, exact.
+ * fs_step takes one at the sample point of the flow statistics above -- after advect(0, dens, buffer) (simulation.cpp:136),
+ * before the frame dump, p as the second projection left it -- by one launch on the step's own stream into a device ring,
+ * without a host synchronisation.  fs_probe_sample takes one record of the state as it is now.
+ * fs_probe_log drains the log: rows[(1 + FS_PROBE_VALUES * n) * i + ...] = {step, then q, u, v, w, p of each probe in list
+ * order}.  step, oldest-first order, rows = NULL, max_rows and *n_dropped are as for fs_force_log.  fs_get_int "probe_count"
+ * reports n; timing family "probes" counts one launch per record, 0 with the feature off.
+ * On z-slab handles the owner of a probe is the rank that owns its global plane (z = 0: rank 0; z = d+1: the last rank) and
+ * only the owner's value is used; every rank makes the same calls, the drain is collective and every rank receives the same
+ * rows (FSNULL transport: FS_EINVAL).  A record is the stored value itself: a slab run gives the single-GPU bits, and launch
+ * shape cannot matter.
+ */
+enum { FS_SAMPLE_NEAREST = 0, FS_SAMPLE_LINEAR = 1, FS_SAMPLE_FLUID = 2 };
+#define FS_SAMPLE_STAT 1024   /* or-ed with an FS_STAT_* selector (and FS_STAT_RAW): a source of fs_sample */
+#define FS_PROBE_MAX 4096
+#define FS_PROBE_VALUES 5
+int fs_sample_points(fs_sim* s, const double* xyz, long n);
+int fs_sample(fs_sim* s, int source, int mode, double* out, long n);
+int fs_set_probes(fs_sim* s, const int* cells_xyz, long n);
+int fs_probe_sample(fs_sim* s);
+int fs_probe_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

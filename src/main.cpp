@@ -32,6 +32,10 @@
 //   --vortex DIR   at the end of the run, write the vorticity components, |omega|^2 and the Q-criterion of the final
 //                  velocities to DIR/{vort_x,vort_y,vort_z,vort_sq,q}.bin, one frame per file in the frame-dump layout
 //                  (fs_vortex_dump); may be combined with the logs and --mean-flow
+//   --probes FILE  point probes: a text file with one cell `x y z` per line in padded global coordinates (the numbers the
+//                  mutators use; ghost cells 0 and N+1 allowed), `#` starts a comment; --probe-log FILE records dens, v_x,
+//                  v_y, v_z and the pressure at every probe after every step (option "probe_log" = steps) and writes them
+//                  to FILE as CSV: step,q_0,u_0,v_0,w_0,p_0,q_1,... with the values as %.17g (they read back exactly)
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <chrono>
 #include <cmath>
@@ -153,6 +157,55 @@ int write_residuals(fs_sim* sim, const char* path)
     return ok ? 0 : 1;
 }
 
+// the probe cells of --probes: `x y z` per line, `#` comments
+int read_probes(const char* path, std::vector<int>& cells)
+{
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot open %s\n", path); return 1; }
+    char line[512];
+    int lineno = 0;
+    bool ok = true;
+    while (ok && fgets(line, sizeof line, fp)) {
+        ++lineno;
+        if (char* hash = strchr(line, '#')) *hash = 0;
+        int x, y, z, used = 0;
+        const int got = sscanf(line, "%d %d %d %n", &x, &y, &z, &used);
+        if (got == EOF || (got <= 0 && strspn(line, " \t\r\n") == strlen(line))) continue;   // blank or comment
+        if (got != 3 || line[used] != 0) {
+            fprintf(stderr, "simulation.out: %s:%d: expected `x y z`\n", path, lineno);
+            ok = false;
+        } else {
+            cells.push_back(x); cells.push_back(y); cells.push_back(z);
+        }
+    }
+    fclose(fp);
+    return ok ? 0 : 1;
+}
+
+// the per-step probe log of the run -> CSV (the rows of fs_probe_log)
+int write_probes(fs_sim* sim, const char* path, long nprobes)
+{
+    long n = 0, dropped = 0;
+    if (fs_probe_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    const size_t cols = 1 + (size_t)FS_PROBE_VALUES * (size_t)nprobes;
+    std::vector<double> rows((size_t)n * cols + 1);
+    if (fs_probe_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step");
+    for (long k = 0; k < nprobes; ++k) fprintf(fp, ",q_%ld,u_%ld,v_%ld,w_%ld,p_%ld", k, k, k, k, k);
+    fprintf(fp, "\n");
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * cols];
+        fprintf(fp, "%ld", (long)r[0]);
+        for (size_t k = 1; k < cols; ++k) fprintf(fp, ",%.17g", r[k]);
+        fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "simulation.out: %s: %s\n", what, fs_last_error());
@@ -170,7 +223,7 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir;
+    std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir, probes_path, probe_log_path;
     bool mean_moments = false;
     std::vector<std::pair<std::string, std::string>> options;
 
@@ -194,13 +247,15 @@ int main(int argc, char** argv)
         if (key == "residuals") { residuals_path = val; return true; }
         if (key == "mean-flow") { mean_dir = val; return true; }
         if (key == "vortex") { vortex_dir = val; return true; }
+        if (key == "probes") { probes_path = val; return true; }
+        if (key == "probe-log") { probe_log_path = val; return true; }
         if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
-                                        "mean-every", "vortex" };
+                                        "mean-every", "vortex", "probes", "probe-log" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -231,6 +286,12 @@ int main(int argc, char** argv)
     if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
     if (!residuals_path.empty()) options.push_back({ "residual_log", std::to_string(iter) });
     if (!mean_dir.empty()) options.push_back({ "flow_stats", mean_moments ? "moments" : "mean" });
+    std::vector<int> probe_cells;
+    if (!probes_path.empty()) {
+        if (read_probes(probes_path.c_str(), probe_cells)) return 2;
+        if (fs_set_probes(sim, probe_cells.data(), (long)(probe_cells.size() / 3))) return die("fs_set_probes");
+    }
+    if (!probe_log_path.empty()) options.push_back({ "probe_log", std::to_string(iter) });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
     for (const Stl& s : stls) {
@@ -249,6 +310,7 @@ int main(int argc, char** argv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
+    if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     int mean_samples = 0;
     if (!mean_dir.empty()) {
         if (fs_get_int(sim, "flow_stats_samples", &mean_samples)) return die("flow_stats_samples");

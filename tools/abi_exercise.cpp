@@ -28,6 +28,13 @@ static int slab_rank(int rank, const char* id, const char* ascii, const char* du
     snprintf(idbuf, sizeof idbuf, "%s", id);
     CHECK(fs_comm_init(s, rank, 2, idbuf));
     CHECK(fs_set_option(s, "residual_log", "2"));
+    {   // point probes on both sides of the slab boundary and in both z ghost planes; the sampler is single-GPU only
+        const int cells[] = { 5, 5, 16, 5, 5, 17, 0, 0, 0, 33, 17, 33, 9, 7, 1 };
+        CHECK(fs_set_probes(s, cells, 5));
+        CHECK(fs_set_option(s, "probe_log", "3"));
+        const double pt[3] = { 1.0, 1.0, 1.0 };
+        if (fs_sample_points(s, pt, 1) != FS_EINVAL || fs_sample(s, FS_DENS, FS_SAMPLE_LINEAR, nullptr, 0) != FS_EINVAL) return 13;
+    }
     long added = 0;
     CHECK(fs_load_stl(s, ascii, 0.6f, 0.f, 0.f, 0.f, 5.f, 0.f, 0.f, &added));
     CHECK(fs_add_obstacle(s, 9, 7, 16));
@@ -58,6 +65,16 @@ static int slab_rank(int rank, const char* id, const char* ascii, const char* du
         double out[FS_RESIDUAL_COLS];
         CHECK(fs_solve_residual(s, 0, FS_PRESSURE, FS_DIVERGENCE, 1.0, 6.0, out, planes.data()));
         if (nr != 2 || !(out[3] > 0.0)) { fprintf(stderr, "rank %d: %ld residual rows, %g cells\n", rank, nr, out[3]); return 12; }
+    }
+    {   // the probe log of the slab steps: a record on demand, then the collective drain (the ring of 3 wrapped)
+        CHECK(fs_probe_sample(s));
+        long nr = 0, nd = 0;
+        CHECK(fs_probe_log(s, nullptr, 0, &nr, &nd));
+        const size_t cols = 1 + 5 * (size_t)FS_PROBE_VALUES;
+        std::vector<double> rows((size_t)nr * cols + 1);
+        if (nr != 3 || nd != 3 || fs_probe_log(s, rows.data(), 2, &nr, &nd) != FS_EINVAL) { fprintf(stderr, "rank %d: %ld probe rows, %ld dropped\n", rank, nr, nd); return 14; }
+        CHECK(fs_probe_log(s, rows.data(), nr, &nr, &nd));
+        if (rows[2 * cols] != 5.0 || !(rows[2 * cols + 2] == rows[2 * cols + 2])) return 15;   // five steps completed; a number
     }
     CHECK(fs_sync(s));
     CHECK(fs_destroy(s));
@@ -253,6 +270,63 @@ int main(int argc, char** argv)
             if (nv != ov || nt != ot) return 29;
             if (fs_isosurface(s, FS_ISO_VORTEX | 7, 0.0, &nv, &nt) != FS_EINVAL) return 30;
             if (fs_isosurface(s, FS_NFIELDS, 0.0, &nv, &nt) != FS_EINVAL) return 31;
+        }
+        {   // field sampling: every kind of source in every mode at the mesh's vertices and a few odd points, the error cases
+            long nv = 0, nt = 0;
+            CHECK(fs_obstacle_surface(s, &nv, &nt));
+            std::vector<float> verts(3 * (size_t)nv + 1);
+            CHECK(fs_obstacle_surface_fetch(s, verts.data(), nullptr));
+            std::vector<double> pts(verts.begin(), verts.begin() + 3 * nv);
+            const double odd[] = { 0.0, 0.0, 0.0, 41.0, 25.0, 21.0, 41.5, 1.0, 1.0, -0.5, 1.0, 1.0, 1.0, 0.0 / 0.0, 1.0, 7.25, 3.5, 20.75 };
+            pts.insert(pts.end(), odd, odd + 18);
+            const long np = (long)(pts.size() / 3);
+            std::vector<double> out((size_t)np);
+            if (fs_sample(s, FS_PRESSURE, FS_SAMPLE_LINEAR, out.data(), np) != FS_EINVAL) return 32;     // no points kept yet
+            CHECK(fs_sample_points(s, pts.data(), np));
+            CHECK(fs_set_option(s, "flow_stats", "moments"));
+            CHECK(fs_run_one(s));
+            const int sources[] = { FS_PRESSURE, FS_OBS, FS_VX_PREV, FS_ISO_VORTEX | FS_VORTEX_Q, FS_SAMPLE_STAT | FS_STAT_MEAN_P,
+                                    FS_SAMPLE_STAT | FS_STAT_RAW | FS_STAT_UV, FS_SAMPLE_STAT | FS_STAT_TKE };
+            for (int src : sources)
+                for (int mode = FS_SAMPLE_NEAREST; mode <= FS_SAMPLE_FLUID; ++mode) {
+                    CHECK(fs_sample(s, src, mode, out.data(), np));
+                    if (out[(size_t)np - 3] == out[(size_t)np - 3] || out[(size_t)np - 2] == out[(size_t)np - 2]) return 33;   // outside the box: NaN
+                }
+            if (fs_sample(s, FS_NFIELDS, FS_SAMPLE_LINEAR, out.data(), np) != FS_EINVAL) return 34;
+            if (fs_sample(s, FS_PRESSURE, 3, out.data(), np) != FS_EINVAL) return 35;
+            if (fs_sample(s, FS_PRESSURE, FS_SAMPLE_FLUID, out.data(), np - 1) != FS_EINVAL) return 36;
+            if (fs_sample_points(s, pts.data(), (1L << 24) + 1) != FS_EINVAL) return 37;
+            CHECK(fs_set_option(s, "flow_stats", "off"));
+            if (fs_sample(s, FS_SAMPLE_STAT | FS_STAT_MEAN_P, FS_SAMPLE_LINEAR, out.data(), np) != FS_EINVAL) return 38;
+            CHECK(fs_sample_points(s, pts.data(), 2));          // a smaller set replaces it
+            CHECK(fs_sample(s, FS_DENS, FS_SAMPLE_NEAREST, out.data(), 2));
+            CHECK(fs_sample_points(s, nullptr, 0));
+        }
+        {   // point probes: the list, the ring through a wrap, a record on demand, the drain, the limits, off again
+            const int cells[] = { 0, 0, 0, 41, 25, 21, 3, 3, 3, 20, 12, 10 };
+            const int bad[] = { 42, 1, 1 };
+            if (fs_probe_sample(s) != FS_EINVAL) return 39;
+            if (fs_set_probes(s, bad, 1) != FS_EINVAL || fs_set_probes(s, cells, FS_PROBE_MAX + 1) != FS_EINVAL) return 40;
+            CHECK(fs_set_probes(s, cells, 4));
+            CHECK(fs_set_option(s, "probe_log", "2"));
+            for (int k = 0; k < 3; ++k) CHECK(fs_run_one(s));
+            CHECK(fs_probe_sample(s));
+            long nr = 0, nd = 0;
+            int count = 0;
+            CHECK(fs_get_int(s, "probe_count", &count));
+            CHECK(fs_probe_log(s, nullptr, 0, &nr, &nd));
+            if (count != 4 || nr != 2 || nd != 2) return 41;
+            const size_t cols = 1 + 4 * (size_t)FS_PROBE_VALUES;
+            std::vector<double> rows((size_t)nr * cols);
+            if (fs_probe_log(s, rows.data(), 1, &nr, &nd) != FS_EINVAL) return 42;
+            CHECK(fs_probe_log(s, rows.data(), nr, &nr, &nd));
+            if (rows[0] != rows[cols] || rows[1] != rows[cols + 1]) return 43;     // the last step's record and the one on demand
+            if (fs_set_option(s, "probe_log", "1048577") != FS_EINVAL) return 44;
+            CHECK(fs_get_timing(s, "probes", &ms, &launches));
+            if (launches != 4) return 45;
+            CHECK(fs_set_probes(s, nullptr, 0));
+            CHECK(fs_run_one(s));
+            CHECK(fs_set_option(s, "probe_log", "0"));
         }
         CHECK(fs_set_option(s, "solver", "gs_lex"));
         CHECK(fs_run_one(s));
