@@ -17,6 +17,10 @@ FIELD_NAMES = ["dens", "v_x", "v_y", "v_z", "obs", "pressure", "divergence",
                "v_x_prev", "v_y_prev", "v_z_prev", "buffer"]
 COMM_ID_BYTES = 128
 FORCE_LOG_COLS = 9      # FS_FORCE_LOG_COLS: step, S1x, S1y, S1z, S2x, S2y, S2z, faces, frontal
+BODY_MAX = 16           # FS_BODY_MAX: bodies with a record of their own; the other components share record 0, the REST
+BODY_COLS = 8           # FS_BODY_COLS: Sx, Sy, Sz, Mx, My, Mz, faces, frontal rows
+BODY_INFO_COLS = 12     # FS_BODY_INFO_COLS: cells, anchor, xmin, xmax, ymin, ymax, zmin, zmax, sum x, sum y, sum z, frontal rows
+BODY_LOG_COLS = 16      # FS_BODY_LOG_COLS: step, body, S1xyz, M1xyz, S2xyz, M2xyz, faces, frontal rows
 RESIDUAL_COLS = 4       # FS_RESIDUAL_COLS: sum r^2, sum x0^2, max |r|, free cells
 RESIDUAL_LOG_SOLVES = 6     # FS_RESIDUAL_LOG_SOLVES: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density
 RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, r_sq, r_max, rhs_sq, cells
@@ -88,6 +92,11 @@ _SIGNATURES = {
     "fs_surface_case_table": (C.c_int, [C.c_int, C.c_void_p]),
     "fs_obstacle_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_force_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_label_bodies": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_body_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fs_body_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]),
+    "fs_body_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]),
+    "fs_body_force_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_solve_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "fs_diffuse_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fs_residual_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),

@@ -16,6 +16,7 @@
 #include "surface.h"
 #include "multigrid.h"
 #include "forces.h"
+#include "bodies.h"
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
@@ -55,8 +56,8 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -110,6 +111,12 @@ struct EngineBase {
     virtual int sample(int source, int mode, double* out, long n) = 0;
     virtual int probe_sample() = 0;
     virtual int probe_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
+    virtual int label_bodies(long* n_components, long* n_bodies) = 0;
+    virtual int body_labels(int32_t* dst, size_t n) = 0;
+    virtual int body_info(double* rows, long max_rows, long* n_rows) = 0;
+    virtual int body_force(double* out, long max_rows, long* n_rows, double* per_plane) = 0;
+    virtual int body_force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
+    virtual int body_counts(int* bodies, int* components) = 0;
 };
 
 struct fs_sim {
@@ -178,6 +185,9 @@ struct fs_sim {
     std::vector<int> probes;     // fs_set_probes: x, y, z per probe, padded global coordinates
     int probe_log = 0;           // "probe_log": records the probe log keeps, 0 = off
     long probe_gen = 0;          // bumped by fs_set_probes and fs_set_option("probe_log"): list and ring are set up anew, the log is cleared
+    int body_log = 0;            // "body_force_log": steps the per-body force log keeps, 0 = off
+    long body_log_gen = 0;       // bumped by fs_set_option("body_force_log") and ("moment_origin"): the ring is reallocated and cleared
+    double moment_origin[3] = {0.0, 0.0, 0.0};   // "moment_origin": r0 of the per-body moments, padded index coordinates
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -330,6 +340,22 @@ struct Engine : EngineBase {
     long probe_gen = -1;                // S->probe_gen they were set up for
     long probe_logged = 0;              // records taken since the ring was cleared or last drained
     std::vector<long> probe_step;       // step number held by each ring slot
+    // per-body forces and moments (bodies.h): the labels (dense padded int32), what the host keeps of the last labelling, and
+    // the per-step log, a device ring of body_cap steps x 2 projections x (body_B + 1) whole-grid records
+    int* body_L = nullptr;
+    bool bodies_dirty = true;           // obs changed since the last labelling (set where the flag bytes are rebuilt)
+    int body_B = 0;                     // bodies 1 .. body_B; record 0 is the REST
+    long body_ncomp = 0;                // components, the REST's included
+    std::vector<double> body_info_host; // (body_B + 1) x BODY_INFO
+    int* body_bbox = nullptr;           // per record, the cells its workgroups scan
+    double* body_planes = nullptr;      // plane records of the last launch: g.D x (BODY_MAX + 1) x BODY_REC (stream-ordered reuse)
+    double* body_total = nullptr;       // fs_body_force: the whole-grid records
+    double* body_ring = nullptr;
+    int body_cap = 0;
+    long body_gen = -1;                 // S->body_log_gen the ring was allocated for
+    bool body_ring_stale = false;       // a relabelling since then: the ring is set up anew, the log is cleared
+    long body_logged = 0;               // steps logged since the ring was cleared or last drained
+    std::vector<long> body_step;        // step number held by each ring slot
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -458,6 +484,8 @@ struct Engine : EngineBase {
         if (samp_out) hipFree(samp_out);
         if (probe_idx) hipFree(probe_idx);
         if (probe_ring) hipFree(probe_ring);
+        for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total, (void*)body_ring })
+            if (q) hipFree(q);
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -537,6 +565,7 @@ struct Engine : EngineBase {
         fs::launch_build_kill(S->stream, g, sc, flags, kill);
         if ((rc = build_clean())) return rc;
         flags_dirty = false;
+        bodies_dirty = true;
         mg_current = false;
         return FS_OK;
     }
@@ -1163,6 +1192,12 @@ struct Engine : EngineBase {
             ScopedSpan sp(S, FAM_FORCES);
             fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_slot(force_logged % force_cap, proj));
         }
+        if (proj >= 0 && proj < 2 && body_cap > 0) {
+            // "body_force_log": this projection's whole-grid records of every body go into the step's ring slot (no host sync)
+            ScopedSpan sp(S, FAM_BODYFORCES);
+            fs::launch_body_forces<T>(S->stream, g, arr[slot[FS_PRESSURE]], flags, body_L, body_bbox, body_B + 1, S->moment_origin,
+                                      body_planes, body_slot(body_logged % body_cap, proj));
+        }
         // the next consumer of v's z-halo planes is the divergence of the second projection
         // (v_z[z+-1]) and the advection back-trace; refresh them now.
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1372,6 +1407,7 @@ struct Engine : EngineBase {
         if ((rc = ensure_residual_ring())) return rc;
         if ((rc = flow_stats_config())) return rc;
         if ((rc = ensure_probe_ring())) return rc;
+        if ((rc = ensure_body_ring())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1442,6 +1478,7 @@ struct Engine : EngineBase {
         S->step_no++;
         S->steps_total++;
         if (force_cap > 0) force_step[(size_t)(force_logged++ % force_cap)] = S->steps_total;
+        if (body_cap > 0) body_step[(size_t)(body_logged++ % body_cap)] = S->steps_total;
         if (res_cap > 0) {
             res_ran[(size_t)(res_logged % res_cap)] = res_ran_now;
             res_step[(size_t)(res_logged++ % res_cap)] = S->steps_total;
@@ -2341,6 +2378,229 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- per-body forces and moments (bodies.h; beyond the reference) ------------------------------------
+    // Label the body cells if obs changed since the last labelling (or `force`).  Synchronises: a mask change is a set-up event.
+    int ensure_bodies(bool force = false)
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
+        int rc = ensure_flags();
+        if (rc) return rc;
+        if (!bodies_dirty && !force && body_L) return FS_OK;
+        const long N = dense_cells();
+        if (N >= (1L << 31)) return fail(FS_EINVAL, "body labels are 32-bit: %ld padded cells are too many", N);
+        struct Temp {                                    // freed on every path out
+            std::vector<void*> v;
+            ~Temp() { for (void* q : v) if (q) hipFree(q); }
+            hipError_t get(void** q, size_t bytes) { hipError_t e = hipMalloc(q, bytes ? bytes : 1); if (e == hipSuccess) v.push_back(*q); return e; }
+        } tmp;
+        constexpr int NINFO = (fs::BODY_MAX + 1) * fs::BODY_INFO;
+        if (!body_L) HIP_TRY(hipMalloc((void**)&body_L, (size_t)N * sizeof(int)));
+        if (!body_bbox) HIP_TRY(hipMalloc((void**)&body_bbox, (fs::BODY_MAX + 1) * 6 * sizeof(int)));
+        if (!body_planes) HIP_TRY(hipMalloc((void**)&body_planes, (size_t)g.D * (fs::BODY_MAX + 1) * fs::BODY_REC * sizeof(double)));
+        if (!body_total) HIP_TRY(hipMalloc((void**)&body_total, (fs::BODY_MAX + 1) * fs::BODY_REC * sizeof(double)));
+        int* cnt = nullptr;
+        unsigned long long* ctr = nullptr;               // body cells, components, cursor, changed; then the info table
+        HIP_TRY(tmp.get((void**)&cnt, (size_t)N * sizeof(int)));
+        HIP_TRY(tmp.get((void**)&ctr, (4 + NINFO) * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), S->stream));
+        fs::launch_body_init<T>(S->stream, g, arr[slot[FS_OBS]], body_L, ctr);
+        unsigned long long n_cells = 0;
+        HIP_TRY(hipMemcpyAsync(&n_cells, ctr, sizeof n_cells, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        for (unsigned long long round = 0;; ++round) {
+            if (round > n_cells + 1) return fail(FS_EHIP, "body labels did not settle within %llu rounds", round);
+            int changed = 0;
+            HIP_TRY(hipMemsetAsync(ctr + 3, 0, sizeof(unsigned long long), S->stream));
+            fs::launch_body_merge(S->stream, g, body_L, (int*)(ctr + 3));
+            HIP_TRY(hipMemcpyAsync(&changed, ctr + 3, sizeof changed, hipMemcpyDeviceToHost, S->stream));
+            HIP_TRY(hipStreamSynchronize(S->stream));
+            if (!changed) break;
+        }
+        HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), S->stream));
+        fs::launch_body_count(S->stream, g, body_L, cnt, ctr + 1);
+        unsigned long long n_roots = 0;
+        HIP_TRY(hipMemcpyAsync(&n_roots, ctr + 1, sizeof n_roots, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        long* pairs = nullptr;
+        int* lab = nullptr;
+        HIP_TRY(tmp.get((void**)&pairs, (size_t)n_roots * 2 * sizeof(long)));
+        HIP_TRY(tmp.get((void**)&lab, (size_t)n_roots * sizeof(int)));
+        fs::launch_body_compact(S->stream, g, body_L, cnt, pairs, ctr + 2);
+        std::vector<fs::BodyPair> hp((size_t)n_roots);
+        static_assert(sizeof(fs::BodyPair) == 2 * sizeof(long), "pairs travel as two longs");
+        if (n_roots) HIP_TRY(hipMemcpyAsync(hp.data(), pairs, (size_t)n_roots * 2 * sizeof(long), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        const std::vector<int> remap = fs::order_bodies(hp, fs::BODY_MAX);
+        if (n_roots) HIP_TRY(hipMemcpyAsync(lab, remap.data(), (size_t)n_roots * sizeof(int), hipMemcpyHostToDevice, S->stream));
+        fs::launch_body_relabel(S->stream, g, (long)n_roots, pairs, lab, body_L, cnt);
+        unsigned long long hinfo[NINFO];
+        for (int k = 0; k <= fs::BODY_MAX; ++k)
+            for (int c = 0; c < fs::BODY_INFO; ++c)
+                hinfo[k * fs::BODY_INFO + c] = (c == 1 || c == 2 || c == 4 || c == 6) ? ~0ull : 0ull;
+        HIP_TRY(hipMemcpyAsync(ctr + 4, hinfo, sizeof hinfo, hipMemcpyHostToDevice, S->stream));
+        fs::launch_body_info(S->stream, g, body_L, flags, ctr + 4);
+        HIP_TRY(hipMemcpyAsync(hinfo, ctr + 4, sizeof hinfo, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        body_ncomp = (long)n_roots;
+        body_B = (int)std::min<unsigned long long>(n_roots, fs::BODY_MAX);
+        body_info_host.assign((size_t)(body_B + 1) * fs::BODY_INFO, 0.0);
+        int bbox[(fs::BODY_MAX + 1) * 6];
+        for (int k = 0; k <= fs::BODY_MAX; ++k) {
+            int* b = bbox + 6 * k;
+            b[0] = b[2] = b[4] = 1;
+            b[1] = b[3] = b[5] = 0;                     // empty
+            if (k > body_B) continue;
+            const unsigned long long* q = hinfo + k * fs::BODY_INFO;
+            double* o = &body_info_host[(size_t)k * fs::BODY_INFO];
+            if (q[0] == 0) {                             // only the REST can be empty
+                o[1] = -1.0;
+                continue;
+            }
+            for (int c = 0; c < fs::BODY_INFO; ++c) o[c] = (double)q[c];
+            if (k == 0) {                                // the REST scans whole planes
+                b[1] = g.W; b[3] = g.H; b[5] = g.D;
+            } else {
+                b[0] = std::max(1, (int)q[2] - 1); b[1] = std::min(g.W, (int)q[3] + 1);
+                b[2] = std::max(1, (int)q[4] - 1); b[3] = std::min(g.H, (int)q[5] + 1);
+                b[4] = std::max(1, (int)q[6] - 1); b[5] = std::min(g.D, (int)q[7] + 1);
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(body_bbox, bbox, sizeof bbox, hipMemcpyHostToDevice, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));       // `bbox` and the temporaries leave scope
+        bodies_dirty = false;
+        body_ring_stale = true;
+        return FS_OK;
+    }
+
+    // ring slot k, projection j: body_B + 1 whole-grid records
+    size_t body_slot_doubles() const { return (size_t)(body_B + 1) * fs::BODY_REC; }
+    double* body_slot(long k, int j) const { return body_ring + ((size_t)k * 2 + (size_t)j) * body_slot_doubles(); }
+
+    // "body_force_log" on: label anew if obs changed; (re)allocate and clear the ring after a relabelling,
+    // fs_set_option("body_force_log") and ("moment_origin").  Off: nothing is launched or allocated.
+    int ensure_body_ring()
+    {
+        if (S->body_log > 0) {
+            int rc = ensure_bodies();
+            if (rc) return rc;
+        }
+        if (body_gen == S->body_log_gen && !body_ring_stale) return FS_OK;
+        if (body_ring) HIP_TRY(hipFree(body_ring));
+        body_ring = nullptr;
+        body_cap = 0;
+        body_logged = 0;
+        body_step.clear();
+        body_gen = S->body_log_gen;
+        body_ring_stale = false;
+        if (S->body_log <= 0) return FS_OK;
+        const size_t bytes = (size_t)S->body_log * 2 * body_slot_doubles() * sizeof(double);
+        HIP_TRY(hipMalloc((void**)&body_ring, bytes));
+        HIP_TRY(hipMemsetAsync(body_ring, 0, bytes, S->stream));
+        body_cap = S->body_log;
+        body_step.assign((size_t)body_cap, 0);
+        return FS_OK;
+    }
+
+    int label_bodies(long* n_components, long* n_bodies) override
+    {
+        int rc = ensure_bodies(true);
+        if (rc) return rc;
+        if (n_components) *n_components = body_ncomp;
+        if (n_bodies) *n_bodies = body_B;
+        return FS_OK;
+    }
+
+    int body_counts(int* bodies, int* components) override
+    {
+        int rc = ensure_bodies();
+        if (rc) return rc;
+        *bodies = body_B;
+        *components = (int)std::min<long>(body_ncomp, 0x7fffffffL);
+        return FS_OK;
+    }
+
+    int body_labels(int32_t* dst, size_t n) override
+    {
+        int rc = ensure_bodies();
+        if (rc) return rc;
+        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_body_labels: expected %ld elements, got %zu", dense_cells(), n);
+        HIP_TRY(hipMemcpyAsync(dst, body_L, n * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int body_info(double* rows, long max_rows, long* n_rows) override
+    {
+        int rc = ensure_bodies();
+        if (rc) return rc;
+        const long n = body_B + 1;
+        if (n_rows) *n_rows = n;
+        if (!rows) return FS_OK;
+        if (max_rows < n) return fail(FS_EINVAL, "fs_body_info: %ld rows, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        memcpy(rows, body_info_host.data(), body_info_host.size() * sizeof(double));
+        return FS_OK;
+    }
+
+    int body_force(double* out, long max_rows, long* n_rows, double* per_plane) override
+    {
+        int rc = ensure_bodies();
+        if (rc) return rc;
+        const long n = body_B + 1;
+        if (n_rows) *n_rows = n;
+        if (!out) return FS_OK;
+        if (max_rows < n) return fail(FS_EINVAL, "fs_body_force: %ld rows, room for %ld (pass out = NULL to ask)", n, max_rows);
+        {
+            ScopedSpan sp(S, FAM_BODYFORCES);
+            fs::launch_body_forces<T>(S->stream, g, arr[slot[FS_PRESSURE]], flags, body_L, body_bbox, (int)n, S->moment_origin,
+                                      body_planes, body_total);
+        }
+        HIP_TRY(hipMemcpyAsync(out, body_total, (size_t)n * fs::BODY_REC * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        if (per_plane)
+            HIP_TRY(hipMemcpyAsync(per_plane, body_planes, (size_t)g.D * n * fs::BODY_REC * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int body_force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
+        int rc = ensure_body_ring();
+        if (rc) return rc;
+        const long steps = body_cap > 0 ? std::min<long>(body_logged, body_cap) : 0;
+        const long nrec = body_B + 1, n = steps * nrec;
+        if (n_rows) *n_rows = n;
+        if (n_dropped) *n_dropped = body_logged - steps;
+        if (!rows) return FS_OK;                         // sizes only: nothing drained
+        if (max_rows < n) return fail(FS_EINVAL, "fs_body_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        const size_t per = 2 * body_slot_doubles();      // one step: both projections
+        const long first = body_logged - steps;
+        std::vector<double> mine((size_t)steps * per);
+        // the retained steps are at most two runs of consecutive slots (where the ring wraps): at most two copies
+        for (long i = 0; i < steps;) {
+            const long s0 = (first + i) % body_cap, run = std::min<long>(steps - i, body_cap - s0);
+            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, body_slot(s0, 0), (size_t)run * per * sizeof(double),
+                                   hipMemcpyDeviceToHost, S->stream));
+            i += run;
+        }
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        for (long i = 0; i < steps; ++i)
+            for (long k = 0; k < nrec; ++k) {
+                const double* a = &mine[(size_t)i * per + (size_t)k * fs::BODY_REC];
+                const double* b = a + per / 2;
+                double* o = rows + ((size_t)i * nrec + (size_t)k) * FS_BODY_LOG_COLS;
+                o[0] = (double)body_step[(size_t)((first + i) % body_cap)];
+                o[1] = (double)k;
+                for (int c = 0; c < 6; ++c) {
+                    o[2 + c] = a[c];
+                    o[8 + c] = b[c];
+                }
+                o[14] = b[6];
+                o[15] = b[7];
+            }
+        body_logged = 0;                                 // drained
+        return FS_OK;
+    }
+
     // ---- residual of the linear solves (residual.h; beyond the reference) ------------------------------------
     static constexpr int RES_SOLVES = FS_RESIDUAL_LOG_SOLVES;
     size_t res_plane_doubles() const { return (size_t)fs::RESIDUAL_REC * (size_t)g.D; }
@@ -2604,6 +2864,25 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "force_log: steps kept, 0 (off) .. 1048576");
         s->force_log = (int)n;
         s->force_log_gen++;
+    } else if (k == "body_force_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "body_force_log: steps kept, 0 (off) .. 1048576");
+        if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "body_force_log: bodies are labelled on a single-GPU handle");
+        s->body_log = (int)n;
+        s->body_log_gen++;
+    } else if (k == "moment_origin") {
+        double r[3];
+        const char* q = value;
+        for (int a = 0; a < 3; ++a) {
+            char* end = nullptr;
+            r[a] = strtod(q, &end);
+            if (end == q || !std::isfinite(r[a]) || *end != (a < 2 ? ',' : '\0'))
+                return fail(FS_EINVAL, "moment_origin: \"x,y,z\", three finite numbers (padded index coordinates)");
+            q = end + 1;
+        }
+        for (int a = 0; a < 3; ++a) s->moment_origin[a] = r[a];
+        s->body_log_gen++;
     } else if (k == "residual_log") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -2743,6 +3022,14 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "reach_hidden") *out = (int)s->n_reach_hidden;          // advections queued while the device still had the work placed before them ...
     else if (n == "reach_exposed") *out = (int)s->n_reach_exposed;        // ... and after it had run dry (a bubble on the device)
     else if (n == "probe_count") *out = (int)(s->probes.size() / 3);      // probes set by fs_set_probes
+    else if (n == "body_count" || n == "body_components") {               // bodies / components of the labelling (made now if obs changed)
+        int b = 0, c = 0;
+        { int rc_ = ensure_engine(s); if (rc_) return rc_; }
+        hipSetDevice(s->device);
+        const int rc = s->eng->body_counts(&b, &c);
+        if (rc) return rc;
+        *out = (n == "body_count") ? b : c;
+    }
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -3057,6 +3344,33 @@ int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_d
     return s->eng->force_log_fetch(rows, max_rows, n_rows, n_dropped);
 }
 
+int fs_label_bodies(fs_sim* s, long* n_components, long* n_bodies)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->label_bodies(n_components, n_bodies);
+}
+int fs_body_labels(fs_sim* s, int32_t* dst, size_t n)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dst) return fail(FS_EINVAL, "null buffer");
+    return s->eng->body_labels(dst, n);
+}
+int fs_body_info(fs_sim* s, double* rows, long max_rows, long* n_rows)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->body_info(rows, max_rows, n_rows);
+}
+int fs_body_force(fs_sim* s, double* out, long max_rows, long* n_rows, double* per_plane)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->body_force(out, max_rows, n_rows, per_plane);
+}
+int fs_body_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->body_force_log_fetch(rows, max_rows, n_rows, n_dropped);
+}
+
 int fs_solve_residual(fs_sim* s, int b, int field, int prev, double a, double c, double out[4], double* per_plane)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
@@ -3172,6 +3486,7 @@ int fs_comm_init(fs_sim* s, int rank, int nranks, const void* id)
     if (s->D % nranks) return fail(FS_EINVAL, "depth %d does not divide over %d slabs", s->D, nranks);
     if (nranks > 1 && s->D / nranks < 2) return fail(FS_EINVAL, "a slab needs at least 2 planes (two-deep halos), got %d", s->D / nranks);
     if (nranks == 1) return FS_OK;
+    if (s->body_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"body_force_log\" is on, and bodies are labelled on a single-GPU handle");
     hipSetDevice(s->device);
     if (s->comm.init(rank, nranks, id)) return fail(FS_ECOMM, "%s", s->comm.last_error());
     if (rank == 0 && !s->quiet)          // one line of provenance for multi-GPU logs

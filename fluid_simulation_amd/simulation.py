@@ -20,6 +20,19 @@ FORCE_LOG_DTYPE = np.dtype([("step", np.int64), ("s1x", np.float64), ("s1y", np.
                             ("frontal", np.int64), ("fx", np.float64), ("fy", np.float64), ("fz", np.float64),
                             ("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
 
+# Rows of Simulation.label_bodies(): fs_body_info's columns for record `body` (0 = the REST), then the centroid sum / cells
+BODY_INFO_DTYPE = np.dtype([("body", np.int64)] +
+                           [(n, np.int64) for n in ("cells", "anchor", "xmin", "xmax", "ymin", "ymax", "zmin", "zmax",
+                                                    "sum_x", "sum_y", "sum_z", "frontal")] +
+                           [("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
+
+# Columns of Simulation.body_force_log(): fs_body_force_log's raw columns, then force F, torque T and the coefficients C
+# (force) and CM (moment, for the l_ref of the call) of the step (S = S1 + S2, M = M1 + M2)
+BODY_LOG_DTYPE = np.dtype([("step", np.int64), ("body", np.int64)] +
+                          [(n + a, np.float64) for n in ("s1", "m1", "s2", "m2") for a in "xyz"] +
+                          [("faces", np.int64), ("frontal", np.int64)] +
+                          [(n + a, np.float64) for n in ("f", "t", "c", "cm") for a in "xyz"])
+
 # Columns of Simulation.residual_log(): fs_residual_log's raw columns (step, then r0_sq_k, r_sq_k, r_max_k, rhs_sq_k,
 # cells_k for the step's six solves k = 0..5: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density), then
 # reduction_k = sqrt(r_sq_k / r0_sq_k)
@@ -69,6 +82,31 @@ def pressure_force(s, frontal, dt, speed, width, height, depth):
     return force, coeff
 
 
+def pressure_moment(m, frontal, l_ref, dt, speed, width, height, depth):
+    """Torque and moment coefficients of raw pressure moments (include/fluidsim.h, "per-body pressure forces and
+    moments"): T = M * h^3 / dt with h = 1 / cbrt(width * height * depth), and C_M = 2 * M / (dt * speed^2 * N_front *
+    L_ref), N_front = `frontal`, L_ref = `l_ref` in cells (NaN where the denominator is 0).  `m` has shape (..., 3),
+    `frontal` the leading shape; returns (T, C_M), both (..., 3), in fp64."""
+    m = np.asarray(m, dtype=np.float64)
+    n = np.asarray(frontal, dtype=np.float64)[..., None]
+    h = 1.0 / np.cbrt(float(int(width) * int(height) * int(depth)))
+    dt = float(dt)
+    torque = m * (h * h * h) / dt
+    denom = dt * (float(speed) * float(speed)) * n * float(l_ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        coeff = np.where(denom != 0.0, 2.0 * m / np.where(denom != 0.0, denom, 1.0), np.nan)
+    return torque, coeff
+
+
+def shift_moment(m, s, origin_from, origin_to):
+    """The moment about `origin_to` of a record whose moment about `origin_from` is `m` and whose sum is `s`:
+    M - (to - from) x S, in fp64.  `m` and `s` have shape (..., 3)."""
+    m = np.asarray(m, dtype=np.float64)
+    s = np.asarray(s, dtype=np.float64)
+    d = np.asarray(origin_to, dtype=np.float64) - np.asarray(origin_from, dtype=np.float64)
+    return m - np.cross(np.broadcast_to(d, s.shape), s)
+
+
 class Simulation:
     """Simulation(w, h, d, iter, speed=30, dt=0.05, diff=2.0e-5, visc=1.5e-5, acc=15)
     -- simulation.h:59-64.  Extra keyword options map to fs_set_option."""
@@ -110,6 +148,8 @@ class Simulation:
     def set_option(self, key, value):
         if isinstance(value, bool):
             value = "1" if value else "0"
+        elif key == "moment_origin" and not isinstance(value, str):
+            value = ",".join(repr(float(v)) for v in value)
         check(self._L.fs_set_option(self._h, key.encode(), str(value).encode()))
 
     # -- public data members of the reference class (simulation.h:44-54) ---------------
@@ -270,6 +310,74 @@ class Simulation:
         for k, a in enumerate("xyz"):
             rows["f" + a] = force[:, k]
             rows["c" + a] = coeff[:, k]
+        return (rows, dropped.value) if with_dropped else rows
+
+    # -- per-body forces and moments (single GPU) --------------------------------------------
+    def _body_info(self):
+        n = C.c_long()
+        check(self._L.fs_body_info(self._h, None, 0, C.byref(n)))
+        raw = np.zeros((n.value, _lib.BODY_INFO_COLS), dtype=np.float64)
+        check(self._L.fs_body_info(self._h, raw.ctypes.data, n.value, C.byref(n)))
+        rows = np.zeros(n.value, dtype=BODY_INFO_DTYPE)
+        rows["body"] = np.arange(n.value)
+        for k, name in enumerate(BODY_INFO_DTYPE.names[1:1 + _lib.BODY_INFO_COLS]):
+            rows[name] = raw[:, k]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for a in "xyz":
+                rows["c" + a] = raw[:, 8 + "xyz".index(a)] / raw[:, 0]
+        return rows
+
+    def label_bodies(self):
+        """Labels the solid cells into bodies now (fs_label_bodies) and returns the body table (fs_body_info) as a
+        BODY_INFO_DTYPE structured array: row 0 is the REST, rows 1..B the bodies by decreasing size; cx, cy, cz is
+        the centroid sum / cells (NaN for an empty REST)."""
+        check(self._L.fs_label_bodies(self._h, None, None))
+        return self._body_info()
+
+    def body_info(self):
+        """The body table of the current mask (labelled anew only if obs changed); see label_bodies."""
+        return self._body_info()
+
+    body_count = property(lambda s: s._geti("body_count"))
+    body_components = property(lambda s: s._geti("body_components"))
+
+    def body_labels(self):
+        """The label array (fs_body_labels), int32 of `shape`: k on the cells of body k, -1 on REST cells, 0 elsewhere."""
+        n = self._L.fs_padded_size(self._h)
+        out = np.zeros(n, dtype=np.int32)
+        check(self._L.fs_body_labels(self._h, out.ctypes.data, n))
+        return out.reshape(self.shape)
+
+    def body_force(self, per_plane=False):
+        """Per-body pressure force and moment from FS_PRESSURE as it is now (fs_body_force): (B + 1, 8) records
+        {Sx, Sy, Sz, Mx, My, Mz, faces, frontal rows}, row 0 the REST; with per_plane=True also the plane records,
+        (depth, B + 1, 8), as a pair."""
+        n = C.c_long()
+        check(self._L.fs_body_force(self._h, None, 0, C.byref(n), None))
+        out = np.zeros((n.value, _lib.BODY_COLS), dtype=np.float64)
+        pp = np.zeros((self.depth, n.value, _lib.BODY_COLS), dtype=np.float64) if per_plane else None
+        check(self._L.fs_body_force(self._h, out.ctypes.data, n.value, C.byref(n), None if pp is None else pp.ctypes.data))
+        return (out, pp) if per_plane else out
+
+    def body_force_log(self, with_dropped=False, l_ref=1.0):
+        """Drains the per-step body-force log (option body_force_log=N; fs_body_force_log): B + 1 rows per retained
+        step, oldest first, as a BODY_LOG_DTYPE structured array.  with_dropped=True returns (rows, number of logged
+        steps the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_body_force_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        raw = np.zeros((n.value, _lib.BODY_LOG_COLS), dtype=np.float64)
+        check(self._L.fs_body_force_log(self._h, raw.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        rows = np.zeros(n.value, dtype=BODY_LOG_DTYPE)
+        for k, name in enumerate(BODY_LOG_DTYPE.names[:_lib.BODY_LOG_COLS]):
+            rows[name] = raw[:, k]
+        dims = (self.dt, self.speed, self.width, self.height, self.depth)
+        force, coeff = pressure_force(raw[:, 2:5] + raw[:, 8:11], raw[:, 15], *dims)
+        torque, cm = pressure_moment(raw[:, 5:8] + raw[:, 11:14], raw[:, 15], l_ref, *dims)
+        for k, a in enumerate("xyz"):
+            rows["f" + a] = force[:, k]
+            rows["t" + a] = torque[:, k]
+            rows["c" + a] = coeff[:, k]
+            rows["cm" + a] = cm[:, k]
         return (rows, dropped.value) if with_dropped else rows
 
     def solve_residual(self, b, field, prev, a, c, per_plane=False):

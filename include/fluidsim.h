@@ -111,6 +111,9 @@ int fs_destroy(fs_sim* s);
  *                 it.  Setting it (re)allocates and clears the log.  May be changed at any time.
  *   "flow_stats"  "off" (default) | "mean" | "moments", "flow_stats_every" N >= 1, "flow_stats_start" S >= 0: time-averaged
  *                 flow statistics on the device, see fs_flow_stats_field below.  May be changed at any time.
+ *   "body_force_log" N >= 0 (at most 1048576): keep the per-body forces and moments of the last N steps (fs_body_force_log); 0
+ *                 (default) = off, and the step launches and allocates nothing for it.  "moment_origin" "x,y,z": the origin of
+ *                 the moments (default "0,0,0").  Setting either clears the log.  May be changed at any time.  Single GPU only.
  *   "probe_log"   N >= 0 (at most 1048576): keep the last N records of the point probes (fs_set_probes, fs_probe_log); 0 (default) =
  *                 off, and the step launches and allocates nothing for it.  Setting it (re)allocates and clears the log.  May be
  *                 changed at any time.
@@ -219,7 +222,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "sweep_pair") "forces" (fs_obstacle_force and the "force_log" records) "residual" (fs_solve_residual / fs_diffuse_residual and the
  * "residual_log" records: one launch counted per record, i.e. per solve and point in time -- 12 per step with the log on,
  * 10 where the dead density solve is elided, 0 with it off) "flow_stats" (one launch per sample of the time-averaged flow
- * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off).  Events are recorded on the handle's own stream. */
+ * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off) "body_forces"
+ * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -297,6 +301,78 @@ int fs_surface_case_table(int config, int* edges);
 #define FS_FORCE_LOG_COLS 9
 int fs_obstacle_force(fs_sim* s, double out[5], double* per_plane);
 int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+
+/* ---- per-body pressure forces and moments (beyond the reference: it has no force output, no file:line counterpart) ----
+ *
+ * The section above weighs everything in the tunnel at once.  Here the solid cells are labelled into bodies on the
+ * device and force AND moment are reported per body.  Nothing above changes.  Single-GPU handles only: on a z-slab
+ * handle all five entries and option "body_force_log" return FS_EINVAL, and so does fs_comm_init on a handle whose
+ * "body_force_log" is on (connectivity across slabs is not built).
+ *
+ * BODY CELLS AND COMPONENTS.  A BODY CELL is an interior cell (1..w, 1..h, 1..d) with obs != 0 -- the condition under
+ * which a neighbour blocks a face above.  A COMPONENT is a maximal set of body cells connected through faces
+ * (6-connectivity); cells that touch only along an edge or at a corner are not connected.  A component's size is its
+ * cell count, its anchor the smallest padded linear index x + (w + 2) * (y + (h + 2) * z) among its cells.
+ *
+ * BODIES.  Components are ordered by decreasing size, ties by increasing anchor.  The first B = min(components,
+ * FS_BODY_MAX) are bodies 1..B; all remaining components together are record 0, the REST (with voxelised geometry: the
+ * speckle).  The label array holds k on the cells of body k, -1 on REST cells and 0 on every other cell of the padded
+ * array.  The labelling is a pure function of obs (integer work only: every number below that describes it is exact).
+ *
+ * BODY INFO, per record k = 0..B, exact integers carried in fp64 (FS_BODY_INFO_COLS = 12):
+ *     {cells, anchor, xmin, xmax, ymin, ymax, zmin, zmax, sum x, sum y, sum z, frontal rows}
+ * frontal rows = the number of (y, z) rows that hold a cell of record k with obs == 1.  For an empty REST anchor is -1
+ * and the bounds are 0.  The centroid is sum / cells.
+ *
+ * FORCE AND MOMENT RECORD.  A BLOCKED face is exactly what the section above defines, between c with obs(c) != 1 and an
+ * in-range neighbour n with obs(n) != 0; it belongs to the record of n's label.  With q = +p(c) for n on the positive
+ * side of c along axis a and q = -p(c) on the negative side, the face adds q to S_a.  With r = (x, y, z) of cell c minus
+ * the moment origin r0, in padded index coordinates, it adds r x (q e_a) to M:
+ *     axis x: My += q * rz, Mz -= q * ry;   axis y: Mx -= q * rz, Mz += q * rx;   axis z: Mx += q * ry, My -= q * rx.
+ * The face centre lies half a cell from c along e_a, and a cross product with e_a removes any offset along e_a: the half
+ * cell never enters the moment, the arm of a face is its cell's.  All arithmetic is fp64 on the stored p widened; each
+ * product and each add is rounded once, without contraction.  Per z-plane and record the result is (FS_BODY_COLS = 8)
+ *     {Sx, Sy, Sz, Mx, My, Mz, faces, frontal rows of that plane}
+ * and the whole-grid record adds the planes in increasing z in fp64, starting from +0.0.  Every blocked face is a term
+ * of its own: a cell blocked on both sides of an axis by the same record adds +p and then -p.  fs_obstacle_force adds
+ * its terms in another order, so the S of the records summed agrees with its S to rounding, not bit for bit.
+ *
+ * MOMENT ORIGIN.  r0 is option "moment_origin" = "x,y,z" (three doubles; default "0,0,0", the padded array's origin).
+ * It may be set at any time; setting it clears the body-force log.  One origin serves all bodies; M about another point
+ * is M - (r0' - r0) x S.
+ *
+ * UNITS.  F = S * h^2 / dt as above; torque per unit density T = M * h^3 / dt; C_M = 2 * M / (dt * speed^2 * N_front *
+ * L_ref) with L_ref in cells supplied by the caller.  PRESSURE only, as above: there is no viscous stress.
+ *
+ * PURE FUNCTION.  A plane's record for a body is a pure function of that plane's p, the flag bytes, the labels, the
+ * origin and (w, h): one workgroup of a fixed size per plane and record, a fixed assignment of cells to lanes, a fixed
+ * shuffle / LDS tree, no floating-point atomics.  Launch shape and timing cannot change a bit of it.
+ *
+ * fs_label_bodies labels now, whatever changed; the other entries (and fs_get_int "body_count" = B, "body_components")
+ * label lazily whenever obs has changed.  A labelling synchronises the stream: a mask change is a set-up event.
+ * fs_body_labels writes the labels into a dense padded array of n = (w+2)(h+2)(d+2) entries.
+ * fs_body_info writes rows[FS_BODY_INFO_COLS * k + ...] and *n_rows = B + 1.
+ * fs_body_force writes out[FS_BODY_COLS * k + ...] for the pressure in FS_PRESSURE now; per_plane (may be NULL) receives
+ * [((z - 1) * (B + 1) + k) * FS_BODY_COLS + col] for the planes z = 1..d.
+ * In both, rows / out = NULL only reports *n_rows; max_rows < *n_rows is FS_EINVAL.
+ *
+ * fs_body_force_log (option "body_force_log" = N, 0 = off by default, at most 1048576): inside fs_step, right after EACH
+ * of the step's two projections, the whole-grid records of all B + 1 records go into a device ring on the step's own
+ * stream, without a host synchronisation; with the option off a step launches and allocates nothing for it.  If obs
+ * changed, the labelling is made anew at the top of fs_step.  The call drains the log, B + 1 rows per retained step,
+ * rows[FS_BODY_LOG_COLS * i + ...] = {step, body, S1x, S1y, S1z, M1x, M1y, M1z, S2x, S2y, S2z, M2x, M2y, M2z, faces,
+ * frontal rows}; step, oldest-first order, rows = NULL, max_rows and *n_dropped (in steps) are as for fs_force_log.  A
+ * relabelling, a change of "moment_origin" and setting the option each clear the log.
+ */
+#define FS_BODY_MAX 16
+#define FS_BODY_COLS 8
+#define FS_BODY_INFO_COLS 12
+#define FS_BODY_LOG_COLS 16
+int fs_label_bodies(fs_sim* s, long* n_components, long* n_bodies);
+int fs_body_labels(fs_sim* s, int32_t* dst, size_t n);
+int fs_body_info(fs_sim* s, double* rows, long max_rows, long* n_rows);
+int fs_body_force(fs_sim* s, double* out, long max_rows, long* n_rows, double* per_plane);
+int fs_body_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
 
 /* ---- residual of the linear solves (beyond the reference: it never evaluates one, no file:line counterpart) ----
  *

@@ -22,6 +22,11 @@
 //   --forces FILE  log the obstacle pressure force of every step (option "force_log") and write it to FILE as CSV:
 //                  fs_force_log's columns, then F = (S1 + S2) h^2 / dt and C = 2 (S1 + S2) / (dt speed^2 N_front)
 //                  (include/fluidsim.h)
+//   --body-forces FILE  label the obstacles into bodies and log the pressure force and moment of every body and step
+//                  (option "body_force_log") and write them to FILE as CSV: `#` lines with the body table (fs_body_info),
+//                  then fs_body_force_log's columns and F, the torque T = (M1 + M2) h^3 / dt and the coefficients C and
+//                  C_M (for L_ref = 1 cell); --moment-origin x,y,z sets the origin of the moments (option "moment_origin",
+//                  padded index coordinates, default 0,0,0); single GPU, may be combined with --forces
 //   --residuals FILE  log the residual of the step's six linear solves before and after each (option "residual_log") and
 //                  write it to FILE as CSV: fs_residual_log's columns, then reduction_k = sqrt(r_sq_k / r0_sq_k);
 //                  may be combined with --forces
@@ -126,6 +131,49 @@ int write_forces(fs_sim* sim, const char* path, int w, int h, int d, float dt, i
     return ok ? 0 : 1;
 }
 
+// the body table and the per-step body-force log of the run -> CSV (the columns of Simulation.body_force_log() in the
+// Python package, for l_ref = 1)
+int write_body_forces(fs_sim* sim, const char* path, int w, int h, int d, float dt, int speed)
+{
+    long nb = 0, n = 0, dropped = 0;
+    if (fs_body_info(sim, nullptr, 0, &nb)) return 1;
+    std::vector<double> info((size_t)nb * FS_BODY_INFO_COLS);
+    if (fs_body_info(sim, info.data(), nb, &nb)) return 1;
+    if (fs_body_force_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * FS_BODY_LOG_COLS);
+    if (fs_body_force_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "# body,cells,anchor,xmin,xmax,ymin,ymax,zmin,zmax,sum_x,sum_y,sum_z,frontal (body 0 = the rest)\n");
+    for (long k = 0; k < nb; ++k) {
+        fprintf(fp, "# %ld", k);
+        for (int c = 0; c < FS_BODY_INFO_COLS; ++c) fprintf(fp, ",%ld", (long)info[(size_t)k * FS_BODY_INFO_COLS + c]);
+        fprintf(fp, "\n");
+    }
+    fprintf(fp, "step,body,s1x,s1y,s1z,m1x,m1y,m1z,s2x,s2y,s2z,m2x,m2y,m2z,faces,frontal,fx,fy,fz,tx,ty,tz,cx,cy,cz,cmx,cmy,cmz\n");
+    const double hh = 1.0 / std::cbrt((double)((long)w * h * d)), t = (double)dt, sp = (double)speed;
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * FS_BODY_LOG_COLS];
+        fprintf(fp, "%ld,%ld", (long)r[0], (long)r[1]);
+        for (int k = 2; k < 14; ++k) fprintf(fp, ",%.17g", r[k]);
+        fprintf(fp, ",%ld,%ld", (long)r[14], (long)r[15]);
+        const double denom = t * (sp * sp) * r[15];
+        double f[3], tq[3], c[3], cm[3];
+        for (int k = 0; k < 3; ++k) {
+            const double s = r[2 + k] + r[8 + k], m = r[5 + k] + r[11 + k];
+            f[k] = s * (hh * hh) / t;
+            tq[k] = m * (hh * hh * hh) / t;
+            c[k] = denom != 0.0 ? 2.0 * s / denom : NAN;
+            cm[k] = denom != 0.0 ? 2.0 * m / denom : NAN;
+        }
+        for (const double* v : { f, tq, c, cm }) fprintf(fp, ",%.17g,%.17g,%.17g", v[0], v[1], v[2]);
+        fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
 // the per-step residual log of the run -> CSV (the columns of Simulation.residual_log() in the Python package)
 int write_residuals(fs_sim* sim, const char* path)
 {
@@ -223,7 +271,7 @@ int main(int argc, char** argv)
     float dt = FS_DEFAULT_DT, diff = FS_DEFAULT_DIFF, visc = FS_DEFAULT_VISC;
     std::vector<Stl> stls;
     bool stl_given = false, json = false;
-    std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir, probes_path, probe_log_path;
+    std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir, probes_path, probe_log_path, body_forces_path;
     bool mean_moments = false;
     std::vector<std::pair<std::string, std::string>> options;
 
@@ -244,6 +292,8 @@ int main(int argc, char** argv)
         if (key == "seed") { options.push_back({ "voxel_seed", val }); return true; }
         if (key == "resume") { resume_dir = val; return true; }
         if (key == "forces") { forces_path = val; return true; }
+        if (key == "body-forces") { body_forces_path = val; return true; }
+        if (key == "moment-origin") { options.push_back({ "moment_origin", val }); return true; }
         if (key == "residuals") { residuals_path = val; return true; }
         if (key == "mean-flow") { mean_dir = val; return true; }
         if (key == "vortex") { vortex_dir = val; return true; }
@@ -255,7 +305,7 @@ int main(int argc, char** argv)
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
-                                        "mean-every", "vortex", "probes", "probe-log" };
+                                        "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -284,6 +334,7 @@ int main(int argc, char** argv)
     fs_sim* sim = fs_create(width, height, depth, iter, speed, dt, diff, visc, acc);   // simulation.cpp:438
     if (!sim) return die("fs_create");
     if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
+    if (!body_forces_path.empty()) options.push_back({ "body_force_log", std::to_string(iter) });
     if (!residuals_path.empty()) options.push_back({ "residual_log", std::to_string(iter) });
     if (!mean_dir.empty()) options.push_back({ "flow_stats", mean_moments ? "moments" : "mean" });
     std::vector<int> probe_cells;
@@ -309,6 +360,7 @@ int main(int argc, char** argv)
     if (fs_sync(sim)) return die("fs_sync");
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
+    if (!body_forces_path.empty() && write_body_forces(sim, body_forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_body_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     int mean_samples = 0;
