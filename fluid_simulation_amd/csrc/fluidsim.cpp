@@ -56,6 +56,15 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// what "auto" means for the options "zero_start" and "fuse_project_advect": decided by measurement.
+// (-DFS_ZERO_START_AUTO=0|1, -DFS_PROJECT_ADVECT_AUTO=0|1: development builds for same-box A/B runs of an unchanged bench.py)
+#ifndef FS_ZERO_START_AUTO
+#define FS_ZERO_START_AUTO 1
+#endif
+#ifndef FS_PROJECT_ADVECT_AUTO
+#define FS_PROJECT_ADVECT_AUTO 1
+#endif
+constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
 enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_COUNT };
 const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces" };
 
@@ -138,6 +147,10 @@ struct fs_sim {
     unsigned voxel_seed = 1;
     bool quiet = false, profile = false, elide_dead = false;
     bool fuse_advect = true;     // one kernel for the three velocity advections of a step (single GPU)
+    // "zero_start" / "fuse_project_advect": -1 = auto, 0, 1.  What auto means is decided by measurement.
+    int zero_start = -1;         // project(): the divergence pass does not zero p in memory, the first pass of the solve takes zeros
+    int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
+    long n_zero_start = 0, n_project_advect = 0;   // projections / steps that took those paths (fs_get_int)
     int overlap = -1;            // z-slabs, how a pass and its halo exchange are scheduled: 0 the pass, then the exchange; 1 boundary
                                  // planes first, their exchange on the communication stream while the interior is computed; 2 boundary
                                  // launch + exchange on the communication stream beside the interior launch; -1 (default) = "auto":
@@ -623,13 +636,13 @@ struct Engine : EngineBase {
     // second >= 0, to the equally long range starting there).
     // push: the pass also stores the planes its z neighbours need into their halo planes (plain Jacobi passes, FSIPC)
     void launch_pass(hipStream_t st, int levels, bool rb, const T* src_, const T* rhs_, T* dst_, int b, T a, T inv_c, int zf,
-                     int zl, int second = -1, const fs::PeerPush* push = nullptr)
+                     int zl, int second = -1, const fs::PeerPush* push = nullptr, bool zero_src = false)
     {
         const T omega = rb ? rb_omega : (T)0;
         const bool fused2 = fs::decode_plan(false, plan_two).kind == fs::SweepKernel::Fused2;
         if (levels == 3)
             fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_three, second, push,
-                                       &maskplan);
+                                       &maskplan, zero_src);
         else if (levels == 2 && !rb && fused2)
             fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 2, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_two, second, push);
         else if (levels == 2)
@@ -759,6 +772,7 @@ struct Engine : EngineBase {
         int next = 0;                // first pass not yet launched
         int b = 0, rhs = -1, src = -1;
         bool src_temp = false, rb = false, damped = false;
+        bool zero_src = false;       // the initial iterate is all zeros and its array is not read (zero_start_ok)
         T a = (T)0, inv_c = (T)1, omega = (T)1;
     };
 
@@ -821,9 +835,10 @@ struct Engine : EngineBase {
 
     // `cur` holds the initial iterate (may equal rhs when the caller aliased a snapshot).
     // smoother = true: `sweeps` passes of two 6/7-damped Jacobi sweeps each (the level-0 smoothing step of solver=mg)
-    int solve_begin(SolveRun& r, int b, int cur, int rhs, T a, T c, int sweeps, bool smoother = false)
+    int solve_begin(SolveRun& r, int b, int cur, int rhs, T a, T c, int sweeps, bool smoother = false, bool zero_src = false)
     {
         r = SolveRun();
+        r.zero_src = zero_src;
         r.b = b; r.rhs = rhs; r.src = cur; r.a = a;
         r.inv_c = (T)1 / c;                              // cRecip, :257
         // solver=rbsor: every iteration is one pass of the pair kernel (its two levels are the two colours)
@@ -845,6 +860,9 @@ struct Engine : EngineBase {
             left -= lv;
         }
         const int npass = (int)r.plan.size();
+        if (r.zero_src && !(npass > 0 && r.plan[0] == 3 && !r.rb && !S->comm.active() &&
+                            fs::jacobi_fused_zero_start(S->tune, g, sc, (int)sizeof(T), plan_three)))
+            return fail(FS_EINVAL, "zero start: the first pass of this solve has no zero-start kernel");   // zero_start_ok promised it
         if (npass > 0 && S->comm.active() && (r.plan[0] > 1 || npass > 1)) {
             // a fused pass recomputes the lower levels of the neighbours' boundary planes: it reads the
             // right-hand side there, so its halo planes must be current
@@ -885,7 +903,8 @@ struct Engine : EngineBase {
             if (span < 0) { span = S->span_begin(fam); span_fam = fam; }
             ++span_launches;
             if (!S->comm.active()) {
-                launch_pass(S->stream, lv, r.rb, arr[r.src], arr[r.rhs], arr[dst], r.b, r.a, r.inv_c, 1, g.D);
+                launch_pass(S->stream, lv, r.rb, arr[r.src], arr[r.rhs], arr[dst], r.b, r.a, r.inv_c, 1, g.D, -1, nullptr,
+                            r.zero_src && i == 0);
             } else {
                 // planes a neighbour needs of this pass's result: as many as its next pass has levels; after
                 // the last pass the halos are brought to their full depth (what every other kernel assumes)
@@ -913,7 +932,7 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int solve(int b, int cur, int rhs, T a, T c, int sweeps, int* result, bool smoother = false)
+    int solve(int b, int cur, int rhs, T a, T c, int sweeps, int* result, bool smoother = false, bool zero_src = false)
     {
         if (S->solver == FS_SOLVER_GS_LEX) {
             if (S->comm.active()) return fail(FS_EINVAL, "gs_lex is a single-GPU verification mode");
@@ -925,7 +944,7 @@ struct Engine : EngineBase {
             return FS_OK;
         }
         SolveRun r;
-        int rc = solve_begin(r, b, cur, rhs, a, c, sweeps, smoother);
+        int rc = solve_begin(r, b, cur, rhs, a, c, sweeps, smoother, zero_src);
         if (rc) return rc;
         return solve_end(r, result);
     }
@@ -1156,7 +1175,23 @@ struct Engine : EngineBase {
     }
 
     // ---- project (simulation.cpp:289-362) ----------------------------------------------
-    int project() override
+    // "zero_start": may this projection leave p unzeroed in memory and start its solve from zeros that are not read?  Only
+    // where the solve is `acc` >= 3 Jacobi sweeps whose first pass is the three-sweep kernel in a build that has the zero-start
+    // form, the launch plans are already chosen (timing them reads the iterate), there are no slabs (the halo exchange of p
+    // carries the zeros) and nothing reads p before the solve (the residual log's "before" record).
+    bool zero_start_ok(int log_k) const
+    {
+        if (!(S->zero_start < 0 ? ZERO_START_AUTO : S->zero_start != 0) || S->solver != FS_SOLVER_JACOBI || S->acc < 3 || S->comm.active()) return false;
+        if (log_k >= 0 && res_cap > 0) return false;
+        const TunedFor now{S->tune.fuse, S->tune.pair_shape, S->tune.two_kind, S->replay_two, S->replay_three};
+        if (!(plan_two >= 0 && tuned_for == now) || plan_three < 0) return false;
+        return fs::jacobi_fused_zero_start(S->tune, g, sc, (int)sizeof(T), plan_three);
+    }
+
+    int project() override { return project_T(false); }
+    // defer_gradient (step(), "fuse_project_advect"): everything but the gradient pass -- v stays as it was before the
+    // projection and FS_PRESSURE holds the solved pressure; the caller's next launch applies the gradient itself
+    int project_T(bool defer_gradient)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         int rc = ensure_flags();
@@ -1164,25 +1199,27 @@ struct Engine : EngineBase {
         for (int f : { FS_VX, FS_VY, FS_VZ, FS_PRESSURE, FS_DIVERGENCE })
             if ((rc = unalias(f))) return rc;
         const T h = (T)1 / host_cbrt<T>((T)(S->W * S->H * S->D));   // :295 (int product, like the reference)
+        const int proj = in_step ? projections_this_step++ : -1;   // which of the step's two projections this is
+        const int log_k = (proj >= 0 && proj < 2) ? 3 + proj : -1;
+        const bool zero_start = zero_start_ok(log_k);
+        if (zero_start) ++S->n_zero_start;
         {
             ScopedSpan sp(S, FAM_DIV);
             fs::launch_divergence<T>(S->stream, S->tune, g, sc, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]],
-                                     arr[slot[FS_DIVERGENCE]], arr[slot[FS_PRESSURE]], flags, (T)(-0.5) * h);
+                                     arr[slot[FS_DIVERGENCE]], arr[slot[FS_PRESSURE]], flags, (T)(-0.5) * h, !zero_start);
         }
         // divergence of the neighbouring slabs' boundary planes is never read (the solve only reads
         // rhs at the cell itself); the pressure halo planes still hold the previous projection and
         // must become the neighbours' freshly zeroed planes before the first sweep reads them.
         if ((rc = halo(arr[slot[FS_PRESSURE]]))) return rc;
-        const int proj = in_step ? projections_this_step++ : -1;   // which of the step's two projections this is
-        const int log_k = (proj >= 0 && proj < 2) ? 3 + proj : -1;
         if ((rc = log_residual(log_k, 0, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
         int res;
         if (S->solver == FS_SOLVER_MG) rc = multigrid_solve(FS_PRESSURE, FS_DIVERGENCE, &res);
-        else rc = solve(0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], (T)1, (T)6, S->acc, &res);   // :320
+        else rc = solve(0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], (T)1, (T)6, S->acc, &res, false, zero_start);   // :320
         if (rc) return rc;
         adopt(FS_PRESSURE, res);
         if ((rc = log_residual(log_k, 1, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
-        {
+        if (!defer_gradient) {
             ScopedSpan sp(S, FAM_GRAD);
             fs::launch_gradient<T>(S->stream, S->tune, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
                                    arr[slot[FS_VZ]], flags, h, (T)2 * h);
@@ -1393,6 +1430,19 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // The gradient pass a project_T(true) left out and advect_velocity_fused() in one kernel (single GPU).
+    int gradient_advect_velocity_fused()
+    {
+        const T h = (T)1 / host_cbrt<T>((T)(S->W * S->H * S->D));   // :295, as in project_T
+        const T kx = (T)S->dt * (T)S->W, ky = (T)S->dt * (T)S->H, kz = (T)S->dt * (T)S->D;   // :384-386
+        ScopedSpan sp(S, FAM_ADVECT);
+        fs::launch_gradient_advect_velocity<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
+                                               arr[slot[FS_VZ]], arr[slot[FS_VX_PREV]], arr[slot[FS_VY_PREV]],
+                                               arr[slot[FS_VZ_PREV]], flags, h, (T)2 * h, kx, ky, kz);
+        ++S->n_project_advect;
+        return FS_OK;
+    }
+
     // ---- step (simulation.cpp:96-150) ---------------------------------------------------
     int step() override
     {
@@ -1434,7 +1484,12 @@ struct Engine : EngineBase {
         }
         for (int k = 0; k < 3; ++k)                      // :115-117
             if ((rc = diffuse_T(k + 1, V[k], V0[k], k))) return rc;
-        if ((rc = project())) return rc;                 // :120
+        // "fuse_project_advect": where :125-127 run as one kernel of the per-cell form on one GPU, that kernel also applies the
+        // gradient of :120 (nothing else reads the projected velocities: the force logs read p)
+        const bool fuse_pa = (S->fuse_project_advect < 0 ? PROJECT_ADVECT_AUTO : S->fuse_project_advect != 0) && !S->comm.active() &&
+                             !gs && S->acc > 0 && S->fuse_advect && S->tune.advect_cell == 1 && slot[FS_VX] != slot[FS_VX_PREV] &&
+                             slot[FS_VY] != slot[FS_VY_PREV] && slot[FS_VZ] != slot[FS_VZ_PREV];
+        if ((rc = project_T(fuse_pa))) return rc;        // :120
         // z-slabs: :135's density solve (independent of the velocities; its result is dead, :136 overwrites it) is the work
         // the device does while the reach of each advection travels to the host -- half of its passes here, between the
         // first projection and the velocity advection, the other half where the reference has it, between the second
@@ -1453,8 +1508,10 @@ struct Engine : EngineBase {
             if (!split) return;
             if (hipEventQuery(ev_slack) == hipErrorNotReady) ++S->n_reach_hidden; else ++S->n_reach_exposed;
         };
-        if (S->fuse_advect && slot[FS_VX] != slot[FS_VX_PREV] && slot[FS_VY] != slot[FS_VY_PREV] &&
-            slot[FS_VZ] != slot[FS_VZ_PREV]) {
+        if (fuse_pa) {
+            if ((rc = gradient_advect_velocity_fused())) return rc;
+        } else if (S->fuse_advect && slot[FS_VX] != slot[FS_VX_PREV] && slot[FS_VY] != slot[FS_VY_PREV] &&
+                   slot[FS_VZ] != slot[FS_VZ_PREV]) {
             // :125-127 in one pass (the three traces only chain through the cell's own values)
             if ((rc = advect_velocity_fused())) return rc;
         } else {
@@ -2919,6 +2976,9 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         s->dump_async = (v != "0");
     } else if (k == "fuse_advect") {
         s->fuse_advect = (v != "0");
+    } else if (k == "zero_start" || k == "fuse_project_advect") {
+        if (v != "auto" && v != "0" && v != "1") return fail(FS_EINVAL, "%s: auto | 0 | 1", key);
+        (k == "zero_start" ? s->zero_start : s->fuse_project_advect) = (v == "auto") ? -1 : atoi(value);
     } else if (k == "overlap") {
         if (s->eng && s->overlap_plan >= 0) return fail(FS_EINVAL, "overlap must be set before the first solve");
         s->overlap = (v == "auto") ? -1 : atoi(value);
@@ -3007,6 +3067,8 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "last_advect_reach") *out = s->last_reach;
     else if (n == "pair_shape") *out = s->eng ? s->eng->tuned_two() : -1;
     else if (n == "triple_plan") *out = s->eng ? s->eng->tuned_three() : -1;
+    else if (n == "zero_start_projections") *out = s->n_zero_start;        // projections whose solve started from unread zeros
+    else if (n == "project_advect_steps") *out = s->n_project_advect;      // steps whose first gradient ran inside the advection
     else if (n == "two_sweep_fused")   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
         *out = (s->eng && fs::decode_plan(false, s->eng->tuned_two()).kind == fs::SweepKernel::Fused2) ? 1 : 0;
     else if (n == "halo_depth") *out = s->eng ? s->eng->halo_depth() : 0;

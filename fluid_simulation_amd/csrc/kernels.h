@@ -120,8 +120,12 @@ void launch_jacobi_pair(hipStream_t st, const SweepTune& tune, const GridDesc& g
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
-                         int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr);
+                         int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr, bool zero_src = false);
 // mp: the single-GPU clean table (fp32 three sweeps only; nullptr = no mask-free body)
+// zero_src: level 0 is all zeros and `src` is not read (the first pass of a pressure solve, whose iterate the divergence pass
+// would otherwise have to zero in memory first).  Only where jacobi_fused_zero_start says the launch has such a build: the
+// same launch plan, workgroups and arithmetic as the reading build, bit-identical with it on a zeroed `src`.
+bool jacobi_fused_zero_start(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int elem_size, int plan);
 
 template <class T>
 void launch_gs_lex(hipStream_t st, const GridDesc& g, T* q, const T* rhs, const uint8_t* flags, int b, T a, T inv_c,
@@ -132,7 +136,8 @@ void launch_set_bounds(hipStream_t st, const GridDesc& g, const SlabCtx& sc, T* 
 
 template <class T>
 void launch_divergence(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* vx, const T* vy,
-                       const T* vz, T* div, T* p, const uint8_t* flags, T mhalf_h);
+                       const T* vz, T* div, T* p, const uint8_t* flags, T mhalf_h, bool store_p = true);
+// store_p = false: `p` is left as it is (the solve that follows starts from zeros it does not read, launch_jacobi_fused)
 
 template <class T>
 void launch_gradient(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* p, T* vx, T* vy,
@@ -153,6 +158,13 @@ template <class T>
 void launch_advect_velocity(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, T* vx, T* vy, T* vz,
                             const T* px, const T* py, const T* pz, const uint8_t* flags, const uint8_t* kill, T* coltab, T kx,
                             T ky, T kz, long zshift);
+
+// launch_gradient of a projection and the launch_advect_velocity that follows it in one pass (single GPU, per-cell form):
+// vy, vz hold the velocities before the gradient, p the solved pressure; all three come out advected, as the two launches
+// leave them.  The projected velocities themselves are not stored.
+template <class T>
+void launch_gradient_advect_velocity(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const T* p, T* vx, T* vy, T* vz,
+                                     const T* px, const T* py, const T* pz, const uint8_t* flags, T h, T two_h, T kx, T ky, T kz);
 
 template <class T>
 void launch_build_flags(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const T* obs, uint8_t* flags);

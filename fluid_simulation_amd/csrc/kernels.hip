@@ -776,7 +776,9 @@ __device__ __forceinline__ void store_row_bounds(const GridDesc& g, const SlabCt
 }
 
 // divergence + pressure reset + setBounds(0,div) + setBounds(0,p)   simulation.cpp:295-319
-template <class T, int RY>
+// STORE_P = false leaves `p` alone: the caller starts the pressure solve with a pass that takes level 0 as all zeros
+// instead of reading it (sweep_fused.hip, zero start), so the reset would be written to HBM for nobody.
+template <class T, int RY, bool STORE_P>
 __global__ __launch_bounds__(256) void divergence_march_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ vx,
                                                                 const T* __restrict__ vy, const T* __restrict__ vz,
                                                                 T* __restrict__ dv, T* __restrict__ p,
@@ -830,7 +832,7 @@ __global__ __launch_bounds__(256) void divergence_march_kernel(GridDesc g, SlabC
                 d[e] = (f & F_SOLID) ? zero : mhalf_h * acc;
             }
             store_row_bounds<T>(g, sc, dv, base, t.x0, y, z, d, 0u, 0);
-            store_row_bounds<T>(g, sc, p, base, t.x0, y, z, zeros, 0u, 0);
+            if constexpr (STORE_P) store_row_bounds<T>(g, sc, p, base, t.x0, y, z, zeros, 0u, 0);
         }
 #pragma unroll
         for (int r = 0; r < RY; ++r)
@@ -988,7 +990,7 @@ template void launch_set_bounds<double>(hipStream_t, const GridDesc&, const Slab
 // project, part 1: divergence + pressure reset + setBounds(0,div) + setBounds(0,p)
 //   simulation.cpp:295-319
 // =====================================================================================
-template <class T>
+template <class T, bool STORE_P>
 __global__ __launch_bounds__(256) void divergence_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ vx,
                                                           const T* __restrict__ vy, const T* __restrict__ vz,
                                                           T* __restrict__ dv, T* __restrict__ p,
@@ -1012,29 +1014,39 @@ __global__ __launch_bounds__(256) void divergence_kernel(GridDesc g, SlabCtx sc,
         d = mhalf_h * acc;                               // (-0.5f*h)*div_val, :314
     }
     dv[c] = d;
-    p[c] = (T)0;
     write_face_ghosts(g, sc, dv, c, x, y, z, d, 0);      // setBounds(0,div): solid cells already hold 0
-    write_face_ghosts(g, sc, p, c, x, y, z, (T)0, 0);    // setBounds(0,p)
+    if constexpr (STORE_P) {
+        p[c] = (T)0;
+        write_face_ghosts(g, sc, p, c, x, y, z, (T)0, 0);    // setBounds(0,p)
+    }
 }
 
 template <class T>
 void launch_divergence(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* vx, const T* vy,
-                       const T* vz, T* div, T* p, const uint8_t* flags, T mhalf_h)
+                       const T* vz, T* div, T* p, const uint8_t* flags, T mhalf_h, bool store_p)
 {
     if (tune.project_cell) {
-        hipLaunchKernelGGL((divergence_kernel<T>), cell_grid(g), cell_block(), 0, st, g, sc, vx, vy, vz, div, p, flags,
-                           mhalf_h);
+        if (store_p)
+            hipLaunchKernelGGL((divergence_kernel<T, true>), cell_grid(g), cell_block(), 0, st, g, sc, vx, vy, vz, div, p, flags,
+                               mhalf_h);
+        else
+            hipLaunchKernelGGL((divergence_kernel<T, false>), cell_grid(g), cell_block(), 0, st, g, sc, vx, vy, vz, div, p, flags,
+                               mhalf_h);
         return;
     }
     constexpr int RY = 2;
     const MarchLaunch m = march_launch(g, RY);
-    hipLaunchKernelGGL((divergence_march_kernel<T, RY>), dim3(m.nblk), dim3(256), 0, st, g, sc, vx, vy, vz, div, p, flags,
-                       mhalf_h, m.zc_len, m.nxw, m.nybg, m.nblk);
+    if (store_p)
+        hipLaunchKernelGGL((divergence_march_kernel<T, RY, true>), dim3(m.nblk), dim3(256), 0, st, g, sc, vx, vy, vz, div, p, flags,
+                           mhalf_h, m.zc_len, m.nxw, m.nybg, m.nblk);
+    else
+        hipLaunchKernelGGL((divergence_march_kernel<T, RY, false>), dim3(m.nblk), dim3(256), 0, st, g, sc, vx, vy, vz, div, p, flags,
+                           mhalf_h, m.zc_len, m.nxw, m.nybg, m.nblk);
 }
 template void launch_divergence<float>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const float*,
-                                       const float*, const float*, float*, float*, const uint8_t*, float);
+                                       const float*, const float*, float*, float*, const uint8_t*, float, bool);
 template void launch_divergence<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const double*,
-                                        const double*, const double*, double*, double*, const uint8_t*, double);
+                                        const double*, const double*, double*, double*, const uint8_t*, double, bool);
 
 // =====================================================================================
 // project, part 2: v -= grad p, then setBounds(1,vx), (2,vy), (3,vz)
@@ -1230,6 +1242,50 @@ __global__ __launch_bounds__(256) void advect_velocity_kernel(GridDesc g, SlabCt
             sy = near ? (T)0 : ny;
             nz = back_trace<T>(g, sc, pz, zshift, x, y, z, sx, sy, pz[c + zshift], kx, ky, kz);
         }
+    }
+    vx[c] = near ? (T)0 : nx;
+    vy[c] = near ? (T)0 : ny;
+    vz[c] = near ? (T)0 : nz;
+    write_face_ghosts(g, sc, vx, c, x, y, z, nx, 1);
+    write_face_ghosts(g, sc, vy, c, x, y, z, ny, 2);
+    write_face_ghosts(g, sc, vz, c, x, y, z, nz, 3);
+}
+
+// The gradient pass of the step's first projection (simulation.cpp:322-361) and the three velocity advections that follow
+// it (:125-127) in one pass.  The advection overwrites all three velocities and reads the projected ones only at its own cell,
+// and of those only v_y and v_z (v_x is carried by the pre-diffusion snapshot px, :380): a thread forms what the gradient pass
+// would have stored there -- v - grad p, zeroed next to a solid (store_row_bounds) -- in registers and traces with it.  The
+// projected v_x is never formed, the projected v_y, v_z and all three ghost-face sets never reach memory: the advection's own
+// setBounds writes every one of those cells again, and no trace reads them (the traces read px, py, pz).  p's y and z
+// neighbours come from L1 / L2 as in gradient_kernel.  In place: a thread reads vy, vz at its own cell before it writes it.
+template <class T>
+__global__ __launch_bounds__(256) void gradient_advect_velocity_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ p,
+                                                                        T* __restrict__ vx, T* __restrict__ vy,
+                                                                        T* __restrict__ vz, const T* __restrict__ px,
+                                                                        const T* __restrict__ py, const T* __restrict__ pz,
+                                                                        const uint8_t* __restrict__ flags, T h, T two_h, T kx,
+                                                                        T ky, T kz)
+{
+    const int x = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = 1 + blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);   // cell_block(): a wave is one row
+    const int z = 1 + blockIdx.z;
+    if (x > g.W || y > g.H) return;
+    const long c = cell(g, x, y, z);
+    const unsigned f = flags[c];
+    const bool near = (f & F_NEAR) != 0;
+    T nx = (T)0, ny = (T)0, nz = (T)0;                   // un-zeroed results (0 inside solids, :375-377)
+    T sx = (T)0, sy = (T)0;                              // what setBounds leaves in v_x, v_y
+    if (!(f & F_SOLID)) {
+        T oy = vy[c], oz = vz[c];
+        const T pc = p[c];
+        oy -= one_sided_grad<T>(f & F_YP, f & F_YM, p[c + g.sy], pc, p[c - g.sy], h, two_h);   // :326-334
+        oz -= one_sided_grad<T>(f & F_ZP, f & F_ZM, p[c + g.sz], pc, p[c - g.sz], h, two_h);
+        if (near) oy = oz = (T)0;                        // setBounds(2, v_y), (3, v_z) of the projection
+        nx = back_trace<T>(g, sc, px, 0, x, y, z, px[c], oy, oz, kx, ky, kz);
+        sx = near ? (T)0 : nx;
+        ny = back_trace<T>(g, sc, py, 0, x, y, z, sx, py[c], oz, kx, ky, kz);
+        sy = near ? (T)0 : ny;
+        nz = back_trace<T>(g, sc, pz, 0, x, y, z, sx, sy, pz[c], kx, ky, kz);
     }
     vx[c] = near ? (T)0 : nx;
     vy[c] = near ? (T)0 : ny;
@@ -1531,6 +1587,20 @@ template void launch_advect_velocity<float>(hipStream_t, const SweepTune&, const
 template void launch_advect_velocity<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, double*, double*,
                                              double*, const double*, const double*, const double*, const uint8_t*,
                                              const uint8_t*, double*, double, double, double, long);
+
+template <class T>
+void launch_gradient_advect_velocity(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const T* p, T* vx, T* vy, T* vz,
+                                     const T* px, const T* py, const T* pz, const uint8_t* flags, T h, T two_h, T kx, T ky, T kz)
+{
+    hipLaunchKernelGGL((gradient_advect_velocity_kernel<T>), cell_grid(g), cell_block(), 0, st, g, sc, p, vx, vy, vz, px, py, pz,
+                       flags, h, two_h, kx, ky, kz);
+}
+template void launch_gradient_advect_velocity<float>(hipStream_t, const GridDesc&, const SlabCtx&, const float*, float*, float*,
+                                                     float*, const float*, const float*, const float*, const uint8_t*, float,
+                                                     float, float, float, float);
+template void launch_gradient_advect_velocity<double>(hipStream_t, const GridDesc&, const SlabCtx&, const double*, double*, double*,
+                                                      double*, const double*, const double*, const double*, const uint8_t*,
+                                                      double, double, double, double, double);
 
 template <class T>
 void launch_advect(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int b, T* field, const T* prev,

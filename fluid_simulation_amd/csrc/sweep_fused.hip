@@ -84,7 +84,10 @@ struct CleanArgs {
     const int* plan = nullptr;
 };
 
-template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL>
+// Z0 (zero start): level 0 is all zeros and is not read -- no load_core, no hb / ht / eL / eR loads, L0 held as constants.  The
+// level-1 expression stays (rh + a * nb) * inv_c on nb = 0 + 0 + ..., the operations a zeroed `src` would feed it (no
+// fast-math, -ffp-contract=off), so the result is bit-identical with reading zeros; `src` is never dereferenced.
+template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL, bool Z0 = false>
 __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ src,
                                                                       const T* __restrict__ rhs, T* __restrict__ dst,
                                                                       const uint8_t* __restrict__ flags, int b, T a, T inv_c,
@@ -92,6 +95,8 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
                                                                       int nbands, int nblk, PeerPush pp, CleanArgs ca)
 {
     static_assert(NL == 2 || NL == 3, "two or three sweeps per pass");
+    static_assert(!Z0 || (NL == 3 && ALIGNED && !SLAB && sizeof(T) == 4 && (WALLSEL == 1 || WALLSEL == 3)),
+                  "the zero-start form exists for the whole-domain lane-aligned fp32 three-sweep builds");
     constexpr int BY = NYW * RY, TW = NXW * 256 + 8, RW = NXW * 256;
     constexpr int OV = NL - 1;                           // rows / planes a band / chunk loses per side
     constexpr int ES = (int)sizeof(T);
@@ -145,6 +150,16 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     T hb[4], ht[4], eL[RY], eR[RY], rcur[RY][4];
     T gz1[RY][4] = {}, gz2[RY][4] = {};                 // ghost plane D+1 of levels 1 and 2 while it waits for its register slot
     unsigned flc[RY], kl[3][RY] = {};                    // (not in idle load registers: a select on those would wait for the loads)
+    if constexpr (Z0) {
+#pragma unroll
+        for (int r = 0; r < RY; ++r) {
+            eL[r] = eR[r] = (T)0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) L0[0][r][e] = L0[1][r][e] = L0[2][r][e] = (T)0;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hb[e] = ht[e] = (T)0;
+    }
     // `ngroups` groups of three plane iterations from z_from on with one of the bodies (the register slots rotate with period
     // three: a group starts and ends with every plane in its home slot, so bodies can alternate between groups), then, with
     // tail_to >= 0, the march's last one or two iterations up to tail_to.  wallc: 1 general, 0 wall-free, 2 mask-free (wall-free,
@@ -185,6 +200,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     };
 
     auto load_core = [&](int z, T (&out)[RY][4]) {
+        if constexpr (Z0) return;
         const char* sp = plane_of(src, z);
 #pragma unroll
         for (int r = 0; r < RY; ++r) ld4(sp + oc[r], out[r]);
@@ -193,11 +209,14 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         const char* sp = plane_of(src, z);
         const char* rp = plane_of(rhs, z);
         const uint8_t* fp = flags + (long)z * plane_f;
-        ld4(sp - step_b + oc[0], hb);
-        ld4(sp + step_t + oc[RY - 1], ht);
+        if constexpr (!Z0) {
+            ld4(sp - step_b + oc[0], hb);
+            ld4(sp + step_t + oc[RY - 1], ht);
+        }
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
-            if constexpr (XS) {                          // the cells x = 256 wx and 256 wx + 257 of the row (wave-uniform)
+            if constexpr (Z0) {                          // (level 0 is not read)
+            } else if constexpr (XS) {                   // the cells x = 256 wx and 256 wx + 257 of the row (wave-uniform)
                 const char* rowp = sp + (long)(wx * 256 + (int)clampy(y0 + r) * g.sy) * ES;
                 eL[r] = load_uniform(rowp);
                 eR[r] = load_uniform(rowp + 257 * ES);
@@ -382,7 +401,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
                         yp[e] = (r < RY - 1) ? L0[I1][r < RY - 1 ? r + 1 : r][e] : ht[e];
                     }
                     T left = eL[r], right = eR[r];
-                    if constexpr (XS) {
+                    if constexpr (XS && !Z0) {
                         left = lane_from_left(L0[I1][r][3], eL[r]);
                         right = lane_from_right(L0[I1][r][0], eR[r]);
                     }
@@ -587,7 +606,7 @@ void MaskPlan::release()
 template <class T, int NL, int NXW, int NYW, int RY>
 static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
                            const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last,
-                           const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp)
+                           const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src)
 {
     const PeerPush pp = (push && second_first < 0) ? *push : PeerPush();
     constexpr int BY = NYW * RY, THREADS = NXW * NYW * 64;
@@ -620,6 +639,10 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
 #define FS_LAUNCH(AL, SL, WS)                                                                                            \
     hipLaunchKernelGGL((jacobi_fused_kernel<T, NL, NXW, NYW, RY, AL, SL, WS>), dim3(nblk), dim3(THREADS), 0, st, g, sc, src, \
                        rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp, ca)
+    // the same launch with the zero-start form of the kernel: same plan, same workgroups, `src` not read
+#define FS_LAUNCH_Z0(WS)                                                                                                  \
+    hipLaunchKernelGGL((jacobi_fused_kernel<T, NL, NXW, NYW, RY, true, false, WS, true>), dim3(nblk), dim3(THREADS), 0, st, g, sc, \
+                       src, rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp, ca)
     // The wall-free second body exists for the three-sweep kernel on lane-aligned whole-domain grids (the benchmark grids).
     // Rounds 1-2 selected a body per WORKGROUP: 9 % (512^3) to 14 % (256^3) faster for the interior ones, but a pass ends with its
     // slowest workgroup, and at 512^3 (256 workgroups, one per CU) half of them touch a z wall.  Round 3 selects per GROUP OF
@@ -633,10 +656,18 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
             // mask_free "auto": rows of two waves only -- on 256-cell rows (c2) this build measured slower (4.70 -> 4.81 ms per step)
             const bool mask_free = tune.mask_free >= 2 || (tune.mask_free == 1 && NXW >= 2);
             if (whole && mask_free && mp && !mp->host.empty() &&
-                (ca.plan = mask_free_plan(st, *mp, tune.chunk_cost, g, BY, nbands, nblk / nbands, zc_len)))
-                FS_LAUNCH(true, false, 3);   // the mask-free build, on z chunks balanced per band unless the cost model is off
-            else if (whole) FS_LAUNCH(true, false, 1);
-            else FS_LAUNCH(true, true, 1);               // z-slabs: an inner rank has no z wall at all
+                (ca.plan = mask_free_plan(st, *mp, tune.chunk_cost, g, BY, nbands, nblk / nbands, zc_len))) {
+                // the mask-free build, on z chunks balanced per band unless the cost model is off
+                if constexpr (sizeof(T) == 4) {
+                    if (zero_src) { FS_LAUNCH_Z0(3); return; }
+                }
+                FS_LAUNCH(true, false, 3);
+            } else if (whole) {
+                if constexpr (sizeof(T) == 4) {
+                    if (zero_src) { FS_LAUNCH_Z0(1); return; }
+                }
+                FS_LAUNCH(true, false, 1);
+            } else FS_LAUNCH(true, true, 1);             // z-slabs: an inner rank has no z wall at all
             return;
         }
     }
@@ -644,6 +675,17 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
     else if (aligned) FS_LAUNCH(true, true, 0);
     else FS_LAUNCH(false, true, 0);
 #undef FS_LAUNCH
+#undef FS_LAUNCH_Z0
+}
+
+// Whether a whole-range launch of the three-sweep kernel with this plan reaches a build that has the zero-start form: the
+// conditions launch_fused_v tests on its way to FS_LAUNCH_Z0 (fp32, lane-aligned rows of 256 or 512 cells, whole domain, the
+// two-body builds), asked by the host before it decides not to zero the iterate in memory.
+bool jacobi_fused_zero_start(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int elem_size, int plan)
+{
+    if (elem_size != 4 || plan < 0 || tune.abl == 16 || tune.wall_free < 1 || !sc.lo_wall || !sc.hi_wall || g.D < 1) return false;
+    const SweepShape* shape = launch_shape(4, SweepKernel::Three, g.W, decode_plan(true, plan).shape);
+    return shape && shape->NL == 3 && g.W == shape->NXW * 256;
 }
 
 // The builds of jacobi_fused_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them).
@@ -659,7 +701,7 @@ static_assert(FusedBuildsF32::covers(4, SweepKernel::Three) && FusedBuildsF32::c
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
-                         int second_first, const PeerPush* push, MaskPlan* mp)
+                         int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src)
 {
     const PlanId p = decode_plan(levels == 3, plan);
     const SweepKernel kind = levels == 3 ? SweepKernel::Three : SweepKernel::Fused2;
@@ -680,14 +722,14 @@ void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& 
     List::run(*shape, [&](auto build) {
         using B = decltype(build);
         launch_fused_v<T, B::NL, B::NXW, B::NYW, B::RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, *shape,
-                                                        p.alt, second_first, push, sizeof(T) == 4 ? mp : nullptr);
+                                                        p.alt, second_first, push, sizeof(T) == 4 ? mp : nullptr, zero_src);
     });
 }
 template void launch_jacobi_fused<float>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const float*,
                                          const float*, float*, const uint8_t*, int, float, float, int, int, int, int,
-                                         const PeerPush*, MaskPlan*);
+                                         const PeerPush*, MaskPlan*, bool);
 template void launch_jacobi_fused<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const double*,
                                           const double*, double*, const uint8_t*, int, double, double, int, int, int, int,
-                                          const PeerPush*, MaskPlan*);
+                                          const PeerPush*, MaskPlan*, bool);
 
 }  // namespace fs

@@ -134,6 +134,13 @@ int fs_destroy(fs_sim* s);
  *                 in another run; -1 = none): replay those launch plans instead of timing candidates (profiling);
  *   "wall_free"   "auto" (default) | "0" | "1": whether workgroups of the three-sweep kernel that touch no wall run its
  *                 wall-free second body (auto: when a launch has more than 256 workgroups);
+ *   "zero_start"  "auto" (default: on) | "0" | "1": a projection whose pressure solve starts with the three-sweep kernel on
+ *                 lane-aligned fp32 rows (256 or 512 cells, one GPU, acc >= 3, Jacobi, residual log off) does not zero p in
+ *                 memory; the first pass takes the zeros as constants.  "0" = the launches without it;
+ *   "fuse_project_advect" "auto" (default: on) | "0" | "1": on one GPU the gradient pass of a step's first projection runs
+ *                 inside the kernel of the three velocity advections ("advect_kernels" = "cell", Jacobi, acc > 0; fs_project
+ *                 and fs_advect are not affected).  fs_get_int "zero_start_projections" / "project_advect_steps" count
+ *                 the projections / steps that took these paths;
  *   "sweep_ry" "sweep_zc" "sweep_blocks" "pair_zc" "pair_shape" "project_kernels" "fuse_advect"
  *                 -- see csrc/kernels.h (SweepTune), csrc/fluidsim.cpp and tools/tune_*.py.
  * z-slab handles only (never change results either):

@@ -34,7 +34,9 @@ if len(sys.argv) > 4:
 import re  # noqa: E402
 
 # json key -> pattern of the kernel name as rocprofv3 prints it (first match wins)
-KEYS = (("jacobi_fused_kernel<NL=3>", r"jacobi_fused_kernel<\w+, 3,"), ("jacobi_fused_kernel<NL=2>", r"jacobi_fused_kernel<\w+, 2,"),
+KEYS = (("jacobi_fused_kernel<NL=3, zero start>", r"jacobi_fused_kernel<\w+, 3,[^>]*, true>"),
+        ("gradient_advect_velocity_kernel", "gradient_advect_velocity_kernel"),
+        ("jacobi_fused_kernel<NL=3>", r"jacobi_fused_kernel<\w+, 3,"), ("jacobi_fused_kernel<NL=2>", r"jacobi_fused_kernel<\w+, 2,"),
         ("jacobi_pair_kernel", "jacobi_pair_kernel"), ("jacobi_sweep_kernel", "jacobi_sweep_kernel"),
         ("advect_velocity_kernel", "advect_velocity_kernel"), ("advect_kernel", "advect_kernel"),
         ("divergence_march_kernel", "divergence_march_kernel"), ("gradient_march_kernel", "gradient_march_kernel"),
