@@ -208,7 +208,11 @@ int fs_advect(fs_sim* s, int b, int field, int prev);                           
 
 /* Copies one field in the reference's own layout: padded (w+2)(h+2)(d+2), x fastest
  * (simulation.h:9).  elem_size selects the host element type (4 = float, 8 = double);
- * conversion happens on the device.  n is the element count of the host buffer. */
+ * conversion happens on the device.  n is the element count of the host buffer.
+ * The twelve edges of the padded box (cells that are ghosts in two or three directions) are written by no pass of the
+ * reference, so they are 0 in every state a run reaches; a caller of fs_set_field keeps them 0.  Passes here do not
+ * preserve other values there (a solve leaves its result in another array, row-wise kernels store whole 16-byte groups
+ * across the row end), while the reference would carry them along and corner back-traces would read them. */
 int fs_get_field(fs_sim* s, int which, void* dst, size_t n, int elem_size);
 int fs_set_field(fs_sim* s, int which, const void* src, size_t n, int elem_size);
 size_t fs_padded_size(fs_sim* s);   /* Simulation::size  simulation.cpp:35 */

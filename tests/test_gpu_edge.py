@@ -148,17 +148,21 @@ def test_two_sweep_kernels_agree_at_benchmark_row_widths(F):
 @pytest.mark.parametrize("speed,shape,fp64", [(30, (70, 33, 21), False), (1, (70, 33, 21), False), (-20, (66, 20, 17), False),
                                               (30, (300, 12, 9), True), (2, (23, 9, 40), True)])
 def test_advection_row_kernels_match_cell_kernels_and_oracle(F, oracle_mod, speed, shape, fp64):
-    """The default advection kernels (four cells per lane; traces whose x coordinate clamps read the
-    pre-interpolated inlet / outlet column tables) against the per-cell kernels and the oracle: inlet speed 30
-    (every trace clamps low), 1 (hardly any does), negative (clamps at the outlet side), ragged row ends."""
+    """The row, clamp-table and tile forms of the advection kernels against the per-cell kernels and the oracle over the
+    first steps of the tunnel's own start, at inlet speeds 30, 1, 2 and -20, on grids with ragged row ends.  That flow has
+    not left the inlet region after four steps: a few per cent of the fluid cells have an x coordinate that clamps to the
+    inlet side and read the clamp tables, no trace clamps at the outlet side (not at speed -20 either), hardly any clamps in
+    y or z, and no clamped trace leaves a tile's window, not even one of radius 1.  So this covers the launch shapes, the
+    ragged ends and the unclamped gather of every form; the outlet side of the tables, the tile kernel's fallback, the window's
+    clipping and LDS cap and the x clamps combined with y / z clamps are held by tests/test_gpu_advect_rough.py."""
     O = oracle_mod
     W, H, D = shape
     kw = dict(precision="fp64") if fp64 else {}
     m = ball_mask(W, H, D, W / 3.0, H / 2.0, D / 2.0, min(W, H, D) / 4.0)
     m[1, 1, 1] = m[D, H, W] = True
     sims = [F.Simulation(W, H, D, 1, speed=speed, acc=4, quiet=1, advect_kernels=k, **kw) for k in ("row", "cell", "celltab")]
-    # the tile kernels (inlet table windows staged in LDS): a window of 1 row / plane (most traces leave it and take the
-    # per-cell path) and the default one
+    # the tile kernels (inlet table windows staged in LDS): a window of 1 row / plane and the default one (under this flow
+    # every clamped trace stays inside either; traces that leave a window: tests/test_gpu_advect_rough.py)
     sims += [F.Simulation(W, H, D, 1, speed=speed, acc=4, quiet=1, advect_kernels="tile", advect_window=w, **kw) for w in (1, 24)]
     ora = O.Oracle(W, H, D, solver=O.JACOBI, fp64=fp64, threads=4, speed=speed, acc=4)
     for x in sims + [ora]:
