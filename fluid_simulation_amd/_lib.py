@@ -43,6 +43,10 @@ SAMPLE_STAT = 1024
 PROBE_MAX = 4096        # FS_PROBE_MAX: probes fs_set_probes takes
 PROBE_VALUES = 5        # FS_PROBE_VALUES: dens, v_x, v_y, v_z, pressure per probe and record
 PROBE_NAMES = ["dens", "v_x", "v_y", "v_z", "pressure"]
+# FS_IMG_*: kinds of fs_image_values / fs_image_rgb -- a slice, or the sum, maximum or minimum along the axis
+IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN = range(4)
+IMG_KINDS = {"slice": IMG_SLICE, "sum": IMG_SUM, "max": IMG_MAX, "min": IMG_MIN}
+IMAGE_VIEWS_MAX = 8     # FS_IMAGE_VIEWS_MAX: views fs_image_views takes
 
 
 class FluidsimError(RuntimeError):
@@ -113,6 +117,15 @@ _SIGNATURES = {
     "fs_set_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "fs_probe_sample": (C.c_int, [C.c_void_p]),
     "fs_probe_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_image_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fs_image_rgb": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                               C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fs_image_colormap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_image_png": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p]),
+    "fs_image_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_image_sample": (C.c_int, [C.c_void_p]),
+    "fs_image_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

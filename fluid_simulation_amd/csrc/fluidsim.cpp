@@ -17,6 +17,7 @@
 #include "multigrid.h"
 #include "forces.h"
 #include "bodies.h"
+#include "image.h"
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
@@ -65,8 +66,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -126,6 +127,18 @@ struct EngineBase {
     virtual int body_force(double* out, long max_rows, long* n_rows, double* per_plane) = 0;
     virtual int body_force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
     virtual int body_counts(int* bodies, int* components) = 0;
+    virtual int image_values(int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows) = 0;
+    virtual int image_rgb(int source, int kind, int axis, int index, double vmin, double vmax, double alpha, uint8_t* out, size_t n_bytes,
+                          int* cols, int* rows) = 0;
+    virtual int image_config() = 0;            // apply fs_image_views / fs_set_option("image_log"): allocate or free, clear
+    virtual int image_sample() = 0;
+    virtual int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
+};
+
+// one view of the image log (fs_image_views)
+struct ImageView {
+    int source, kind, axis, index;
+    double vmin, vmax, alpha;
 };
 
 struct fs_sim {
@@ -201,6 +214,12 @@ struct fs_sim {
     int body_log = 0;            // "body_force_log": steps the per-body force log keeps, 0 = off
     long body_log_gen = 0;       // bumped by fs_set_option("body_force_log") and ("moment_origin"): the ring is reallocated and cleared
     double moment_origin[3] = {0.0, 0.0, 0.0};   // "moment_origin": r0 of the per-body moments, padded index coordinates
+    std::vector<ImageView> image_views;   // fs_image_views
+    int image_log = 0;           // "image_log": frames the image log keeps, 0 = off
+    long image_every = 1;        // "image_every": fs_step takes a frame when (steps_total - 1) % image_every == 0
+    long image_gen = 0;          // bumped by fs_image_views and fs_set_option("image_log"): the ring is set up anew, the log is cleared
+    std::vector<uint8_t> image_table;   // fs_image_colormap: n RGB triples; empty = the built-in table
+    long image_table_gen = 0;    // bumped by fs_image_colormap
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -261,6 +280,33 @@ struct ScopedSpan {
     ScopedSpan(fs_sim* s_, int fam, long launches = 1) : s(s_), id(s_->span_begin(fam)), n(launches) {}
     ~ScopedSpan() { s->span_end(id, n); }
 };
+
+// what the image entries accept without looking at the state: a source of fs_sample by its bits, and a colour range
+bool image_source_ok(int source)
+{
+    if (source >= 0 && source < FS_NFIELDS) return true;
+    if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX) return (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS;
+    if (source >= 0 && (source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
+        const int sel = source & (FS_SAMPLE_STAT - 1), which = sel & ~FS_STAT_RAW;
+        return which >= 0 && which <= FS_STAT_TKE && !((sel & FS_STAT_RAW) && which == FS_STAT_TKE);
+    }
+    return false;
+}
+bool image_range_ok(double vmin, double vmax, double alpha)
+{
+    return std::isfinite(vmin) && std::isfinite(vmax) && vmin < vmax && alpha >= 0.0 && alpha <= 1.0;
+}
+// bytes of one frame of the image log: the views' RGB images one after the other
+size_t image_frame_bytes(const fs_sim* s, const std::vector<ImageView>& views)
+{
+    size_t bytes = 0;
+    for (const ImageView& v : views) {
+        int c, r;
+        fs::image_dims(v.axis, s->W, s->H, s->D, &c, &r);
+        bytes += 3 * (size_t)c * (size_t)r;
+    }
+    return bytes;
+}
 
 template <class T> T host_cbrt(T v);
 template <> float host_cbrt<float>(float v) { return std::cbrt(v); }     // std::cbrt(float), simulation.cpp:295
@@ -353,6 +399,23 @@ struct Engine : EngineBase {
     long probe_gen = -1;                // S->probe_gen they were set up for
     long probe_logged = 0;              // records taken since the ring was cleared or last drained
     std::vector<long> probe_step;       // step number held by each ring slot
+    // slice and projection images (image.h): one allocation holds the value image, the flag image of a slice, the obstacle
+    // silhouette of each axis (valid until obs changes), an RGB staging image and the colour table; the per-step log is a
+    // device ring of img_cap frames x img_frame_bytes (the views' RGB images one after the other)
+    double* img_val = nullptr;          // the allocation's base
+    uint8_t* img_flag = nullptr;
+    uint8_t* img_sil[3] = {nullptr, nullptr, nullptr};
+    bool img_sil_ok[3] = {false, false, false};
+    uint8_t* img_rgb = nullptr;
+    uint8_t* img_table = nullptr;
+    int img_table_n = 0;
+    long img_table_gen = -1;            // S->image_table_gen the device table holds
+    uint8_t* img_ring = nullptr;
+    int img_cap = 0;
+    size_t img_frame_bytes = 0;
+    long img_gen = -1;                  // S->image_gen the ring was set up for
+    long img_logged = 0;                // frames taken since the ring was cleared or last drained
+    std::vector<long> img_step;         // step number held by each ring slot
     // per-body forces and moments (bodies.h): the labels (dense padded int32), what the host keeps of the last labelling, and
     // the per-step log, a device ring of body_cap steps x 2 projections x (body_B + 1) whole-grid records
     int* body_L = nullptr;
@@ -497,6 +560,8 @@ struct Engine : EngineBase {
         if (samp_out) hipFree(samp_out);
         if (probe_idx) hipFree(probe_idx);
         if (probe_ring) hipFree(probe_ring);
+        if (img_val) hipFree(img_val);
+        if (img_ring) hipFree(img_ring);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total, (void*)body_ring })
             if (q) hipFree(q);
         mg.release();
@@ -579,6 +644,7 @@ struct Engine : EngineBase {
         if ((rc = build_clean())) return rc;
         flags_dirty = false;
         bodies_dirty = true;
+        img_sil_ok[0] = img_sil_ok[1] = img_sil_ok[2] = false;
         mg_current = false;
         return FS_OK;
     }
@@ -1458,6 +1524,7 @@ struct Engine : EngineBase {
         if ((rc = flow_stats_config())) return rc;
         if ((rc = ensure_probe_ring())) return rc;
         if ((rc = ensure_body_ring())) return rc;
+        if ((rc = ensure_image_ring())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1546,6 +1613,8 @@ struct Engine : EngineBase {
             return rc;
         // "probe_log": the same state is a record of the probes (one launch, no host synchronisation, the step's own stream)
         if (probe_cap > 0) probe_record();
+        // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
+        if (img_cap > 0 && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -1803,6 +1872,18 @@ struct Engine : EngineBase {
     }
 
     // ---- vortex identification (vortex.h; beyond the reference) and iso-surfaces of any field -------------
+    // the private array the vortex kernel writes, allocated and zeroed at first need
+    int ensure_vort(const char* who)
+    {
+        if (vort) return FS_OK;
+        T* base = nullptr;
+        const hipError_t e = hipMalloc((void**)&base, (size_t)g.n * sizeof(T));
+        if (e != hipSuccess) return fail(FS_ENOMEM, "%s: scratch array of %zu bytes: %s", who, (size_t)g.n * sizeof(T), hipGetErrorString(e));
+        vort = base + g.lead;
+        HIP_TRY(hipMemsetAsync(base, 0, (size_t)g.n * sizeof(T), S->stream));
+        return FS_OK;
+    }
+
     // One field into `vort`.  Collective on slab handles: the stencil reads one plane of each neighbour.
     int vortex_compute(const char* who, int which)
     {
@@ -1813,13 +1894,7 @@ struct Engine : EngineBase {
         if (rc) return rc;
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = halo(arr[slot[f]]))) return rc;
-        if (!vort) {
-            T* base = nullptr;
-            const hipError_t e = hipMalloc((void**)&base, (size_t)g.n * sizeof(T));
-            if (e != hipSuccess) return fail(FS_ENOMEM, "%s: scratch array of %zu bytes: %s", who, (size_t)g.n * sizeof(T), hipGetErrorString(e));
-            vort = base + g.lead;
-            HIP_TRY(hipMemsetAsync(base, 0, (size_t)g.n * sizeof(T), S->stream));
-        }
+        if ((rc = ensure_vort(who))) return rc;
         ScopedSpan sp(S, FAM_VORTEX);
         fs::launch_vortex<T>(S->stream, S->tune, g, sc, which, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], flags, vort);
         return FS_OK;
@@ -2186,24 +2261,23 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int sample(int source, int mode, double* out, long n) override
+    // The array behind a source of fs_sample and of the image entries: a field selector (-> field), FS_ISO_VORTEX |
+    // FS_VORTEX_* (the field is computed first, -> field), or FS_SAMPLE_STAT | sel (the derived field goes into the staging
+    // buffer in the accumulators' layout, which is the fields' pitched one, -> stat).  Both are LEAD-shifted.
+    int resolve_source(const char* who, int source, const T*& field, const double*& stat)
     {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
-        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "fs_sample: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", mode);
-        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
-        const T* field = nullptr;
-        const double* stat = nullptr;
         int rc;
+        field = nullptr;
+        stat = nullptr;
         if (source >= 0 && source < FS_NFIELDS) {
             field = arr[slot[source]];
         } else if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS) {
-            if ((rc = vortex_compute("fs_sample", source & (FS_ISO_VORTEX - 1)))) return rc;
+            if ((rc = vortex_compute(who, source & (FS_ISO_VORTEX - 1)))) return rc;
             field = vort;
         } else if ((source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
-            // the derived field goes into the staging buffer in the accumulators' layout, which is the fields' pitched one
             const int sel = source & (FS_SAMPLE_STAT - 1);
             if ((rc = flow_stats_config())) return rc;
-            if ((rc = flow_stats_check("fs_sample", sel))) return rc;
+            if ((rc = flow_stats_check(who, sel))) return rc;
             if ((rc = need_dense(stat_bytes()))) return rc;
             if (S->flow_stats_n == 0)                    // a raw sum before the first sample: +0.0
                 HIP_TRY(hipMemsetAsync(dense, 0, stat_bytes(), S->stream));
@@ -2212,8 +2286,20 @@ struct Engine : EngineBase {
                                                false, false, (double*)dense);
             stat = (const double*)dense + fs::LEAD;
         } else {
-            return fail(FS_EINVAL, "fs_sample: unknown source %d (a field selector, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", source);
+            return fail(FS_EINVAL, "%s: unknown source %d (a field selector, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", who, source);
         }
+        return FS_OK;
+    }
+
+    int sample(int source, int mode, double* out, long n) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
+        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "fs_sample: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", mode);
+        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
+        const T* field = nullptr;
+        const double* stat = nullptr;
+        int rc = resolve_source("fs_sample", source, field, stat);
+        if (rc) return rc;
         if (n == 0) return FS_OK;
         if (!out) return fail(FS_EINVAL, "fs_sample: null output");
         const T* obs = arr[slot[FS_OBS]];
@@ -2323,6 +2409,214 @@ struct Engine : EngineBase {
                     o[1 + (size_t)k * fs::PROBE_VALUES + j] = all[owner_off[(size_t)k] + (size_t)i * per + j];
         }
         probe_logged = 0;                                // drained
+        return FS_OK;
+    }
+
+    // ---- slice and projection images (image.h; the reference's 2-D viewer does this on the host, gui.py:61-79, 257-295) ----
+    long image_max_pixels() const
+    {
+        const long a = (long)(g.W + 2) * (g.H + 2), b = (long)(g.W + 2) * (g.D + 2), c = (long)(g.H + 2) * (g.D + 2);
+        return std::max(a, std::max(b, c));
+    }
+
+    // the scratch images and the device copy of the colour table, at first need and after fs_image_colormap
+    int ensure_image_scratch()
+    {
+        if (!img_val) {
+            const size_t np = ((size_t)image_max_pixels() + 15) / 16 * 16;
+            uint8_t* base = nullptr;
+            const hipError_t e = hipMalloc((void**)&base, np * 16 + 3 * (size_t)fs::IMG_TABLE_MAX);
+            if (e != hipSuccess) return fail(FS_ENOMEM, "image scratch of %zu bytes: %s", np * 16 + 3 * (size_t)fs::IMG_TABLE_MAX, hipGetErrorString(e));
+            img_val = (double*)base;
+            img_flag = base + 8 * np;
+            for (int a = 0; a < 3; ++a) img_sil[a] = base + (9 + (size_t)a) * np;
+            img_rgb = base + 12 * np;
+            img_table = base + 16 * np;
+            img_sil_ok[0] = img_sil_ok[1] = img_sil_ok[2] = false;
+            img_table_gen = -1;
+        }
+        if (img_table_gen != S->image_table_gen) {
+            const bool own = !S->image_table.empty();
+            img_table_n = own ? (int)(S->image_table.size() / 3) : fs::IMG_DEFAULT_N;
+            HIP_TRY(hipMemcpyAsync(img_table, own ? S->image_table.data() : fs::IMG_DEFAULT_TABLE, 3 * (size_t)img_table_n,
+                                   hipMemcpyHostToDevice, S->stream));
+            HIP_TRY(hipStreamSynchronize(S->stream));    // the handle's table may be replaced by the caller
+            img_table_gen = S->image_table_gen;
+        }
+        return FS_OK;
+    }
+
+    // One value image into img_val and its obstacle flags (-> flag): the kernels of one view.  The arguments are checked.
+    int image_render(const char* who, int source, int kind, int axis, int index, const uint8_t*& flag)
+    {
+        int rc = ensure_flags();                         // obs changed: the silhouettes are stale
+        if (rc) return rc;
+        const T* field = nullptr;
+        const double* stat = nullptr;
+        if ((rc = resolve_source(who, source, field, stat))) return rc;
+        const T* obs = arr[slot[FS_OBS]];
+        if (kind == fs::IMG_SLICE) {
+            if (stat) fs::launch_image_slice<double, T>(S->stream, g, axis, index, stat, obs, img_val, img_flag);
+            else fs::launch_image_slice<T, T>(S->stream, g, axis, index, field, obs, img_val, img_flag);
+            flag = img_flag;
+            return FS_OK;
+        }
+        if (stat) fs::launch_image_project<double>(S->stream, g, kind, axis, stat, img_val, nullptr);
+        else fs::launch_image_project<T>(S->stream, g, kind, axis, field, img_val, nullptr);
+        if (!img_sil_ok[axis]) {                         // the silhouette depends on obs and the axis only
+            fs::launch_image_project<T>(S->stream, g, fs::IMG_ANY, axis, obs, nullptr, img_sil[axis]);
+            img_sil_ok[axis] = true;
+        }
+        flag = img_sil[axis];
+        return FS_OK;
+    }
+
+    int image_args(const char* who, int kind, int axis, int index, int* cols, int* rows)
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "%s: images are taken on a single-GPU handle", who);
+        if (kind < 0 || kind >= fs::IMG_NKINDS) return fail(FS_EINVAL, "%s: unknown kind %d (FS_IMG_SLICE | SUM | MAX | MIN)", who, kind);
+        if (axis < 0 || axis > 2) return fail(FS_EINVAL, "%s: axis %d (0 = x, 1 = y, 2 = z)", who, axis);
+        const int N = axis == 0 ? g.W : axis == 1 ? g.H : g.D;
+        if (index < 0 || index > (kind == fs::IMG_SLICE ? N + 1 : 0))
+            return fail(FS_EINVAL, "%s: index %d (a slice: 0 .. %d; a projection: 0)", who, index, N + 1);
+        int c, r;
+        fs::image_dims(axis, g.W, g.H, g.D, &c, &r);
+        if (cols) *cols = c;
+        if (rows) *rows = r;
+        return FS_OK;
+    }
+
+    int image_values(int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows) override
+    {
+        int c, r;
+        int rc = image_args("fs_image_values", kind, axis, index, &c, &r);
+        if (rc) return rc;
+        if (!image_source_ok(source)) return fail(FS_EINVAL, "fs_image_values: unknown source %d", source);
+        if (cols) *cols = c;
+        if (rows) *rows = r;
+        if (!out) return FS_OK;
+        if (n != (size_t)c * (size_t)r) return fail(FS_EINVAL, "fs_image_values: the image has %d x %d values, the call has room for %zu", c, r, n);
+        if ((rc = ensure_image_scratch())) return rc;
+        const uint8_t* flag = nullptr;
+        {
+            ScopedSpan sp(S, FAM_MISC);
+            if ((rc = image_render("fs_image_values", source, kind, axis, index, flag))) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out, img_val, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int image_rgb(int source, int kind, int axis, int index, double vmin, double vmax, double alpha, uint8_t* out, size_t n_bytes,
+                  int* cols, int* rows) override
+    {
+        int c, r;
+        int rc = image_args("fs_image_rgb", kind, axis, index, &c, &r);
+        if (rc) return rc;
+        if (!image_source_ok(source)) return fail(FS_EINVAL, "fs_image_rgb: unknown source %d", source);
+        if (!image_range_ok(vmin, vmax, alpha)) return fail(FS_EINVAL, "fs_image_rgb: vmin < vmax, both finite, and obstacle_alpha in [0, 1]");
+        if (cols) *cols = c;
+        if (rows) *rows = r;
+        if (!out) return FS_OK;
+        const size_t npix = (size_t)c * (size_t)r;
+        if (n_bytes != 3 * npix) return fail(FS_EINVAL, "fs_image_rgb: the image has %d x %d x 3 bytes, the call has room for %zu", c, r, n_bytes);
+        if ((rc = ensure_image_scratch())) return rc;
+        const uint8_t* flag = nullptr;
+        {
+            ScopedSpan sp(S, FAM_MISC);
+            if ((rc = image_render("fs_image_rgb", source, kind, axis, index, flag))) return rc;
+            fs::launch_image_colour(S->stream, (long)npix, img_val, flag, vmin, vmax, alpha, img_table, img_table_n, img_rgb);
+        }
+        HIP_TRY(hipMemcpyAsync(out, img_rgb, n_bytes, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int image_config() override { return ensure_image_ring(); }
+
+    // (re)allocate and clear the ring after fs_image_views / fs_set_option("image_log"), and set up whatever a view needs, so
+    // that a record in mid-step allocates nothing: the scratch images, the vortex array, the staging of a statistics source
+    int ensure_image_ring()
+    {
+        if (img_gen == S->image_gen) return img_cap > 0 ? ensure_image_scratch() : FS_OK;   // a new colour table
+        if (img_ring) {
+            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued frame may still use what is freed here
+            HIP_TRY(hipFree(img_ring));
+        }
+        img_ring = nullptr;
+        img_cap = 0;
+        img_frame_bytes = 0;
+        img_logged = 0;
+        img_step.clear();
+        img_gen = S->image_gen;
+        if (S->image_views.empty() || S->image_log <= 0) return FS_OK;
+        if (S->comm.active()) return fail(FS_EINVAL, "the image log needs a single-GPU handle");
+        int rc = ensure_image_scratch();
+        if (rc) return rc;
+        size_t bytes = 0;
+        for (const ImageView& v : S->image_views) {
+            int c, r;
+            fs::image_dims(v.axis, g.W, g.H, g.D, &c, &r);
+            bytes += 3 * (size_t)c * (size_t)r;
+            if ((v.source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (rc = ensure_vort("fs_image_views"))) return rc;
+            if ((v.source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT && (rc = need_dense(stat_bytes()))) return rc;
+        }
+        const hipError_t e = hipMalloc((void**)&img_ring, (size_t)S->image_log * bytes);
+        if (e != hipSuccess) return fail(FS_ENOMEM, "image_log: %d frames of %zu bytes: %s", S->image_log, bytes, hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(img_ring, 0, (size_t)S->image_log * bytes, S->stream));
+        img_cap = S->image_log;
+        img_frame_bytes = bytes;
+        img_step.assign((size_t)img_cap, 0);
+        return FS_OK;
+    }
+
+    // one frame of the state as it is now into the next ring slot: every view's kernels, then its colouring
+    int image_record()
+    {
+        uint8_t* dst = img_ring + (size_t)(img_logged % img_cap) * img_frame_bytes;
+        for (const ImageView& v : S->image_views) {
+            int c, r;
+            fs::image_dims(v.axis, g.W, g.H, g.D, &c, &r);
+            const uint8_t* flag = nullptr;
+            ScopedSpan sp(S, FAM_IMAGES);
+            const int rc = image_render("the image log", v.source, v.kind, v.axis, v.index, flag);
+            if (rc) return rc;
+            fs::launch_image_colour(S->stream, (long)c * r, img_val, flag, v.vmin, v.vmax, v.alpha, img_table, img_table_n, dst);
+            dst += 3 * (size_t)c * (size_t)r;
+        }
+        img_step[(size_t)(img_logged++ % img_cap)] = S->steps_total;
+        return FS_OK;
+    }
+
+    int image_sample() override
+    {
+        int rc = ensure_image_ring();
+        if (rc) return rc;
+        if (img_cap == 0) return fail(FS_EINVAL, "fs_image_sample: no views are set (fs_image_views), or option \"image_log\" is 0");
+        return image_record();
+    }
+
+    int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) override
+    {
+        int rc = ensure_image_ring();
+        if (rc) return rc;
+        const long n = img_cap > 0 ? std::min<long>(img_logged, img_cap) : 0;
+        if (n_frames) *n_frames = n;
+        if (n_dropped) *n_dropped = img_logged - n;
+        if (!frames) return FS_OK;                       // sizes only: nothing drained
+        if (max_frames < n) return fail(FS_EINVAL, "fs_image_log: %ld frames retained, room for %ld (pass frames = NULL to ask)", n, max_frames);
+        const long first = img_logged - n;
+        if (n > 0) {                                     // the retained frames are one run of ring slots, or two where it wraps
+            const long start = first % img_cap, run = std::min<long>(n, img_cap - start);
+            HIP_TRY(hipMemcpyAsync(frames, img_ring + (size_t)start * img_frame_bytes, (size_t)run * img_frame_bytes, hipMemcpyDeviceToHost, S->stream));
+            if (run < n)
+                HIP_TRY(hipMemcpyAsync(frames + (size_t)run * img_frame_bytes, img_ring, (size_t)(n - run) * img_frame_bytes,
+                                       hipMemcpyDeviceToHost, S->stream));
+            HIP_TRY(hipStreamSynchronize(S->stream));
+        }
+        if (steps)
+            for (long i = 0; i < n; ++i) steps[i] = img_step[(size_t)((first + i) % img_cap)];
+        img_logged = 0;                                  // drained
         return FS_OK;
     }
 
@@ -2954,6 +3248,23 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
             return fail(FS_EINVAL, "probe_log: %ld records of %zu probes exceed 1 GiB", n, s->probes.size() / 3);
         s->probe_log = (int)n;
         s->probe_gen++;
+    } else if (k == "image_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > 65536) return fail(FS_EINVAL, "image_log: frames kept, 0 (off) .. 65536");
+        if ((size_t)n * image_frame_bytes(s, s->image_views) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "image_log: %ld frames of %zu bytes exceed 1 GiB", n, image_frame_bytes(s, s->image_views));
+        s->image_log = (int)n;
+        s->image_gen++;
+        if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
+            hipSetDevice(s->device);
+            return s->eng->image_config();
+        }
+    } else if (k == "image_every") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "image_every: K >= 1");
+        s->image_every = n;
     } else if (k == "flow_stats") {
         if (v == "off") s->flow_stats = 0;
         else if (v == "mean") s->flow_stats = fs::ST_NMEAN;
@@ -3092,6 +3403,8 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
         if (rc) return rc;
         *out = (n == "body_count") ? b : c;
     }
+    else if (n == "image_views") *out = (int)s->image_views.size();       // views set by fs_image_views
+    else if (n == "image_frame_bytes") *out = (int)image_frame_bytes(s, s->image_views);   // one frame of the image log
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -3521,6 +3834,134 @@ int fs_probe_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_d
     return s->eng->probe_log_fetch(rows, max_rows, n_rows, n_dropped);
 }
 
+// ---- slice and projection images ------------------------------------------------------------------------------
+int fs_image_values(fs_sim* s, int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->image_values(source, kind, axis, index, out, n, cols, rows);
+}
+int fs_image_rgb(fs_sim* s, int source, int kind, int axis, int index, double vmin, double vmax, double obstacle_alpha,
+                 uint8_t* out, size_t n_bytes, int* cols, int* rows)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->image_rgb(source, kind, axis, index, vmin, vmax, obstacle_alpha, out, n_bytes, cols, rows);
+}
+int fs_image_colormap(fs_sim* s, const uint8_t* rgb, int n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (n != 0 && (n < 2 || n > fs::IMG_TABLE_MAX)) return fail(FS_EINVAL, "fs_image_colormap: 2 .. %d triples (0: the built-in table), got %d", fs::IMG_TABLE_MAX, n);
+    if (n > 0 && !rgb) return fail(FS_EINVAL, "fs_image_colormap: null table");
+    if (n == 0) s->image_table.clear();
+    else s->image_table.assign(rgb, rgb + 3 * (size_t)n);
+    s->image_table_gen++;
+    return FS_OK;
+}
+int fs_image_views(fs_sim* s, const int* spec, const double* range, int n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (n < 0 || n > FS_IMAGE_VIEWS_MAX) return fail(FS_EINVAL, "fs_image_views: 0 .. %d views, got %d", FS_IMAGE_VIEWS_MAX, n);
+    if (n > 0 && (!spec || !range)) return fail(FS_EINVAL, "fs_image_views: null views");
+    if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "fs_image_views: images are taken on a single-GPU handle");
+    std::vector<ImageView> views((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        ImageView& v = views[(size_t)k];
+        v.source = spec[4 * k]; v.kind = spec[4 * k + 1]; v.axis = spec[4 * k + 2]; v.index = spec[4 * k + 3];
+        v.vmin = range[3 * k]; v.vmax = range[3 * k + 1]; v.alpha = range[3 * k + 2];
+        if (!image_source_ok(v.source)) return fail(FS_EINVAL, "fs_image_views: view %d: unknown source %d", k, v.source);
+        if (v.kind < 0 || v.kind >= fs::IMG_NKINDS) return fail(FS_EINVAL, "fs_image_views: view %d: unknown kind %d", k, v.kind);
+        if (v.axis < 0 || v.axis > 2) return fail(FS_EINVAL, "fs_image_views: view %d: axis %d (0 = x, 1 = y, 2 = z)", k, v.axis);
+        const int N = v.axis == 0 ? s->W : v.axis == 1 ? s->H : s->D;
+        if (v.index < 0 || v.index > (v.kind == fs::IMG_SLICE ? N + 1 : 0))
+            return fail(FS_EINVAL, "fs_image_views: view %d: index %d (a slice: 0 .. %d; a projection: 0)", k, v.index, N + 1);
+        if (!image_range_ok(v.vmin, v.vmax, v.alpha))
+            return fail(FS_EINVAL, "fs_image_views: view %d: vmin < vmax, both finite, and obstacle_alpha in [0, 1]", k);
+    }
+    if ((size_t)s->image_log * image_frame_bytes(s, views) > ((size_t)1 << 30))
+        return fail(FS_EINVAL, "fs_image_views: %d frames (\"image_log\") of %zu bytes exceed 1 GiB", s->image_log, image_frame_bytes(s, views));
+    s->image_views.swap(views);
+    s->image_gen++;
+    if (s->eng) {
+        hipSetDevice(s->device);
+        return s->eng->image_config();
+    }
+    return FS_OK;
+}
+int fs_image_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->image_sample(); }
+int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->image_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
+}
+
+// An 8-bit RGB, non-interlaced PNG whose one IDAT chunk is a zlib stream of stored deflate blocks: filter type 0 on every
+// scanline, no compression, no zlib dependency; the bytes are a pure function of the pixels.
+int fs_image_png(const uint8_t* rgb, int cols, int rows, const char* path)
+{
+    if (!rgb || !path) return fail(FS_EINVAL, "fs_image_png: null argument");
+    if (cols < 1 || rows < 1 || (double)cols * rows * 3 + rows > 1.0e9) return fail(FS_EINVAL, "fs_image_png: bad size %d x %d", cols, rows);
+    uint32_t crc_table[256];
+    for (uint32_t n = 0; n < 256; ++n) {
+        uint32_t c = n;
+        for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+        crc_table[n] = c;
+    }
+    std::vector<uint8_t> file;
+    auto be32 = [&](uint32_t v) { for (int k = 3; k >= 0; --k) file.push_back((uint8_t)(v >> (8 * k))); };
+    auto chunk = [&](const char* type, const std::vector<uint8_t>& data) {
+        be32((uint32_t)data.size());
+        const size_t from = file.size();
+        file.insert(file.end(), type, type + 4);
+        file.insert(file.end(), data.begin(), data.end());
+        uint32_t c = 0xFFFFFFFFu;
+        for (size_t k = from; k < file.size(); ++k) c = crc_table[(c ^ file[k]) & 0xFF] ^ (c >> 8);
+        be32(c ^ 0xFFFFFFFFu);
+    };
+    static const uint8_t magic[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    file.assign(magic, magic + 8);
+    std::vector<uint8_t> ihdr;
+    for (uint32_t v : { (uint32_t)cols, (uint32_t)rows })
+        for (int k = 3; k >= 0; --k) ihdr.push_back((uint8_t)(v >> (8 * k)));
+    for (uint8_t b : { 8, 2, 0, 0, 0 }) ihdr.push_back(b);      // bit depth 8, colour type 2 (RGB), deflate, filter method 0, no interlace
+    chunk("IHDR", ihdr);
+    // the scanlines, each behind its filter byte 0
+    const size_t line = 3 * (size_t)cols;
+    std::vector<uint8_t> raw((line + 1) * (size_t)rows);
+    for (int r = 0; r < rows; ++r) {
+        raw[(line + 1) * (size_t)r] = 0;
+        memcpy(&raw[(line + 1) * (size_t)r + 1], rgb + line * (size_t)r, line);
+    }
+    uint32_t a = 1, b = 0;                               // Adler-32 of the uncompressed data
+    for (size_t k = 0; k < raw.size();) {
+        const size_t run = std::min<size_t>(raw.size() - k, 5552);
+        for (size_t j = 0; j < run; ++j) { a += raw[k + j]; b += a; }
+        a %= 65521u;
+        b %= 65521u;
+        k += run;
+    }
+    std::vector<uint8_t> idat;
+    idat.push_back(0x78);                                // deflate, 32 KiB window
+    idat.push_back(0x01);                                // no dictionary, fastest; 0x7801 is a multiple of 31
+    for (size_t k = 0; k < raw.size();) {
+        const size_t run = std::min<size_t>(raw.size() - k, 65535);
+        idat.push_back(k + run == raw.size() ? 1 : 0);   // BFINAL, BTYPE = 00 (stored)
+        idat.push_back((uint8_t)(run & 0xFF));
+        idat.push_back((uint8_t)(run >> 8));
+        idat.push_back((uint8_t)(~run & 0xFF));
+        idat.push_back((uint8_t)((~run >> 8) & 0xFF));
+        idat.insert(idat.end(), raw.begin() + (long)k, raw.begin() + (long)(k + run));
+        k += run;
+    }
+    const uint32_t adler = (b << 16) | a;
+    for (int k = 3; k >= 0; --k) idat.push_back((uint8_t)(adler >> (8 * k)));
+    chunk("IDAT", idat);
+    chunk("IEND", std::vector<uint8_t>());
+    FILE* fp = fopen(path, "wb");
+    if (!fp) return fail(FS_EIO, "fs_image_png: cannot open '%s'", path);
+    const bool ok = fwrite(file.data(), 1, file.size(), fp) == file.size();
+    if (fclose(fp) != 0 || !ok) return fail(FS_EIO, "fs_image_png: cannot write '%s'", path);
+    return FS_OK;
+}
+
 int fs_comm_unique_id(void* id_out)
 {
     if (!id_out) return fail(FS_EINVAL, "null id buffer");
@@ -3549,6 +3990,7 @@ int fs_comm_init(fs_sim* s, int rank, int nranks, const void* id)
     if (nranks > 1 && s->D / nranks < 2) return fail(FS_EINVAL, "a slab needs at least 2 planes (two-deep halos), got %d", s->D / nranks);
     if (nranks == 1) return FS_OK;
     if (s->body_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"body_force_log\" is on, and bodies are labelled on a single-GPU handle");
+    if (s->image_log > 0 && !s->image_views.empty()) return fail(FS_EINVAL, "fs_comm_init: the image log is on, and images are taken on a single-GPU handle");
     hipSetDevice(s->device);
     if (s->comm.init(rank, nranks, id)) return fail(FS_ECOMM, "%s", s->comm.last_error());
     if (rank == 0 && !s->quiet)          // one line of provenance for multi-GPU logs

@@ -515,6 +515,78 @@ class Simulation:
         log = {"step": raw[:, 0].astype(np.int64), "values": raw[:, 1:].reshape(n.value, count, _lib.PROBE_VALUES).copy()}
         return (log, dropped.value) if with_dropped else log
 
+    # -- slice and projection images (single GPU) ----------------------------------------------
+    def _image_shape(self, kind, axis, index):
+        cols, rows = C.c_int(), C.c_int()
+        check(self._L.fs_image_values(self._h, _lib.DENS, kind, int(axis), int(index), None, 0, C.byref(cols), C.byref(rows)))
+        return rows.value, cols.value
+
+    def image_values(self, source, kind, axis, index=0):
+        """One value image of the state as it is now (fs_image_values): (rows, cols) float64.  `kind` is "slice" (the
+        stored values at padded index `index` of `axis`), "sum", "max" or "min" (over the interior cells of the axis,
+        in increasing order), or an IMG_* constant; `axis` is 0 (x), 1 (y) or 2 (z); `source` as for sample()."""
+        k = _lib.IMG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        rows, cols = self._image_shape(k, axis, index)
+        out = np.empty((rows, cols), dtype=np.float64)
+        check(self._L.fs_image_values(self._h, int(source), k, int(axis), int(index), out.ctypes.data_as(C.c_void_p), out.size,
+                                      None, None))
+        return out
+
+    def image_rgb(self, source, kind, axis, index=0, vmin=0.0, vmax=1.0, obstacle_alpha=0.0):
+        """The same image through the handle's colour table (fs_image_rgb): (rows, cols, 3) uint8.  Values are clamped
+        to vmin .. vmax, NaN is black, obstacle pixels are darkened by the factor 1 - obstacle_alpha."""
+        k = _lib.IMG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        rows, cols = self._image_shape(k, axis, index)
+        out = np.empty((rows, cols, 3), dtype=np.uint8)
+        check(self._L.fs_image_rgb(self._h, int(source), k, int(axis), int(index), float(vmin), float(vmax),
+                                   float(obstacle_alpha), out.ctypes.data_as(C.c_void_p), out.size, None, None))
+        return out
+
+    def set_colormap(self, table=None):
+        """Sets the colour table (fs_image_colormap): (n, 3) uint8, n = 2 .. 4096; None restores the built-in one, the
+        256 entries of the reference's 2-D viewer."""
+        if table is None:
+            check(self._L.fs_image_colormap(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1, 3)
+        check(self._L.fs_image_colormap(self._h, t.ctypes.data_as(C.c_void_p), t.shape[0]))
+
+    def set_image_views(self, views):
+        """Sets the views of the per-step image log (fs_image_views): a list of up to IMAGE_VIEWS_MAX tuples (source,
+        kind, axis, index, vmin, vmax[, obstacle_alpha]); an empty list turns the log off.  Clears the log."""
+        spec = np.zeros((len(views), 4), dtype=np.intc)
+        rng = np.zeros((len(views), 3), dtype=np.float64)
+        for i, v in enumerate(views):
+            spec[i] = (int(v[0]), _lib.IMG_KINDS[v[1]] if isinstance(v[1], str) else int(v[1]), int(v[2]), int(v[3]))
+            rng[i] = (float(v[4]), float(v[5]), float(v[6]) if len(v) > 6 else 0.0)
+        check(self._L.fs_image_views(self._h, spec.ctypes.data_as(C.c_void_p), rng.ctypes.data_as(C.c_void_p), len(views)))
+        self._image_views = [tuple(int(x) for x in row) for row in spec]
+
+    image_view_count = property(lambda s: s._geti("image_views"))
+    image_frame_bytes = property(lambda s: s._geti("image_frame_bytes"))
+
+    def image_sample(self):
+        """Takes one frame of the image views from the state as it is now (fs_step does so by itself with image_log=N)."""
+        check(self._L.fs_image_sample(self._h))
+
+    def image_log(self, with_dropped=False):
+        """Drains the per-step image log (option image_log=N; fs_image_log): (steps, images) -- steps (F,) int64, and
+        for each view an (F, rows, cols, 3) uint8 array, oldest frame first.  with_dropped=True returns (steps, images,
+        number of frames the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_image_log(self._h, None, None, 0, C.byref(n), C.byref(dropped)))
+        per = self.image_frame_bytes
+        raw = np.zeros((n.value, per), dtype=np.uint8)
+        steps = np.zeros(n.value, dtype=np.int64)
+        check(self._L.fs_image_log(self._h, raw.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p), n.value,
+                                   C.byref(n), C.byref(dropped)))
+        images, at = [], 0
+        for (_, kind, axis, index) in getattr(self, "_image_views", []):
+            rows, cols = self._image_shape(kind, axis, index)
+            images.append(raw[:, at:at + 3 * rows * cols].reshape(n.value, rows, cols, 3).copy())
+            at += 3 * rows * cols
+        return (steps, images, dropped.value) if with_dropped else (steps, images)
+
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()
         check(self._L.fs_time_sweeps(self._h, b, field, prev, a, c, reps, C.byref(ms)))

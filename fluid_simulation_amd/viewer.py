@@ -94,3 +94,29 @@ def surface_pressure(sim, source=_lib.PRESSURE, p_ref=0.0):
         mesh["p"] = p
         mesh["cp"] = 2.0 * (p - float(p_ref)) / denom
     return mesh
+
+
+# the 2-D viewer's colour ranges (gui.py:271-289) and the strength of its obstacle overlay (gui.py:295)
+SLICE_RANGES = {"density": (_lib.DENS, 0.0, 0.01), "v_x": (_lib.VX, -10.0, 10.0), "v_y": (_lib.VY, -1.0, 1.0),
+                "v_z": (_lib.VZ, -1.0, 1.0)}
+SLICE_ALPHA = 0.2
+
+
+def slice_image(sim, field="density", z=None):
+    """The frame the reference's 2-D viewer shows (gui.py:257-295) of a live `Simulation`, rendered on the device: one
+    z-slice of `field` ("density", "v_x", "v_y" or "v_z") through the viewer's colour map and ranges, obstacle cells
+    darkened; (H+2, W+2, 3) uint8.  The default slice is the middle one, (D+2)//2."""
+    source, vmin, vmax = SLICE_RANGES[field]
+    if z is None:
+        z = (sim.depth + 2) // 2
+    return sim.image_rgb(source, "slice", 2, int(z), vmin=vmin, vmax=vmax, obstacle_alpha=SLICE_ALPHA)
+
+
+def write_png(path, rgb):
+    """Writes an (rows, cols, 3) uint8 image as an uncompressed 8-bit RGB PNG (fs_image_png; needs no GPU)."""
+    import ctypes as C
+    import os
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("expected an (rows, cols, 3) image")
+    _lib.check(_lib.lib().fs_image_png(a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], os.fsencode(path)))

@@ -117,6 +117,9 @@ int fs_destroy(fs_sim* s);
  *   "probe_log"   N >= 0 (at most 1048576): keep the last N records of the point probes (fs_set_probes, fs_probe_log); 0 (default) =
  *                 off, and the step launches and allocates nothing for it.  Setting it (re)allocates and clears the log.  May be
  *                 changed at any time.
+ *   "image_log"   N >= 0 (at most 65536): keep the last N frames of the image views (fs_image_views, fs_image_log); 0 (default) =
+ *                 off, and the step launches and allocates nothing for it.  "image_every" K >= 1 (default 1): a frame every
+ *                 Kth step.  Setting "image_log" (re)allocates and clears the log.  May be changed at any time.  Single GPU only.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -234,7 +237,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * "residual_log" records: one launch counted per record, i.e. per solve and point in time -- 12 per step with the log on,
  * 10 where the dead density solve is elided, 0 with it off) "flow_stats" (one launch per sample of the time-averaged flow
  * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off) "body_forces"
- * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off).  Events are recorded on the handle's own stream. */
+ * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off) "images"
+ * (one launch counted per rendered view of the image log, 0 with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -579,6 +583,72 @@ int fs_sample(fs_sim* s, int source, int mode, double* out, long n);
 int fs_set_probes(fs_sim* s, const int* cells_xyz, long n);
 int fs_probe_sample(fs_sim* s);
 int fs_probe_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+
+/* ---- slice and projection images (the frames of the reference's 2-D viewer, gui.py:61-79 and 257-295, which it builds on
+ *      the host from dumped volumes, one z-slice at a time; projections, the log and the PNG writer are beyond it) ----
+ *
+ * IMAGE GEOMETRY.  axis is 0 (x), 1 (y) or 2 (z).  The image spans the padded extents of the other two axes; columns run along
+ * the lower remaining axis, rows along the higher one:
+ *     axis z: cols = w+2, rows = h+2, pixel (r, c) is x = c, y = r
+ *     axis y: cols = w+2, rows = d+2, pixel (r, c) is x = c, z = r
+ *     axis x: cols = h+2, rows = d+2, pixel (r, c) is y = c, z = r
+ * Row 0 comes first in memory, there is no flip: field[frame, slice] as gui.py:272 indexes it.
+ *
+ * THE VALUE IMAGE is fp64, rows * cols; the source's stored values are widened exactly.  With N the interior extent of the
+ * axis and v_k the stored value of the pixel's column at padded index k along it:
+ *     FS_IMG_SLICE   v_index, index = 0 .. N+1.
+ *     FS_IMG_SUM     s = +0.0; for k = 1 .. N (increasing): s = s + v_k.  One rounding per add; interior cells of the axis
+ *                    only, whatever they hold.
+ *     FS_IMG_MAX     m = -inf; for k = 1 .. N: if (v_k > m) m = v_k.  NaN is never taken; of equal values the first stays.
+ *     FS_IMG_MIN     m = +inf; for k = 1 .. N: if (v_k < m) m = v_k.
+ * For SUM, MAX and MIN index must be 0.  The order along the axis is strictly sequential on all three axes: a pixel is a
+ * pure function of its column of cells, and launch shape cannot change a bit.
+ * THE OBSTACLE FLAG of a pixel: SLICE: obs > 0.5 at the slice cell; SUM, MAX, MIN: obs > 0.5 at any cell 1 .. N of the
+ * column (the silhouette).
+ * SOURCES are exactly those of fs_sample: a field selector 0 .. FS_NFIELDS - 1; FS_ISO_VORTEX | FS_VORTEX_* (the field is
+ * computed first); FS_SAMPLE_STAT | sel, with the selectors, FS_STAT_RAW and the errors of fs_flow_stats_field.
+ *
+ * COLOURING.  The handle holds a colour table of n RGB triples, 2 <= n <= 4096 (fs_image_colormap; n = 0 restores the
+ * default).  With vmin < vmax, both finite (else FS_EINVAL), in fp64, every operation rounded once, in this order:
+ *     v NaN: (0, 0, 0);   otherwise   c = v < vmin ? vmin : (v > vmax ? vmax : v),   t = (c - vmin) / (vmax - vmin),
+ *     k = min(n - 1, (int)(t * n)),   rgb = table[k].
+ * If the pixel's obstacle flag is set and obstacle_alpha > 0 (obstacle_alpha in [0, 1], else FS_EINVAL): f = (float)(1.0 -
+ * obstacle_alpha), and each byte b becomes (uint8)((float)b * f) (truncation).  These are the bytes of the 2-D viewer's
+ * apply_cmap followed by overlay_obstacle (gui.py:61-79; checked against numpy 2.2 / matplotlib 3.10, whose Normalize works
+ * in fp64 on float32 input; n = 256, obstacle_alpha = 0.2).
+ * THE DEFAULT TABLE is the 256 triples matplotlib builds for the viewer's seven colour stops (gui.py:38-41): the first is
+ * (255,255,255), entry 127 is (0,190,252), the last (255,0,0).  It is written out in csrc/image.h, not recomputed.
+ *
+ * fs_image_values / fs_image_rgb: one image of the state as it is now, out[rows * cols] doubles / out[rows * cols * 3]
+ * bytes; *cols and *rows (may be NULL) receive the geometry, and out = NULL only reports them.  A wrong size, kind, axis,
+ * index or source is FS_EINVAL.  Single-GPU handles only (slab handles: FS_EINVAL).  They change no field.
+ * fs_image_png writes an 8-bit RGB, non-interlaced PNG: one IDAT chunk whose zlib stream consists of stored deflate blocks
+ * only, filter type 0 on every scanline, correct Adler-32 and CRCs, no zlib dependency; the bytes are a pure function of the
+ * pixels.  Needs neither a handle nor a GPU.
+ *
+ * THE IMAGE LOG.  fs_image_views sets n = 0 .. FS_IMAGE_VIEWS_MAX views: spec[4 k + ..] = {source, kind, axis, index},
+ * range[3 k + ..] = {vmin, vmax, obstacle_alpha}, all validated at the call; it replaces the list and clears the log.  A
+ * FRAME is the views' RGB images one after the other in list order.  Options (fs_set_option, any time): "image_log" = N, 0
+ * (default: off, a step launches and allocates nothing for it) .. 65536 frames kept; "image_every" = K >= 1 (default 1).
+ * Setting "image_log" or the views reallocates and clears the ring; either is FS_EINVAL if N * (bytes of one frame) would
+ * exceed 1 GiB.  fs_step takes a frame at the sample point of the flow statistics and the probes -- after advect(0, dens,
+ * buffer) (simulation.cpp:136), before the frame dump -- when (steps_total - 1) % K == 0, into a device ring on the step's
+ * own stream, without a host synchronisation.  fs_image_sample takes one frame of the state as it is now.
+ * fs_image_log drains the log: frames[i * frame bytes + ..], oldest first, with steps[i] (may be NULL) the steps the handle
+ * had completed; frames = NULL, max_frames and *n_dropped (overwritten frames) are as for fs_force_log.  fs_get_int
+ * "image_frame_bytes" and "image_views" report the frame size and the view count; timing family "images" counts one launch
+ * per rendered view of the log, 0 with the feature off.
+ */
+enum { FS_IMG_SLICE = 0, FS_IMG_SUM = 1, FS_IMG_MAX = 2, FS_IMG_MIN = 3 };
+#define FS_IMAGE_VIEWS_MAX 8
+int fs_image_values(fs_sim* s, int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows);
+int fs_image_rgb(fs_sim* s, int source, int kind, int axis, int index, double vmin, double vmax, double obstacle_alpha,
+                 uint8_t* out, size_t n_bytes, int* cols, int* rows);
+int fs_image_colormap(fs_sim* s, const uint8_t* rgb, int n);      /* n = 0: back to the default table */
+int fs_image_png(const uint8_t* rgb, int cols, int rows, const char* path);   /* needs neither a handle nor a GPU */
+int fs_image_views(fs_sim* s, const int* spec, const double* range, int n);
+int fs_image_sample(fs_sim* s);
+int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

@@ -41,7 +41,18 @@
 //                  mutators use; ghost cells 0 and N+1 allowed), `#` starts a comment; --probe-log FILE records dens, v_x,
 //                  v_y, v_z and the pressure at every probe after every step (option "probe_log" = steps) and writes them
 //                  to FILE as CSV: step,q_0,u_0,v_0,w_0,p_0,q_1,... with the values as %.17g (they read back exactly)
+//   --images DIR   render image views on the device after every step (option "image_log", fs_image_views) and write them as
+//                  uncompressed PNGs DIR/<view number>_<step>.png (fs_image_png); --image-every K takes every Kth step
+//                  (steps 1, K+1, ...); --image-view SRC:KIND:AXIS:INDEX:VMIN:VMAX[:ALPHA] (repeatable, up to
+//                  FS_IMAGE_VIEWS_MAX) replaces the default views -- SRC density|v_x|v_y|v_z|obs|pressure or a source
+//                  selector as a number, KIND slice|sum|max|min, AXIS x|y|z, INDEX the padded slice index (0 for a
+//                  projection), ALPHA the darkening of obstacle pixels (default 0.2).  Default views: density 0..0.01 and
+//                  v_x -10..10 at the middle z-slice (D+2)/2, the 2-D viewer's frames (gui.py:271-279).  The ring holds the
+//                  run's frames where they fit 256 MiB and is drained at the end; a longer run is driven step by step
+//                  (fs_run_one, frame dumps through fs_dump_frame, without run()'s console lines) and the ring is drained
+//                  whenever it is full.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -49,6 +60,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "../include/fluidsim.h"
 
@@ -254,6 +267,64 @@ int write_probes(fs_sim* sim, const char* path, long nprobes)
     return ok ? 0 : 1;
 }
 
+// one view of --image-view: SRC:KIND:AXIS:INDEX:VMIN:VMAX[:ALPHA] -> spec[4], range[3]
+bool parse_view(const char* text, int* spec, double* range)
+{
+    std::vector<std::string> part;
+    std::string t = text;
+    for (size_t at = 0;;) {
+        const size_t next = t.find(':', at);
+        part.push_back(t.substr(at, next == std::string::npos ? std::string::npos : next - at));
+        if (next == std::string::npos) break;
+        at = next + 1;
+    }
+    if (part.size() != 6 && part.size() != 7) return false;
+    static const char* const src[] = { "density", "v_x", "v_y", "v_z", "obs", "pressure" };
+    static const char* const kind[] = { "slice", "sum", "max", "min" };
+    static const char* const axis[] = { "x", "y", "z" };
+    auto pick = [](const std::string& p, const char* const* names, int n, int* out) {
+        for (int k = 0; k < n; ++k)
+            if (p == names[k]) { *out = k; return true; }
+        char* end = nullptr;
+        *out = (int)strtol(p.c_str(), &end, 10);
+        return !p.empty() && *end == 0;
+    };
+    if (!pick(part[0], src, 6, &spec[0]) || !pick(part[1], kind, 4, &spec[1]) || !pick(part[2], axis, 3, &spec[2])) return false;
+    char* end = nullptr;
+    spec[3] = (int)strtol(part[3].c_str(), &end, 10);
+    if (part[3].empty() || *end) return false;
+    range[2] = 0.2;
+    for (size_t k = 4; k < part.size(); ++k) {
+        range[k - 4] = strtod(part[k].c_str(), &end);
+        if (part[k].empty() || *end) return false;
+    }
+    return true;
+}
+
+// drains the image log into DIR/<view number>_<step>.png
+int write_images(fs_sim* sim, const std::string& dir, const std::vector<int>& spec)
+{
+    long n = 0, dropped = 0;
+    int frame_bytes = 0;
+    if (fs_image_log(sim, nullptr, nullptr, 0, &n, &dropped) || fs_get_int(sim, "image_frame_bytes", &frame_bytes)) return 1;
+    if (n == 0) return 0;
+    std::vector<uint8_t> frames((size_t)n * (size_t)frame_bytes);
+    std::vector<long> steps((size_t)n);
+    if (fs_image_log(sim, frames.data(), steps.data(), n, &n, &dropped)) return 1;
+    if (dropped) fprintf(stderr, "simulation.out: %ld image frames were overwritten before they were written\n", dropped);
+    for (long i = 0; i < n; ++i) {
+        size_t at = (size_t)i * (size_t)frame_bytes;
+        for (size_t v = 0; v < spec.size() / 4; ++v) {
+            int cols = 0, rows = 0;
+            if (fs_image_values(sim, spec[4 * v], spec[4 * v + 1], spec[4 * v + 2], spec[4 * v + 3], nullptr, 0, &cols, &rows)) return 1;
+            const std::string path = dir + "/" + std::to_string(v) + "_" + std::to_string(steps[(size_t)i]) + ".png";
+            if (fs_image_png(&frames[at], cols, rows, path.c_str())) return 1;
+            at += 3 * (size_t)cols * (size_t)rows;
+        }
+    }
+    return 0;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "simulation.out: %s: %s\n", what, fs_last_error());
@@ -273,6 +344,11 @@ int main(int argc, char** argv)
     bool stl_given = false, json = false;
     std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir, probes_path, probe_log_path, body_forces_path;
     bool mean_moments = false;
+    std::string images_dir;
+    long image_every = 1;
+    int dump_every = 1;
+    std::vector<int> view_spec;
+    std::vector<double> view_range;
     std::vector<std::pair<std::string, std::string>> options;
 
     auto apply = [&](const std::string& key, const char* val) -> bool {
@@ -283,7 +359,17 @@ int main(int argc, char** argv)
         if (key == "dt") { dt = (float)atof(val); return true; }
         if (key == "diff") { diff = (float)atof(val); return true; }
         if (key == "stl") { stl_given = true; if (strcmp(val, "none") != 0) stls.push_back(parse_stl(val)); return true; }
-        if (key == "dump-every") { options.push_back({ "dump_every", val }); return true; }
+        if (key == "dump-every") { dump_every = atoi(val); options.push_back({ "dump_every", val }); return true; }
+        if (key == "images") { images_dir = val; return true; }
+        if (key == "image-every") { image_every = atol(val); return image_every >= 1; }
+        if (key == "image-view") {
+            int sp[4];
+            double rg[3];
+            if (!parse_view(val, sp, rg)) return false;
+            view_spec.insert(view_spec.end(), sp, sp + 4);
+            view_range.insert(view_range.end(), rg, rg + 3);
+            return true;
+        }
         if (key == "dump-dir") { options.push_back({ "dump_dir", val }); return true; }
         if (key == "precision") { options.push_back({ "precision", val }); return true; }
         if (key == "solver") { options.push_back({ "solver", val }); return true; }
@@ -305,7 +391,8 @@ int main(int argc, char** argv)
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
-                                        "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin" };
+                                        "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
+                                        "image-view" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -345,6 +432,25 @@ int main(int argc, char** argv)
     if (!probe_log_path.empty()) options.push_back({ "probe_log", std::to_string(iter) });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
+    bool stepwise = false;                               // --images: the run's frames do not fit the ring
+    long image_ring = 0;
+    if (!images_dir.empty()) {
+        if (view_spec.empty()) {                         // the 2-D viewer's density and v_x frames (gui.py:271-279)
+            const int mid = (depth + 2) / 2;
+            view_spec = { FS_DENS, FS_IMG_SLICE, 2, mid, FS_VX, FS_IMG_SLICE, 2, mid };
+            view_range = { 0.0, 0.01, 0.2, -10.0, 10.0, 0.2 };
+        }
+        mkdir(images_dir.c_str(), 0777);
+        if (fs_image_views(sim, view_spec.data(), view_range.data(), (int)(view_spec.size() / 4))) return die("fs_image_views");
+        int frame_bytes = 0;
+        if (fs_get_int(sim, "image_frame_bytes", &frame_bytes)) return die("image_frame_bytes");
+        const long wanted = iter > 0 ? (iter - 1) / image_every + 1 : 0;
+        const long room = std::max(1L, std::min(65536L, (256L << 20) / std::max(1, frame_bytes)));
+        image_ring = std::max(1L, std::min(wanted, room));
+        stepwise = wanted > room;
+        if (fs_set_option(sim, "image_every", std::to_string(image_every).c_str())) return die("image_every");
+        if (fs_set_option(sim, "image_log", std::to_string(image_ring).c_str())) return die("image_log");
+    }
     for (const Stl& s : stls) {
         int rc = fs_load_stl(sim, s.path.c_str(), s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], s.v[5], s.v[6], nullptr);
         if (rc != FS_OK && rc != FS_EIO) return die("fs_load_stl");   // unreadable STL: carry on with an empty tunnel
@@ -356,13 +462,25 @@ int main(int argc, char** argv)
             if (resume_field(sim, resume_dir, names[k], which[k])) return 1;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    if (fs_run(sim)) return die("fs_run");                              // simulation.cpp:448
+    if (!stepwise) {
+        if (fs_run(sim)) return die("fs_run");                          // simulation.cpp:448
+    } else {
+        for (int i = 0; i < iter; ++i) {
+            if (fs_run_one(sim)) return die("fs_run_one");
+            if (dump_every > 0 && (i + 1) % dump_every == 0 && fs_dump_frame(sim)) return die("fs_dump_frame");
+            long kept = 0;
+            if (fs_image_log(sim, nullptr, nullptr, 0, &kept, nullptr)) return die("fs_image_log");
+            if (kept == image_ring && write_images(sim, images_dir, view_spec)) return die("writing the images");
+        }
+        if (dump_every == -1 && fs_dump_frame(sim)) return die("fs_dump_frame");
+    }
     if (fs_sync(sim)) return die("fs_sync");
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
     if (!body_forces_path.empty() && write_body_forces(sim, body_forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_body_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
+    if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
     int mean_samples = 0;
     if (!mean_dir.empty()) {
         if (fs_get_int(sim, "flow_stats_samples", &mean_samples)) return die("flow_stats_samples");
