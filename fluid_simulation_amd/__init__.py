@@ -7,7 +7,8 @@ from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_
                    STAT_MEAN_DENS, STAT_MEAN_P, STAT_MEAN_VX, STAT_MEAN_VY, STAT_MEAN_VZ, STAT_NAMES, STAT_PP, STAT_RAW, STAT_TKE,
                    STAT_UU, STAT_UV, STAT_UW, STAT_VV, STAT_VW, STAT_WW, ISO_VORTEX, VORTEX_NAMES, VORTEX_Q, VORTEX_W2, VORTEX_WX,
                    VORTEX_WY, VORTEX_WZ, PROBE_MAX, PROBE_NAMES, PROBE_VALUES, SAMPLE_FLUID, SAMPLE_LINEAR, SAMPLE_NEAREST,
-                   SAMPLE_STAT, IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN, IMAGE_VIEWS_MAX, BODY_COLS, BODY_INFO_COLS, BODY_LOG_COLS, BODY_MAX, FluidsimError)
+                   SAMPLE_STAT, IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN, IMAGE_VIEWS_MAX, TRACER_ALIVE, TRACER_EMITTERS_MAX,
+                   TRACER_FRAME_BYTES, TRACER_FREE, TRACER_HIT, TRACER_OUT, TRACER_STATUS_NAMES, BODY_COLS, BODY_INFO_COLS, BODY_LOG_COLS, BODY_MAX, FluidsimError)
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
                          solve_reduction, BODY_INFO_DTYPE, BODY_LOG_DTYPE, pressure_moment, shift_moment)
 
@@ -21,4 +22,6 @@ __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_for
            "VORTEX_WX", "VORTEX_WY", "VORTEX_WZ", "VORTEX_W2", "VORTEX_Q", "VORTEX_NAMES", "ISO_VORTEX",
            "SAMPLE_NEAREST", "SAMPLE_LINEAR", "SAMPLE_FLUID", "SAMPLE_STAT", "PROBE_MAX", "PROBE_VALUES", "PROBE_NAMES",
            "IMG_SLICE", "IMG_SUM", "IMG_MAX", "IMG_MIN", "IMAGE_VIEWS_MAX",
+           "TRACER_FREE", "TRACER_ALIVE", "TRACER_OUT", "TRACER_HIT", "TRACER_STATUS_NAMES", "TRACER_EMITTERS_MAX",
+           "TRACER_FRAME_BYTES",
            "DENS", "VX", "VY", "VZ", "OBS", "PRESSURE", "DIVERGENCE", "VX_PREV", "VY_PREV", "VZ_PREV", "BUFFER"]

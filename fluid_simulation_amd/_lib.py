@@ -47,6 +47,11 @@ PROBE_NAMES = ["dens", "v_x", "v_y", "v_z", "pressure"]
 IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN = range(4)
 IMG_KINDS = {"slice": IMG_SLICE, "sum": IMG_SUM, "max": IMG_MAX, "min": IMG_MIN}
 IMAGE_VIEWS_MAX = 8     # FS_IMAGE_VIEWS_MAX: views fs_image_views takes
+# FS_TRACER_*: the status word of a tracer slot; the emitters fs_tracer_emitters takes; bytes per slot of a snapshot frame
+TRACER_FREE, TRACER_ALIVE, TRACER_OUT, TRACER_HIT = range(4)
+TRACER_STATUS_NAMES = ["free", "alive", "out", "hit"]
+TRACER_EMITTERS_MAX = 4096
+TRACER_FRAME_BYTES = 28
 
 
 class FluidsimError(RuntimeError):
@@ -126,6 +131,14 @@ _SIGNATURES = {
     "fs_image_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fs_image_sample": (C.c_int, [C.c_void_p]),
     "fs_image_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_tracer_seed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
+    "fs_tracer_emitters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long]),
+    "fs_tracer_clear": (C.c_int, [C.c_void_p]),
+    "fs_tracer_advance": (C.c_int, [C.c_void_p]),
+    "fs_tracer_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]),
+    "fs_tracer_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]),
+    "fs_tracer_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long),
+                                C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

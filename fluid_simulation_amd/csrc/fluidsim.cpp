@@ -18,6 +18,7 @@
 #include "forces.h"
 #include "bodies.h"
 #include "image.h"
+#include "tracers.h"
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
@@ -66,8 +67,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -133,6 +134,13 @@ struct EngineBase {
     virtual int image_config() = 0;            // apply fs_image_views / fs_set_option("image_log"): allocate or free, clear
     virtual int image_sample() = 0;
     virtual int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
+    virtual int tracer_config() = 0;           // apply fs_set_option("tracers") / ("tracer_log"): allocate or free, clear
+    virtual int tracer_seed(const double* xyz, long n) = 0;
+    virtual int tracer_clear() = 0;
+    virtual int tracer_advance() = 0;
+    virtual int tracer_fetch(double* xyz, int32_t* meta, long max, long* n) = 0;
+    virtual int tracer_sample(int source, int mode, double* out, long n) = 0;
+    virtual int tracer_log_fetch(double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
 };
 
 // one view of the image log (fs_image_views)
@@ -220,6 +228,15 @@ struct fs_sim {
     long image_gen = 0;          // bumped by fs_image_views and fs_set_option("image_log"): the ring is set up anew, the log is cleared
     std::vector<uint8_t> image_table;   // fs_image_colormap: n RGB triples; empty = the built-in table
     long image_table_gen = 0;    // bumped by fs_image_colormap
+    int tracers = 0;             // "tracers": slots of the tracer pool, 0 = off
+    long tracer_gen = 0;         // bumped by fs_set_option("tracers"): pool and log are set up anew and cleared
+    int tracer_log = 0;          // "tracer_log": snapshot frames the tracer log keeps, 0 = off
+    long tracer_log_gen = 0;     // bumped by fs_set_option("tracer_log"): the ring is set up anew, the log is cleared
+    long tracer_every = 1;       // "tracer_every": fs_step takes a snapshot when (steps_total - 1) % tracer_every == 0
+    long tracer_seeded = 0;      // particles ever seeded or released since the pool was cleared: the next goes into slot seeded % C
+    std::vector<double> tracer_emit;   // fs_tracer_emitters: x, y, z per emitter
+    long tracer_emit_every = 1;  // fs_step releases one particle per emitter when (steps_total - 1) % tracer_emit_every == 0
+    long tracer_emit_gen = 0;    // bumped by fs_tracer_emitters
     long dump_frames = 0;
     fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
     // result of the last fs_streamlines call
@@ -416,6 +433,20 @@ struct Engine : EngineBase {
     long img_gen = -1;                  // S->image_gen the ring was set up for
     long img_logged = 0;                // frames taken since the ring was cleared or last drained
     std::vector<long> img_step;         // step number held by each ring slot
+    // tracer particles (tracers.h): the pool (positions as the sampler's point list, four meta words per slot), the emitters'
+    // points, and the snapshot log, a device ring of tr_log_cap frames (all position frames, then all status frames)
+    double* tr_xyz = nullptr;
+    int* tr_meta = nullptr;
+    int tr_cap = 0;                     // slots allocated: S->tracers once set up
+    long tr_gen = -1;                   // S->tracer_gen the pool was set up for
+    double* tr_emit = nullptr;          // FS_TRACER_EMITTERS_MAX points, allocated with the pool
+    long tr_emit_gen = -1;              // S->tracer_emit_gen the device list holds
+    double* tr_out = nullptr;           // fs_tracer_sample: one value per slot, allocated at the first call
+    double* tr_ring = nullptr;
+    int tr_log_cap = 0;
+    long tr_log_gen = -1;               // S->tracer_log_gen the ring was set up for
+    long tr_logged = 0;                 // frames taken since the ring was cleared or last drained
+    std::vector<long> tr_step;          // step number held by each ring slot
     // per-body forces and moments (bodies.h): the labels (dense padded int32), what the host keeps of the last labelling, and
     // the per-step log, a device ring of body_cap steps x 2 projections x (body_B + 1) whole-grid records
     int* body_L = nullptr;
@@ -562,6 +593,11 @@ struct Engine : EngineBase {
         if (probe_ring) hipFree(probe_ring);
         if (img_val) hipFree(img_val);
         if (img_ring) hipFree(img_ring);
+        if (tr_xyz) hipFree(tr_xyz);
+        if (tr_meta) hipFree(tr_meta);
+        if (tr_emit) hipFree(tr_emit);
+        if (tr_out) hipFree(tr_out);
+        if (tr_ring) hipFree(tr_ring);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total, (void*)body_ring })
             if (q) hipFree(q);
         mg.release();
@@ -1525,6 +1561,7 @@ struct Engine : EngineBase {
         if ((rc = ensure_probe_ring())) return rc;
         if ((rc = ensure_body_ring())) return rc;
         if ((rc = ensure_image_ring())) return rc;
+        if ((rc = ensure_tracers())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
@@ -1615,6 +1652,10 @@ struct Engine : EngineBase {
         if (probe_cap > 0) probe_record();
         // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
         if (img_cap > 0 && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
+        // "tracers": the particles move through the same state, the emitters release, a snapshot is taken (one launch, no host
+        // synchronisation, the step's own stream)
+        if (tr_cap > 0)
+            tracer_pass((S->steps_total - 1) % S->tracer_emit_every == 0, (S->steps_total - 1) % S->tracer_every == 0);
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
@@ -2291,25 +2332,249 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int sample(int source, int mode, double* out, long n) override
+    // `source` in `mode` at the n device points `pts` into the device array `vals`, copied to `out`: fs_sample on the kept
+    // points, fs_tracer_sample on the pool's positions.  The caller has checked n against its point count.
+    int sample_at(const char* who, int source, int mode, const double* pts, double* vals, double* out, long n)
     {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
-        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "fs_sample: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", mode);
-        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
+        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "%s: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", who, mode);
         const T* field = nullptr;
         const double* stat = nullptr;
-        int rc = resolve_source("fs_sample", source, field, stat);
+        int rc = resolve_source(who, source, field, stat);
         if (rc) return rc;
         if (n == 0) return FS_OK;
-        if (!out) return fail(FS_EINVAL, "fs_sample: null output");
+        if (!out) return fail(FS_EINVAL, "%s: null output", who);
         const T* obs = arr[slot[FS_OBS]];
         {
             ScopedSpan sp(S, FAM_MISC);
-            if (stat) fs::launch_sample<double, T>(S->stream, g, mode, n, samp_pts, stat, obs, samp_out);
-            else fs::launch_sample<T, T>(S->stream, g, mode, n, samp_pts, field, obs, samp_out);
+            if (stat) fs::launch_sample<double, T>(S->stream, g, mode, n, pts, stat, obs, vals);
+            else fs::launch_sample<T, T>(S->stream, g, mode, n, pts, field, obs, vals);
         }
-        HIP_TRY(hipMemcpyAsync(out, samp_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipMemcpyAsync(out, vals, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int sample(int source, int mode, double* out, long n) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
+        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
+        return sample_at("fs_sample", source, mode, samp_pts, samp_out, out, n);
+    }
+
+    // ---- tracer particles (tracers.h; beyond the reference) ---------------------------------------------
+    double* tracer_frame_xyz(long f) const { return tr_ring + (size_t)f * 3 * (size_t)tr_cap; }
+    int* tracer_frame_status(long f) const { return (int*)(tr_ring + (size_t)tr_log_cap * 3 * (size_t)tr_cap) + (size_t)f * (size_t)tr_cap; }
+
+    int tracer_config() override { return ensure_tracers(); }
+
+    // (re)allocate and clear the pool after fs_set_option("tracers") and the ring after that or ("tracer_log"); upload the
+    // emitters after fs_tracer_emitters, so that an advance in mid-step allocates and copies nothing
+    int ensure_tracers()
+    {
+        if (tr_gen != S->tracer_gen) {
+            if (tr_xyz) {
+                HIP_TRY(hipStreamSynchronize(S->stream));    // a queued advance may still use what is freed here
+                HIP_TRY(hipFree(tr_xyz));
+                HIP_TRY(hipFree(tr_meta));
+                HIP_TRY(hipFree(tr_emit));
+                if (tr_out) HIP_TRY(hipFree(tr_out));
+            }
+            tr_xyz = tr_emit = tr_out = nullptr;
+            tr_meta = nullptr;
+            tr_cap = 0;
+            tr_emit_gen = -1;
+            tr_log_gen = -1;                             // the frames are C slots wide: the ring goes with the pool
+            S->tracer_seeded = 0;
+            tr_gen = S->tracer_gen;
+            if (S->tracers > 0) {
+                if (S->comm.active()) return fail(FS_EINVAL, "tracers need a single-GPU handle");
+                const size_t C = (size_t)S->tracers;
+                hipError_t e = hipMalloc((void**)&tr_xyz, C * 3 * sizeof(double));
+                if (e == hipSuccess) e = hipMalloc((void**)&tr_meta, C * fs::TRACER_META * sizeof(int));
+                if (e == hipSuccess) e = hipMalloc((void**)&tr_emit, (size_t)FS_TRACER_EMITTERS_MAX * 3 * sizeof(double));
+                if (e != hipSuccess) {                   // the option goes back to off: capacity and entries agree, a later set tries again
+                    if (tr_xyz) hipFree(tr_xyz);
+                    if (tr_meta) hipFree(tr_meta);
+                    tr_xyz = nullptr;
+                    tr_meta = nullptr;
+                    S->tracers = 0;
+                    return fail(FS_ENOMEM, "tracers: %zu slots: %s (the option is 0 again)", C, hipGetErrorString(e));
+                }
+                HIP_TRY(hipMemsetAsync(tr_xyz, 0, C * 3 * sizeof(double), S->stream));
+                HIP_TRY(hipMemsetAsync(tr_meta, 0, C * fs::TRACER_META * sizeof(int), S->stream));   // every slot FREE
+                tr_cap = S->tracers;
+            }
+        }
+        if (tr_log_gen != S->tracer_log_gen || (tr_cap == 0 && tr_ring)) {
+            if (tr_ring) {
+                HIP_TRY(hipStreamSynchronize(S->stream));
+                HIP_TRY(hipFree(tr_ring));
+            }
+            tr_ring = nullptr;
+            tr_log_cap = 0;
+            tr_logged = 0;
+            tr_step.clear();
+            tr_log_gen = S->tracer_log_gen;
+            if (tr_cap > 0 && S->tracer_log > 0) {
+                const size_t bytes = (size_t)S->tracer_log * (size_t)tr_cap * fs::TRACER_FRAME_BYTES;
+                const hipError_t e = hipMalloc((void**)&tr_ring, bytes);
+                if (e != hipSuccess) {                   // likewise: the log is off until the option is set again
+                    const int frames = S->tracer_log;
+                    S->tracer_log = 0;
+                    return fail(FS_ENOMEM, "tracer_log: %d frames of %d slots: %s (the option is 0 again)", frames, tr_cap, hipGetErrorString(e));
+                }
+                HIP_TRY(hipMemsetAsync(tr_ring, 0, bytes, S->stream));
+                tr_log_cap = S->tracer_log;
+                tr_step.assign((size_t)tr_log_cap, 0);
+            }
+        }
+        if (tr_cap > 0 && tr_emit_gen != S->tracer_emit_gen) {
+            if (!S->tracer_emit.empty()) {
+                HIP_TRY(hipMemcpyAsync(tr_emit, S->tracer_emit.data(), S->tracer_emit.size() * sizeof(double), hipMemcpyHostToDevice, S->stream));
+                HIP_TRY(hipStreamSynchronize(S->stream));    // the host list may change before the copy has run
+            }
+            tr_emit_gen = S->tracer_emit_gen;
+        }
+        return FS_OK;
+    }
+
+    // one advance: the move of every ALIVE particle, the emitters' release (if `release`), a snapshot frame (if `snapshot`
+    // and the log is on).  One launch; the slot cursor is the host's.
+    void tracer_pass(bool release, bool snapshot)
+    {
+        fs::TracerPass pass;
+        pass.C = tr_cap;
+        pass.xyz = tr_xyz;
+        pass.meta = tr_meta;
+        pass.k[0] = (double)S->dt * (double)S->W;        // simulation.cpp:384-386, exact in fp64
+        pass.k[1] = (double)S->dt * (double)S->H;
+        pass.k[2] = (double)S->dt * (double)S->D;
+        pass.emit = tr_emit;
+        pass.n_emit = release ? (int)(S->tracer_emit.size() / 3) : 0;
+        pass.first = (int)(S->tracer_seeded % tr_cap);
+        pass.born = (int)S->steps_total;
+        const bool frame = snapshot && tr_log_cap > 0;
+        pass.frame_xyz = frame ? tracer_frame_xyz(tr_logged % tr_log_cap) : nullptr;
+        pass.frame_status = frame ? tracer_frame_status(tr_logged % tr_log_cap) : nullptr;
+        {
+            ScopedSpan sp(S, FAM_TRACERS);
+            fs::launch_tracer_advance<T>(S->stream, g, pass, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], arr[slot[FS_OBS]]);
+        }
+        S->tracer_seeded += pass.n_emit;
+        if (frame) tr_step[(size_t)(tr_logged++ % tr_log_cap)] = S->steps_total;
+    }
+
+    int tracer_need(const char* who)
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "%s: tracers need a single-GPU handle", who);
+        int rc = ensure_tracers();
+        if (rc) return rc;
+        if (tr_cap == 0) return fail(FS_EINVAL, "%s: option \"tracers\" is 0", who);
+        return FS_OK;
+    }
+
+    int tracer_advance() override
+    {
+        int rc = tracer_need("fs_tracer_advance");
+        if (rc) return rc;
+        tracer_pass(true, true);
+        return FS_OK;
+    }
+
+    int tracer_seed(const double* xyz, long n) override
+    {
+        int rc = tracer_need("fs_tracer_seed");
+        if (rc) return rc;
+        if (n == 0) return FS_OK;
+        // the j-th particle ever seeded goes into slot j % C: of more than C only the last C remain
+        const long C = tr_cap, skip = n > C ? n - C : 0, m = n - skip;
+        const long first = (S->tracer_seeded + skip) % C, run = std::min<long>(m, C - first);
+        std::vector<int32_t> meta((size_t)m * fs::TRACER_META);
+        for (long j = 0; j < m; ++j) {
+            int32_t* w = &meta[(size_t)j * fs::TRACER_META];
+            w[0] = fs::TRACER_ALIVE; w[1] = -1; w[2] = (int32_t)S->steps_total; w[3] = 0;
+        }
+        const double* src = xyz + 3 * skip;
+        HIP_TRY(hipMemcpyAsync(tr_xyz + 3 * first, src, (size_t)run * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
+        HIP_TRY(hipMemcpyAsync(tr_meta + fs::TRACER_META * first, meta.data(), (size_t)run * fs::TRACER_META * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+        if (m > run) {
+            HIP_TRY(hipMemcpyAsync(tr_xyz, src + 3 * run, (size_t)(m - run) * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
+            HIP_TRY(hipMemcpyAsync(tr_meta, meta.data() + (size_t)run * fs::TRACER_META, (size_t)(m - run) * fs::TRACER_META * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, S->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(S->stream));        // `xyz` may be freed by the caller
+        S->tracer_seeded += n;
+        return FS_OK;
+    }
+
+    int tracer_clear() override
+    {
+        int rc = tracer_need("fs_tracer_clear");
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(tr_xyz, 0, (size_t)tr_cap * 3 * sizeof(double), S->stream));
+        HIP_TRY(hipMemsetAsync(tr_meta, 0, (size_t)tr_cap * fs::TRACER_META * sizeof(int), S->stream));
+        S->tracer_seeded = 0;
+        tr_logged = 0;
+        return FS_OK;
+    }
+
+    int tracer_fetch(double* xyz, int32_t* meta, long max, long* n) override
+    {
+        int rc = tracer_need("fs_tracer_fetch");
+        if (rc) return rc;
+        const long count = std::min<long>(S->tracer_seeded, tr_cap);
+        if (n) *n = count;
+        if (!xyz && !meta) return FS_OK;
+        if (max < count) return fail(FS_EINVAL, "fs_tracer_fetch: %ld particles, room for %ld (pass both arrays NULL to ask)", count, max);
+        if (count == 0) return FS_OK;
+        if (xyz) HIP_TRY(hipMemcpyAsync(xyz, tr_xyz, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        if (meta) HIP_TRY(hipMemcpyAsync(meta, tr_meta, (size_t)count * fs::TRACER_META * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int tracer_sample(int source, int mode, double* out, long n) override
+    {
+        int rc = tracer_need("fs_tracer_sample");
+        if (rc) return rc;
+        const long count = std::min<long>(S->tracer_seeded, tr_cap);
+        if (n != count) return fail(FS_EINVAL, "fs_tracer_sample: the pool holds %ld particles, the call has room for %ld", count, n);
+        if (!tr_out && n > 0 && out) {
+            const hipError_t e = hipMalloc((void**)&tr_out, (size_t)tr_cap * sizeof(double));
+            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_tracer_sample: %d values: %s", tr_cap, hipGetErrorString(e));
+        }
+        return sample_at("fs_tracer_sample", source, mode, tr_xyz, tr_out, out, n);
+    }
+
+    int tracer_log_fetch(double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_tracer_log: tracers need a single-GPU handle");
+        int rc = ensure_tracers();
+        if (rc) return rc;
+        const long n = tr_log_cap > 0 ? std::min<long>(tr_logged, tr_log_cap) : 0;
+        if (n_frames) *n_frames = n;
+        if (n_dropped) *n_dropped = tr_logged - n;
+        if (!xyz && !status) return FS_OK;
+        if (max_frames < n) return fail(FS_EINVAL, "fs_tracer_log: %ld frames retained, room for %ld (pass both arrays NULL to ask)", n, max_frames);
+        const long first = tr_logged - n;
+        if (n > 0) {
+            const long start = first % tr_log_cap, run = std::min<long>(n, tr_log_cap - start);
+            const size_t px = (size_t)tr_cap * 3, ps = (size_t)tr_cap;   // elements of one frame
+            if (xyz) {
+                HIP_TRY(hipMemcpyAsync(xyz, tracer_frame_xyz(start), (size_t)run * px * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+                if (n > run)
+                    HIP_TRY(hipMemcpyAsync(xyz + (size_t)run * px, tracer_frame_xyz(0), (size_t)(n - run) * px * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+            }
+            if (status) {
+                HIP_TRY(hipMemcpyAsync(status, tracer_frame_status(start), (size_t)run * ps * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+                if (n > run)
+                    HIP_TRY(hipMemcpyAsync(status + (size_t)run * ps, tracer_frame_status(0), (size_t)(n - run) * ps * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(S->stream));
+        }
+        if (steps)
+            for (long i = 0; i < n; ++i) steps[i] = tr_step[(size_t)((first + i) % tr_log_cap)];
+        tr_logged = 0;                                   // drained
         return FS_OK;
     }
 
@@ -3260,6 +3525,29 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
             hipSetDevice(s->device);
             return s->eng->image_config();
         }
+    } else if (k == "tracers" || k == "tracer_log") {
+        const bool pool = (k == "tracers");
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (s->comm.active()) return fail(FS_EINVAL, "%s: tracers need a single-GPU handle", key);
+        if (end == value || *end || n < 0 || n > (pool ? 4194304L : 65536L))
+            return fail(FS_EINVAL, pool ? "tracers: slots of the pool, 0 (off) .. 4194304" : "tracer_log: frames kept, 0 (off) .. 65536");
+        const size_t C = (size_t)(pool ? n : s->tracers), N = (size_t)(pool ? s->tracer_log : n);
+        if (N * C * FS_TRACER_FRAME_BYTES > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "%s: %zu frames of %zu slots exceed 1 GiB", key, N, C);
+        if (pool) { s->tracers = (int)n; s->tracer_gen++; }
+        else { s->tracer_log = (int)n; s->tracer_log_gen++; }
+        if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
+            hipSetDevice(s->device);
+            return s->eng->tracer_config();
+        }
+        if (pool) s->tracer_seeded = 0;
+    } else if (k == "tracer_every") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (s->comm.active()) return fail(FS_EINVAL, "tracer_every: tracers need a single-GPU handle");
+        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "tracer_every: K >= 1");
+        s->tracer_every = n;
     } else if (k == "image_every") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -3405,6 +3693,10 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     }
     else if (n == "image_views") *out = (int)s->image_views.size();       // views set by fs_image_views
     else if (n == "image_frame_bytes") *out = (int)image_frame_bytes(s, s->image_views);   // one frame of the image log
+    else if (n == "tracer_capacity") *out = s->tracers;                    // slots of the tracer pool
+    else if (n == "tracer_count") *out = (int)std::min<long>(s->tracer_seeded, s->tracers);   // slots a fetch returns
+    else if (n == "tracer_seeded") *out = (int)std::min<long>(s->tracer_seeded, 2147483647L);   // particles seeded or released since the pool was cleared, saturating
+    else if (n == "tracer_emitters") *out = (int)(s->tracer_emit.size() / 3);
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -3893,6 +4185,61 @@ int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long*
     return s->eng->image_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
 }
 
+// ---- tracer particles -----------------------------------------------------------------------------------------------------
+namespace {
+bool tracer_points_ok(const fs_sim* s, const double* xyz, long n, long* bad)
+{
+    for (long k = 0; k < n; ++k)
+        if (!fs::tracer_in_box(xyz + 3 * k, s->W, s->H, s->D)) { *bad = k; return false; }
+    return true;
+}
+}  // namespace
+int fs_tracer_seed(fs_sim* s, const double* xyz, long n)
+{
+    ENGINE_OR_RETURN(s);
+    if (s->comm.active()) return fail(FS_EINVAL, "fs_tracer_seed: tracers need a single-GPU handle");
+    if (n < 0 || n > (1L << 24)) return fail(FS_EINVAL, "fs_tracer_seed: 0 .. 16777216 points, got %ld", n);
+    if (n > 0 && !xyz) return fail(FS_EINVAL, "fs_tracer_seed: null points");
+    long bad = 0;
+    if (!tracer_points_ok(s, xyz, n, &bad))
+        return fail(FS_EINVAL, "fs_tracer_seed: point %ld (%g,%g,%g) outside 0.5..%d.5 x 0.5..%d.5 x 0.5..%d.5", bad, xyz[3 * bad],
+                    xyz[3 * bad + 1], xyz[3 * bad + 2], s->W, s->H, s->D);
+    return s->eng->tracer_seed(xyz, n);
+}
+int fs_tracer_emitters(fs_sim* s, const double* xyz, long n, long every)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (s->comm.active()) return fail(FS_EINVAL, "fs_tracer_emitters: tracers need a single-GPU handle");
+    if (n < 0 || n > FS_TRACER_EMITTERS_MAX) return fail(FS_EINVAL, "fs_tracer_emitters: 0 .. %d emitters, got %ld", FS_TRACER_EMITTERS_MAX, n);
+    if (n > 0 && !xyz) return fail(FS_EINVAL, "fs_tracer_emitters: null points");
+    if (every < 1 || every > (1L << 30)) return fail(FS_EINVAL, "fs_tracer_emitters: every >= 1, got %ld", every);
+    long bad = 0;
+    if (!tracer_points_ok(s, xyz, n, &bad))
+        return fail(FS_EINVAL, "fs_tracer_emitters: point %ld (%g,%g,%g) outside 0.5..%d.5 x 0.5..%d.5 x 0.5..%d.5", bad, xyz[3 * bad],
+                    xyz[3 * bad + 1], xyz[3 * bad + 2], s->W, s->H, s->D);
+    s->tracer_emit.assign(xyz, xyz + 3 * n);
+    s->tracer_emit_every = every;
+    s->tracer_emit_gen++;
+    return FS_OK;
+}
+int fs_tracer_clear(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->tracer_clear(); }
+int fs_tracer_advance(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->tracer_advance(); }
+int fs_tracer_fetch(fs_sim* s, double* xyz, int32_t* meta, long max, long* n)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->tracer_fetch(xyz, meta, max, n);
+}
+int fs_tracer_sample(fs_sim* s, int source, int mode, double* out, long n)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->tracer_sample(source, mode, out, n);
+}
+int fs_tracer_log(fs_sim* s, double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->tracer_log_fetch(xyz, status, steps, max_frames, n_frames, n_dropped);
+}
+
 // An 8-bit RGB, non-interlaced PNG whose one IDAT chunk is a zlib stream of stored deflate blocks: filter type 0 on every
 // scanline, no compression, no zlib dependency; the bytes are a pure function of the pixels.
 int fs_image_png(const uint8_t* rgb, int cols, int rows, const char* path)
@@ -3991,6 +4338,7 @@ int fs_comm_init(fs_sim* s, int rank, int nranks, const void* id)
     if (nranks == 1) return FS_OK;
     if (s->body_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"body_force_log\" is on, and bodies are labelled on a single-GPU handle");
     if (s->image_log > 0 && !s->image_views.empty()) return fail(FS_EINVAL, "fs_comm_init: the image log is on, and images are taken on a single-GPU handle");
+    if (s->tracers > 0) return fail(FS_EINVAL, "fs_comm_init: option \"tracers\" is on, and tracers move on a single-GPU handle");
     hipSetDevice(s->device);
     if (s->comm.init(rank, nranks, id)) return fail(FS_ECOMM, "%s", s->comm.last_error());
     if (rank == 0 && !s->quiet)          // one line of provenance for multi-GPU logs

@@ -587,6 +587,68 @@ class Simulation:
             at += 3 * rows * cols
         return (steps, images, dropped.value) if with_dropped else (steps, images)
 
+    # -- tracer particles (single GPU) -----------------------------------------------------------
+    tracer_count = property(lambda s: s._geti("tracer_count"))
+    tracer_capacity = property(lambda s: s._geti("tracer_capacity"))
+
+    def tracer_seed(self, points):
+        """Appends particles to the tracer pool (option tracers=C; fs_tracer_seed): `points` is (n, 3), x, y, z in the
+        viewer's padded index space, every one inside 0.5 .. N + 0.5 on each axis.  The j-th particle ever seeded goes
+        into slot j % C: a full pool overwrites its oldest particles."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        check(self._L.fs_tracer_seed(self._h, p.ctypes.data_as(C.c_void_p), p.shape[0]))
+
+    def tracer_emitters(self, points, every=1):
+        """Sets the emitters (fs_tracer_emitters): up to TRACER_EMITTERS_MAX points; every `every`-th step releases one
+        particle per emitter, `source` = the emitter's index.  An empty list turns them off.  Replaces the list."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        check(self._L.fs_tracer_emitters(self._h, p.ctypes.data_as(C.c_void_p), p.shape[0], int(every)))
+
+    def tracer_advance(self):
+        """Moves the particles through the velocity field as it is now, releases one particle per emitter and takes a
+        snapshot (fs_tracer_advance; fs_step does all this by itself with tracers=C)."""
+        check(self._L.fs_tracer_advance(self._h))
+
+    def tracer_clear(self):
+        """Frees every slot, resets the seed counter and clears the snapshot log (fs_tracer_clear)."""
+        check(self._L.fs_tracer_clear(self._h))
+
+    def tracers(self):
+        """The pool's slots 0 .. tracer_count - 1 (fs_tracer_fetch): {"xyz": (n, 3) float64, "status", "source", "born",
+        "moves": (n,) int32}; status is TRACER_FREE, TRACER_ALIVE, TRACER_OUT (left the box; xyz is where) or TRACER_HIT
+        (ended in a solid cell)."""
+        n = C.c_long()
+        check(self._L.fs_tracer_fetch(self._h, None, None, 0, C.byref(n)))
+        xyz = np.zeros((n.value, 3), dtype=np.float64)
+        meta = np.zeros((n.value, 4), dtype=np.int32)
+        check(self._L.fs_tracer_fetch(self._h, xyz.ctypes.data_as(C.c_void_p), meta.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return {"xyz": xyz, "status": meta[:, 0].copy(), "source": meta[:, 1].copy(), "born": meta[:, 2].copy(),
+                "moves": meta[:, 3].copy()}
+
+    def tracer_sample(self, source, mode="linear"):
+        """The value of `source` at the particles' current positions (fs_tracer_sample), (tracer_count,) float64: the
+        sampler on the pool's own position array.  `source` and `mode` as for sample()."""
+        m = _lib.SAMPLE_MODES[mode] if isinstance(mode, str) else int(mode)
+        n = self.tracer_count
+        out = np.empty(n, dtype=np.float64)
+        check(self._L.fs_tracer_sample(self._h, int(source), m, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def tracer_log(self, with_dropped=False):
+        """Drains the snapshot log of the pool (option tracer_log=N; fs_tracer_log): {"step": (F,) int64, "xyz": (F, C, 3)
+        float64, "status": (F, C) int32}, oldest frame first.  with_dropped=True returns (that, number of frames the ring
+        overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        cap = self.tracer_capacity
+        check(self._L.fs_tracer_log(self._h, None, None, None, 0, C.byref(n), C.byref(dropped)))
+        xyz = np.zeros((n.value, cap, 3), dtype=np.float64)
+        status = np.zeros((n.value, cap), dtype=np.int32)
+        steps = np.zeros(n.value, dtype=np.int64)
+        check(self._L.fs_tracer_log(self._h, xyz.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p),
+                                    steps.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(dropped)))
+        log = {"step": steps, "xyz": xyz, "status": status}
+        return (log, dropped.value) if with_dropped else log
+
     def time_sweeps(self, b, field, prev, a, c, reps):
         ms = C.c_double()
         check(self._L.fs_time_sweeps(self._h, b, field, prev, a, c, reps, C.byref(ms)))

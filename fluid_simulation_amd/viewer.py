@@ -96,6 +96,41 @@ def surface_pressure(sim, source=_lib.PRESSURE, p_ref=0.0):
     return mesh
 
 
+def streaklines(sim):
+    """The streaklines of a live `Simulation` with emitters (tracer_emitters): one (m, 3) float64 polyline per emitter,
+    that emitter's ALIVE particles ordered by `born`, newest first -- the curve smoke from a nozzle draws, starting at the
+    nozzle.  Particles released in the same step keep their slot order.  Host-side grouping of Simulation.tracers()."""
+    t = sim.tracers()
+    n = sim._geti("tracer_emitters")
+    alive = t["status"] == _lib.TRACER_ALIVE
+    lines = []
+    for e in range(n):
+        idx = np.flatnonzero(alive & (t["source"] == e))
+        idx = idx[np.argsort(-t["born"][idx].astype(np.int64), kind="stable")]
+        lines.append(t["xyz"][idx].copy())
+    return lines
+
+
+def pathlines(log):
+    """The pathlines in a snapshot log (Simulation.tracer_log()): for each slot the list of (m, 3) float64 polylines it
+    drew, cut wherever the slot was not ALIVE in a frame -- a slot that was overwritten while ALIVE in consecutive frames
+    is not told apart here; keep the pool larger than the particles of a run.  Host-side grouping."""
+    alive = log["status"] == _lib.TRACER_ALIVE           # (F, C)
+    frames, slots = alive.shape if alive.ndim == 2 else (0, 0)
+    out = []
+    for s in range(slots):
+        runs, start = [], None
+        for f in range(frames + 1):
+            on = f < frames and alive[f, s]
+            if on and start is None:
+                start = f
+            elif not on and start is not None:
+                runs.append(log["xyz"][start:f, s].copy())
+                start = None
+        out.append(runs)
+    return out
+
+
 # the 2-D viewer's colour ranges (gui.py:271-289) and the strength of its obstacle overlay (gui.py:295)
 SLICE_RANGES = {"density": (_lib.DENS, 0.0, 0.01), "v_x": (_lib.VX, -10.0, 10.0), "v_y": (_lib.VY, -1.0, 1.0),
                 "v_z": (_lib.VZ, -1.0, 1.0)}

@@ -120,6 +120,11 @@ int fs_destroy(fs_sim* s);
  *   "image_log"   N >= 0 (at most 65536): keep the last N frames of the image views (fs_image_views, fs_image_log); 0 (default) =
  *                 off, and the step launches and allocates nothing for it.  "image_every" K >= 1 (default 1): a frame every
  *                 Kth step.  Setting "image_log" (re)allocates and clears the log.  May be changed at any time.  Single GPU only.
+ *   "tracers"     C >= 0 (at most 4194304): slots of the tracer-particle pool (fs_tracer_seed and the entries beside it); 0
+ *                 (default) = off, and the step launches and allocates nothing for it.  "tracer_log" N >= 0 (at most 65536):
+ *                 keep the last N snapshots of the pool (fs_tracer_log); "tracer_every" K >= 1 (default 1): a snapshot every
+ *                 Kth step.  Setting "tracers" (re)allocates and clears the pool and the log, setting "tracer_log" the log.
+ *                 May be changed at any time.  Single GPU only.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -162,7 +167,8 @@ int fs_destroy(fs_sim* s);
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
  * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
- * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count".
+ * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count", and
+ * "tracer_capacity" "tracer_count" "tracer_seeded" "tracer_emitters" (see the tracer particles below).
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -238,7 +244,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * 10 where the dead density solve is elided, 0 with it off) "flow_stats" (one launch per sample of the time-averaged flow
  * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off) "body_forces"
  * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off) "images"
- * (one launch counted per rendered view of the image log, 0 with the feature off).  Events are recorded on the handle's own stream. */
+ * (one launch counted per rendered view of the image log, 0 with the feature off) "tracers" (one launch per advance of the tracer
+ * particles, in fs_step or by fs_tracer_advance, 0 with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -649,6 +656,78 @@ int fs_image_png(const uint8_t* rgb, int cols, int rows, const char* path);   /*
 int fs_image_views(fs_sim* s, const int* spec, const double* range, int n);
 int fs_image_sample(fs_sim* s);
 int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped);
+
+/* ---- tracer particles (beyond the reference: it follows no fluid parcel through time, no file:line counterpart) ----
+ *
+ * Particles released into the flow and carried by it as it evolves: pathlines (one particle's positions over time) and
+ * streaklines (the particles one emitter has released), where fs_streamlines integrates one frozen field.
+ * COORDINATES are the viewer's, as for fs_sample: indices into the padded array, x first.
+ * THE BOX B is 0.5 <= c <= N + 0.5 on each axis (N = w, h, d): the range advect clamps its back-traces to
+ * (simulation.cpp:388-390).  A NaN coordinate is outside B.
+ * THE DISPLACEMENT per step of a parcel with velocity (u, v, w) is what advect traces back (simulation.cpp:384-386):
+ *     k = ((double)dt * w, (double)dt * h, (double)dt * d)      exact: a 24-bit dt times an extent below 2^11
+ *     h = 0.5 * k                                               exact as well
+ * A PARTICLE occupies one slot of a pool of C slots (option "tracers" = C).  Its state is the position xyz[3 * slot + ..] in
+ * fp64, and four int32 {status, source, born, moves}, status one of FS_TRACER_FREE (0), FS_TRACER_ALIVE (1), FS_TRACER_OUT
+ * (2), FS_TRACER_HIT (3).
+ * THE MOVE of an ALIVE particle at P, in fp64; every written operation is rounded once, in exactly this order, without
+ * contraction.  LIN(f, P) is exactly FS_SAMPLE_LINEAR of field f at P as fs_sample defines it above:
+ *     u1 = (LIN(v_x, P), LIN(v_y, P), LIN(v_z, P))
+ *     M_a = P_a + h_a * u1_a                                    a = x, y, z
+ *     if M is in B:  u2 = (LIN(v_x, M), LIN(v_y, M), LIN(v_z, M)),   P'_a = P_a + k_a * u2_a
+ *     else:          P' = M
+ *     status' = P' not in B ? OUT : (obs at cell (floor(P'_x + 0.5), floor(P'_y + 0.5), floor(P'_z + 0.5)) == 1 ? HIT : ALIVE)
+ *     moves' = moves + 1
+ * the explicit midpoint rule on the velocity field frozen at the sample point.  P' is stored whatever the status, so an OUT
+ * particle shows where it left.  A NaN velocity gives NaN and hence OUT.  Slots that are not ALIVE are never touched again
+ * until they are overwritten.  A particle's move is a pure function of its position, the 48 corner values, one obs value, dt
+ * and the extents: launch shape cannot change a bit.
+ *
+ * fs_tracer_seed appends n particles (xyz[3 * k + ..] = x, y, z; n = 0 .. 2^24): status ALIVE, source -1, born = the steps
+ * the handle has completed, moves 0.  The j-th particle ever seeded or released (since the pool was last cleared) goes into
+ * slot j % C, so a full pool overwrites its oldest particles.  Every point must lie in B, else FS_EINVAL and nothing is
+ * seeded.  obs is not looked at: a particle seeded inside a solid sits on zero velocity and becomes HIT at its first move.
+ * fs_tracer_emitters keeps n = 0 (off) .. FS_TRACER_EMITTERS_MAX points in B as the emitters, with every >= 1 (anything else
+ * FS_EINVAL); it replaces the list.  fs_tracer_clear sets every slot FREE and the seed counter to 0, and clears the log.
+ * INSIDE fs_step, at the sample point of the flow statistics, the probes and the images -- after advect(0, dens, buffer)
+ * (simulation.cpp:136), before the frame dump -- on the step's own stream, by one launch, without a host synchronisation:
+ *     1. every ALIVE particle moves;
+ *     2. if emitters are set and (steps_total - 1) % every == 0, one particle per emitter is appended in list order, with
+ *        source = the emitter's index and born = steps_total (the steps completed, this one included); it is not moved in
+ *        this step;
+ *     3. if "tracer_log" is on and (steps_total - 1) % "tracer_every" == 0, the pool's positions and status words go into
+ *        the snapshot ring.
+ * The slot cursor is the host's: how many particles an advance appends is known without asking the device.
+ * fs_tracer_advance does 1 - 3 on the state as it is now, for callers who drive the passes themselves; it releases and
+ * takes a snapshot whatever the two schedules say (as fs_image_sample takes a frame), born and the frame's step being the
+ * steps completed so far.
+ * Options (fs_set_option, any time): "tracers" = C, 0 (default: off, a step launches and allocates nothing for it) ..
+ * 4194304; setting it (re)allocates and clears the pool and the log.  "tracer_log" = N frames kept, 0 .. 65536; setting it
+ * (re)allocates and clears the log.  "tracer_every" = K >= 1.  Setting "tracers" or "tracer_log" is FS_EINVAL if N * C *
+ * FS_TRACER_FRAME_BYTES would exceed 1 GiB; if the device cannot provide the memory the call (or the first use of the handle)
+ * is FS_ENOMEM and the option is 0 again.  fs_get_int: "tracer_capacity" = C, "tracer_count" = min(seeded, C),
+ * "tracer_seeded" (saturates at 2^31 - 1), "tracer_emitters".
+ * fs_tracer_fetch copies slots 0 .. count-1: xyz[3 * count], meta[4 * count] = {status, source, born, moves} per slot;
+ * either array may be NULL, with both NULL it only reports *n = count; max < count is FS_EINVAL.
+ * fs_tracer_sample evaluates any source of fs_sample, in any of its modes, at the particles' current positions into out[n]:
+ * the sampler's kernel on the pool's own position array, no host round trip; n must equal the count.  Dead particles are
+ * evaluated where they stopped; the sampler's own rule gives NaN outside [0, N + 1].
+ * fs_tracer_log drains the snapshot ring, oldest frame first: xyz[(i * C + slot) * 3 + ..], status[i * C + slot], steps[i]
+ * (may be NULL) the steps the handle had completed.  Both arrays NULL only reports the counts; max_frames and *n_dropped
+ * (overwritten frames) are as for fs_image_log.
+ * Timing family "tracers" counts one launch per advance, 0 with the feature off.  Single-GPU handles only: every entry and
+ * option here is FS_EINVAL on a z-slab handle, and so is fs_comm_init on a handle whose "tracers" is on.
+ */
+enum { FS_TRACER_FREE = 0, FS_TRACER_ALIVE = 1, FS_TRACER_OUT = 2, FS_TRACER_HIT = 3 };
+#define FS_TRACER_EMITTERS_MAX 4096
+#define FS_TRACER_FRAME_BYTES 28   /* one slot of one snapshot frame: three fp64 coordinates and the status word */
+int fs_tracer_seed(fs_sim* s, const double* xyz, long n);
+int fs_tracer_emitters(fs_sim* s, const double* xyz, long n, long every);
+int fs_tracer_clear(fs_sim* s);
+int fs_tracer_advance(fs_sim* s);
+int fs_tracer_fetch(fs_sim* s, double* xyz, int32_t* meta, long max, long* n);
+int fs_tracer_sample(fs_sim* s, int source, int mode, double* out, long n);
+int fs_tracer_log(fs_sim* s, double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

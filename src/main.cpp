@@ -51,6 +51,14 @@
 //                  run's frames where they fit 256 MiB and is drained at the end; a longer run is driven step by step
 //                  (fs_run_one, frame dumps through fs_dump_frame, without run()'s console lines) and the ring is drained
 //                  whenever it is full.  Single GPU.
+//   --tracers C    tracer particles: a pool of C slots (option "tracers"); --tracer-emitters FILE sets the emitters, a text file
+//                  with one point `x y z` per line in the viewer's padded index space (0.5 .. N + 0.5 on each axis), `#`
+//                  starts a comment; --tracer-every K releases one particle per emitter every Kth step (steps 1, K+1, ...;
+//                  default 1) -- the `every` of fs_tracer_emitters, NOT the library option "tracer_every", which is the
+//                  cadence of the snapshot log and has no flag here; --tracer-out FILE writes the final pool after the run
+//                  as CSV: slot,source,born,moves,status,x,y,z with the positions as %.17g (they read back exactly).
+//                  --tracer-emitters and --tracer-out need --tracers, --tracer-every needs --tracer-emitters: anything
+//                  else is refused.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -267,6 +275,51 @@ int write_probes(fs_sim* sim, const char* path, long nprobes)
     return ok ? 0 : 1;
 }
 
+// the emitters of --tracer-emitters: `x y z` per line, `#` comments
+int read_points(const char* path, std::vector<double>& pts)
+{
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot open %s\n", path); return 1; }
+    char line[512];
+    int lineno = 0;
+    bool ok = true;
+    while (ok && fgets(line, sizeof line, fp)) {
+        ++lineno;
+        if (char* hash = strchr(line, '#')) *hash = 0;
+        double x, y, z;
+        int used = 0;
+        const int got = sscanf(line, "%lf %lf %lf %n", &x, &y, &z, &used);
+        if (got == EOF || (got <= 0 && strspn(line, " \t\r\n") == strlen(line))) continue;   // blank or comment
+        if (got != 3 || line[used] != 0) {
+            fprintf(stderr, "simulation.out: %s:%d: expected `x y z`\n", path, lineno);
+            ok = false;
+        } else {
+            pts.push_back(x); pts.push_back(y); pts.push_back(z);
+        }
+    }
+    fclose(fp);
+    return ok ? 0 : 1;
+}
+
+// the final tracer pool -> CSV (the arrays of fs_tracer_fetch)
+int write_tracers(fs_sim* sim, const char* path)
+{
+    long n = 0;
+    if (fs_tracer_fetch(sim, nullptr, nullptr, 0, &n)) return 1;
+    std::vector<double> xyz((size_t)n * 3 + 1);
+    std::vector<int32_t> meta((size_t)n * 4 + 1);
+    if (fs_tracer_fetch(sim, xyz.data(), meta.data(), n, &n)) return 1;
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "slot,source,born,moves,status,x,y,z\n");
+    for (long k = 0; k < n; ++k)
+        fprintf(fp, "%ld,%d,%d,%d,%d,%.17g,%.17g,%.17g\n", k, (int)meta[4 * k + 1], (int)meta[4 * k + 2], (int)meta[4 * k + 3],
+                (int)meta[4 * k], xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]);
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
 // one view of --image-view: SRC:KIND:AXIS:INDEX:VMIN:VMAX[:ALPHA] -> spec[4], range[3]
 bool parse_view(const char* text, int* spec, double* range)
 {
@@ -344,7 +397,9 @@ int main(int argc, char** argv)
     bool stl_given = false, json = false;
     std::string resume_dir, forces_path, residuals_path, mean_dir, vortex_dir, probes_path, probe_log_path, body_forces_path;
     bool mean_moments = false;
-    std::string images_dir;
+    std::string images_dir, tracer_emitters_path, tracer_out_path;
+    long tracers = 0, tracer_every = 1;
+    bool tracer_every_given = false;
     long image_every = 1;
     int dump_every = 1;
     std::vector<int> view_spec;
@@ -385,6 +440,10 @@ int main(int argc, char** argv)
         if (key == "vortex") { vortex_dir = val; return true; }
         if (key == "probes") { probes_path = val; return true; }
         if (key == "probe-log") { probe_log_path = val; return true; }
+        if (key == "tracers") { tracers = atol(val); return tracers >= 0; }
+        if (key == "tracer-emitters") { tracer_emitters_path = val; return true; }
+        if (key == "tracer-every") { tracer_every = atol(val); tracer_every_given = true; return tracer_every >= 1; }
+        if (key == "tracer-out") { tracer_out_path = val; return true; }
         if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         return false;
@@ -392,7 +451,7 @@ int main(int argc, char** argv)
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
-                                        "image-view" };
+                                        "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -412,6 +471,14 @@ int main(int argc, char** argv)
         }
         ++i;
     }
+    if (tracers == 0 && (!tracer_emitters_path.empty() || !tracer_out_path.empty())) {
+        fprintf(stderr, "simulation.out: --tracer-emitters and --tracer-out need --tracers C with C > 0\n");
+        return 2;
+    }
+    if (tracer_every_given && tracer_emitters_path.empty()) {
+        fprintf(stderr, "simulation.out: --tracer-every is the emitters' release period and needs --tracer-emitters\n");
+        return 2;
+    }
     if (!stl_given) {
         Stl s;
         s.path = "/media/raoul/Speed/Data/3D-Printing/Models/Cars/F1Car-basic.stl";   // simulation.cpp:441
@@ -430,8 +497,14 @@ int main(int argc, char** argv)
         if (fs_set_probes(sim, probe_cells.data(), (long)(probe_cells.size() / 3))) return die("fs_set_probes");
     }
     if (!probe_log_path.empty()) options.push_back({ "probe_log", std::to_string(iter) });
+    if (tracers > 0) options.push_back({ "tracers", std::to_string(tracers) });
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
+    if (!tracer_emitters_path.empty()) {
+        std::vector<double> pts;
+        if (read_points(tracer_emitters_path.c_str(), pts)) return 2;
+        if (fs_tracer_emitters(sim, pts.data(), (long)(pts.size() / 3), tracer_every)) return die("fs_tracer_emitters");
+    }
     bool stepwise = false;                               // --images: the run's frames do not fit the ring
     long image_ring = 0;
     if (!images_dir.empty()) {
@@ -481,6 +554,7 @@ int main(int argc, char** argv)
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
+    if (!tracer_out_path.empty() && write_tracers(sim, tracer_out_path.c_str())) return die("fs_tracer_fetch");
     int mean_samples = 0;
     if (!mean_dir.empty()) {
         if (fs_get_int(sim, "flow_stats_samples", &mean_samples)) return die("flow_stats_samples");

@@ -328,6 +328,34 @@ int main(int argc, char** argv)
             CHECK(fs_run_one(s));
             CHECK(fs_set_option(s, "probe_log", "0"));
         }
+        {   // tracer particles: seeds past the pool's end, emitters, steps and an advance on demand, the ring through a wrap, off again
+            const double seeds[] = { 2.0, 12.0, 10.0, 0.5, 0.5, 0.5, 40.5, 24.5, 20.5, 3.0, 3.0, 3.0, 5.5, 6.25, 7.75 };
+            const double bad[] = { 0.25, 1.0, 1.0 };
+            if (fs_tracer_advance(s) != FS_EINVAL || fs_tracer_seed(s, seeds, 1) != FS_EINVAL) return 46;   // the option is off
+            CHECK(fs_set_option(s, "tracers", "6"));
+            CHECK(fs_set_option(s, "tracer_log", "2"));
+            if (fs_tracer_seed(s, bad, 1) != FS_EINVAL || fs_tracer_emitters(s, seeds, 2, 0) != FS_EINVAL) return 47;
+            CHECK(fs_tracer_seed(s, seeds, 5));
+            CHECK(fs_tracer_emitters(s, seeds, 2, 2));
+            for (int k = 0; k < 3; ++k) CHECK(fs_run_one(s));
+            CHECK(fs_tracer_advance(s));
+            long np = 0, nf = 0, nd = 0;
+            CHECK(fs_tracer_fetch(s, nullptr, nullptr, 0, &np));
+            if (np != 6) return 48;
+            std::vector<double> xyz(3 * 6 * 2), val(6);
+            std::vector<int32_t> meta(4 * 6), status(6 * 2);
+            std::vector<long> steps(2);
+            if (fs_tracer_fetch(s, xyz.data(), meta.data(), 5, &np) != FS_EINVAL) return 49;
+            CHECK(fs_tracer_fetch(s, xyz.data(), meta.data(), 6, &np));
+            CHECK(fs_tracer_sample(s, FS_PRESSURE, FS_SAMPLE_LINEAR, val.data(), 6));
+            CHECK(fs_tracer_log(s, nullptr, nullptr, nullptr, 0, &nf, &nd));
+            if (nf != 2 || nd != 2) return 50;
+            CHECK(fs_tracer_log(s, xyz.data(), status.data(), steps.data(), 2, &nf, &nd));
+            CHECK(fs_get_timing(s, "tracers", &ms, &launches));
+            if (launches != 4) return 51;
+            CHECK(fs_tracer_clear(s));
+            CHECK(fs_set_option(s, "tracers", "0"));
+        }
         CHECK(fs_set_option(s, "solver", "gs_lex"));
         CHECK(fs_run_one(s));
         CHECK(fs_destroy(s));
