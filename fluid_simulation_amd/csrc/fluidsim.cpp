@@ -23,6 +23,7 @@
 #include "flow_stats.h"
 #include "vortex.h"
 #include "sample.h"
+#include "step_ring.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -298,6 +299,50 @@ struct ScopedSpan {
     ~ScopedSpan() { s->span_end(id, n); }
 };
 
+// The device ring of a per-step log: `at` keeps the books (step_ring.h), `base` holds at.cap slots of slot_bytes, set up for
+// generation `gen` of the options that size it.  What a slot holds, when a record is committed and how the fetched slots
+// become rows is the log's own business.
+struct LogRing {
+    fs::StepRing at;
+    char* base = nullptr;
+    size_t slot_bytes = 0;
+    long gen = -1;
+
+    bool on() const { return at.cap > 0; }
+    char* slot(long k) const { return base + (size_t)k * slot_bytes; }
+    void release() { if (base) hipFree(base); base = nullptr; }   // the engine's end
+    // For generation `gen_`: the old ring goes (a queued record may still write to it: the stream is synchronised first) and
+    // `cap` zero-filled slots of `bytes` come; cap <= 0 = the log is off.  Where the allocation fails, `base` is null.
+    hipError_t setup(hipStream_t stream, long gen_, int cap = 0, size_t bytes = 0)
+    {
+        hipError_t e = base ? hipStreamSynchronize(stream) : hipSuccess;
+        if (e == hipSuccess && base) e = hipFree(base);
+        if (e != hipSuccess) return e;
+        base = nullptr;
+        slot_bytes = bytes;
+        at.reset(0);
+        gen = gen_;
+        if (cap <= 0) return hipSuccess;
+        if ((e = hipMalloc((void**)&base, (size_t)cap * bytes)) != hipSuccess) { base = nullptr; return e; }
+        if ((e = hipMemsetAsync(base, 0, (size_t)cap * bytes, stream)) == hipSuccess) at.reset(cap);
+        return e;
+    }
+    // The retained slots, oldest first, to the host buffer `dst`, in at most two copies on `stream`.  A ring laid out in
+    // sections (the tracer log) names the section's first slot and its bytes per slot.
+    hipError_t copy_out(hipStream_t stream, void* dst, const void* section = nullptr, size_t bytes = 0) const
+    {
+        const char* from = section ? (const char*)section : base;
+        if (!section) bytes = slot_bytes;
+        fs::StepRing::Run run[2];
+        hipError_t e = hipSuccess;
+        for (int r = 0, n = at.runs(run); r < n && e == hipSuccess; ++r) {
+            e = hipMemcpyAsync(dst, from + (size_t)run[r].first_slot * bytes, (size_t)run[r].count * bytes, hipMemcpyDeviceToHost, stream);
+            dst = (char*)dst + (size_t)run[r].count * bytes;
+        }
+        return e;
+    }
+};
+
 // what the image entries accept without looking at the state: a source of fs_sample by its bits, and a colour range
 bool image_source_ok(int source)
 {
@@ -381,23 +426,14 @@ struct Engine : EngineBase {
     double vzmax_prev = -1.0;           // max |v_z| at the end of the previous step (= v_z_prev of this one), -1 = unknown
     double vzmax_end = -1.0;            // the same for the step that is running
     bool in_step = false;               // inside step(): the data flow between the solver's calls is known
-    // pressure force (forces.h): the per-step log is a device ring of force_cap steps x 2 projections x g.D plane records
-    double* force_ring = nullptr;
+    // pressure force (forces.h): the per-step log is a device ring of steps x 2 projections x g.D plane records
+    LogRing force_ring;                 // for S->force_log_gen
     double* force_scratch = nullptr;    // fs_obstacle_force: one record per local plane
-    int force_cap = 0;
-    long force_gen = -1;                // S->force_log_gen the ring was allocated for
-    long force_logged = 0;              // steps logged since the ring was cleared or last drained
-    std::vector<long> force_step;       // step number held by each ring slot
-    // solve residuals (residual.h): the per-step log is a device ring of res_cap steps x 6 solves x {before, after} x g.D plane records
-    double* res_ring = nullptr;
+    // solve residuals (residual.h): the per-step log is a device ring of steps x 6 solves x {before, after} x g.D plane records
+    LogRing res_ring;                   // for S->residual_log_gen; a slot's tag, bit k: solve k of that step ran (an elided solve leaves no record)
     double* res_scratch = nullptr;      // fs_solve_residual: one record per local plane
     double* res_partial = nullptr;      // the row-chunk records between the two kernels of a launch (stream-ordered reuse)
-    int res_cap = 0;
-    long res_gen = -1;                  // S->residual_log_gen the ring was allocated for
-    long res_logged = 0;                // steps logged since the ring was cleared or last drained
-    std::vector<long> res_step;         // step number held by each ring slot
-    std::vector<unsigned> res_ran;      // bit k: solve k of that step ran (an elided solve leaves no record)
-    unsigned res_ran_now = 0;           // the same for the step that is running
+    unsigned res_ran_now = 0;           // the tag of the step that is running
     // time-averaged flow statistics (flow_stats.h): private allocations, one per accumulator, never exported to slab neighbours
     fs::FlowStatsAcc stat_acc = {};
     int stat_nacc = 0;                  // accumulators allocated: 0, 5 or 12
@@ -409,16 +445,13 @@ struct Engine : EngineBase {
     double* samp_pts = nullptr;
     double* samp_out = nullptr;
     long samp_n = 0, samp_room = 0;     // points kept / points the two arrays have room for
-    // point probes (sample.h): the per-step log is a device ring of probe_cap records x probe_n probes x {q, u, v, w, p}
+    // point probes (sample.h): the per-step log is a device ring of records x probe_n probes x {q, u, v, w, p}
     long* probe_idx = nullptr;          // each probe's cell index in this slab's arrays, -1 = a plane another rank owns
-    double* probe_ring = nullptr;
-    int probe_n = 0, probe_cap = 0;     // probe_cap > 0 only with probe_n > 0
-    long probe_gen = -1;                // S->probe_gen they were set up for
-    long probe_logged = 0;              // records taken since the ring was cleared or last drained
-    std::vector<long> probe_step;       // step number held by each ring slot
+    LogRing probe_ring;                 // for S->probe_gen, as is the list; on only with probe_n > 0
+    int probe_n = 0;
     // slice and projection images (image.h): one allocation holds the value image, the flag image of a slice, the obstacle
     // silhouette of each axis (valid until obs changes), an RGB staging image and the colour table; the per-step log is a
-    // device ring of img_cap frames x img_frame_bytes (the views' RGB images one after the other)
+    // device ring of frames (the views' RGB images one after the other)
     double* img_val = nullptr;          // the allocation's base
     uint8_t* img_flag = nullptr;
     uint8_t* img_sil[3] = {nullptr, nullptr, nullptr};
@@ -427,14 +460,9 @@ struct Engine : EngineBase {
     uint8_t* img_table = nullptr;
     int img_table_n = 0;
     long img_table_gen = -1;            // S->image_table_gen the device table holds
-    uint8_t* img_ring = nullptr;
-    int img_cap = 0;
-    size_t img_frame_bytes = 0;
-    long img_gen = -1;                  // S->image_gen the ring was set up for
-    long img_logged = 0;                // frames taken since the ring was cleared or last drained
-    std::vector<long> img_step;         // step number held by each ring slot
+    LogRing img_ring;                   // for S->image_gen
     // tracer particles (tracers.h): the pool (positions as the sampler's point list, four meta words per slot), the emitters'
-    // points, and the snapshot log, a device ring of tr_log_cap frames (all position frames, then all status frames)
+    // points, and the snapshot log, a device ring of frames (all position frames, then all status frames)
     double* tr_xyz = nullptr;
     int* tr_meta = nullptr;
     int tr_cap = 0;                     // slots allocated: S->tracers once set up
@@ -442,13 +470,9 @@ struct Engine : EngineBase {
     double* tr_emit = nullptr;          // FS_TRACER_EMITTERS_MAX points, allocated with the pool
     long tr_emit_gen = -1;              // S->tracer_emit_gen the device list holds
     double* tr_out = nullptr;           // fs_tracer_sample: one value per slot, allocated at the first call
-    double* tr_ring = nullptr;
-    int tr_log_cap = 0;
-    long tr_log_gen = -1;               // S->tracer_log_gen the ring was set up for
-    long tr_logged = 0;                 // frames taken since the ring was cleared or last drained
-    std::vector<long> tr_step;          // step number held by each ring slot
+    LogRing tr_ring;                    // for S->tracer_log_gen, -1 after a new pool
     // per-body forces and moments (bodies.h): the labels (dense padded int32), what the host keeps of the last labelling, and
-    // the per-step log, a device ring of body_cap steps x 2 projections x (body_B + 1) whole-grid records
+    // the per-step log, a device ring of steps x 2 projections x (body_B + 1) whole-grid records
     int* body_L = nullptr;
     bool bodies_dirty = true;           // obs changed since the last labelling (set where the flag bytes are rebuilt)
     int body_B = 0;                     // bodies 1 .. body_B; record 0 is the REST
@@ -457,12 +481,7 @@ struct Engine : EngineBase {
     int* body_bbox = nullptr;           // per record, the cells its workgroups scan
     double* body_planes = nullptr;      // plane records of the last launch: g.D x (BODY_MAX + 1) x BODY_REC (stream-ordered reuse)
     double* body_total = nullptr;       // fs_body_force: the whole-grid records
-    double* body_ring = nullptr;
-    int body_cap = 0;
-    long body_gen = -1;                 // S->body_log_gen the ring was allocated for
-    bool body_ring_stale = false;       // a relabelling since then: the ring is set up anew, the log is cleared
-    long body_logged = 0;               // steps logged since the ring was cleared or last drained
-    std::vector<long> body_step;        // step number held by each ring slot
+    LogRing body_ring;                  // for S->body_log_gen, -1 after a relabelling: the ring is set up anew, the log is cleared
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -580,9 +599,7 @@ struct Engine : EngineBase {
         if (dense) hipFree(dense);
         if (red) hipFree(red);
         if (coltab) hipFree(coltab);
-        if (force_ring) hipFree(force_ring);
         if (force_scratch) hipFree(force_scratch);
-        if (res_ring) hipFree(res_ring);
         if (res_scratch) hipFree(res_scratch);
         if (res_partial) hipFree(res_partial);
         for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
@@ -590,16 +607,14 @@ struct Engine : EngineBase {
         if (samp_pts) hipFree(samp_pts);
         if (samp_out) hipFree(samp_out);
         if (probe_idx) hipFree(probe_idx);
-        if (probe_ring) hipFree(probe_ring);
         if (img_val) hipFree(img_val);
-        if (img_ring) hipFree(img_ring);
         if (tr_xyz) hipFree(tr_xyz);
         if (tr_meta) hipFree(tr_meta);
         if (tr_emit) hipFree(tr_emit);
         if (tr_out) hipFree(tr_out);
-        if (tr_ring) hipFree(tr_ring);
-        for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total, (void*)body_ring })
+        for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
             if (q) hipFree(q);
+        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring }) r->release();
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1284,7 +1299,7 @@ struct Engine : EngineBase {
     bool zero_start_ok(int log_k) const
     {
         if (!(S->zero_start < 0 ? ZERO_START_AUTO : S->zero_start != 0) || S->solver != FS_SOLVER_JACOBI || S->acc < 3 || S->comm.active()) return false;
-        if (log_k >= 0 && res_cap > 0) return false;
+        if (log_k >= 0 && res_ring.on()) return false;
         const TunedFor now{S->tune.fuse, S->tune.pair_shape, S->tune.two_kind, S->replay_two, S->replay_three};
         if (!(plan_two >= 0 && tuned_for == now) || plan_three < 0) return false;
         return fs::jacobi_fused_zero_start(S->tune, g, sc, (int)sizeof(T), plan_three);
@@ -1326,16 +1341,16 @@ struct Engine : EngineBase {
             fs::launch_gradient<T>(S->stream, S->tune, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
                                    arr[slot[FS_VZ]], flags, h, (T)2 * h);
         }
-        if (proj >= 0 && proj < 2 && force_cap > 0) {
+        if (proj >= 0 && proj < 2 && force_ring.on()) {
             // "force_log": this projection's plane records go straight into the step's ring slot (no host sync)
             ScopedSpan sp(S, FAM_FORCES);
-            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_slot(force_logged % force_cap, proj));
+            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_slot(force_ring.at.next(), proj));
         }
-        if (proj >= 0 && proj < 2 && body_cap > 0) {
+        if (proj >= 0 && proj < 2 && body_ring.on()) {
             // "body_force_log": this projection's whole-grid records of every body go into the step's ring slot (no host sync)
             ScopedSpan sp(S, FAM_BODYFORCES);
             fs::launch_body_forces<T>(S->stream, g, arr[slot[FS_PRESSURE]], flags, body_L, body_bbox, body_B + 1, S->moment_origin,
-                                      body_planes, body_slot(body_logged % body_cap, proj));
+                                      body_planes, body_slot(body_ring.at.next(), proj));
         }
         // the next consumer of v's z-halo planes is the divergence of the second projection
         // (v_z[z+-1]) and the advection back-trace; refresh them now.
@@ -1638,20 +1653,17 @@ struct Engine : EngineBase {
         slack_check();
         S->step_no++;
         S->steps_total++;
-        if (force_cap > 0) force_step[(size_t)(force_logged++ % force_cap)] = S->steps_total;
-        if (body_cap > 0) body_step[(size_t)(body_logged++ % body_cap)] = S->steps_total;
-        if (res_cap > 0) {
-            res_ran[(size_t)(res_logged % res_cap)] = res_ran_now;
-            res_step[(size_t)(res_logged++ % res_cap)] = S->steps_total;
-        }
+        if (force_ring.on()) force_ring.at.commit(S->steps_total);
+        if (body_ring.on()) body_ring.at.commit(S->steps_total);
+        if (res_ring.on()) res_ring.at.commit(S->steps_total, res_ran_now);
         // "flow_stats": the state as :136 left it is a sample (no host synchronisation, the step's own stream)
         if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
             (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
             return rc;
         // "probe_log": the same state is a record of the probes (one launch, no host synchronisation, the step's own stream)
-        if (probe_cap > 0) probe_record();
+        if (probe_ring.on()) probe_record();
         // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
-        if (img_cap > 0 && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
+        if (img_ring.on() && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
         // "tracers": the particles move through the same state, the emitters release, a snapshot is taken (one launch, no host
         // synchronisation, the step's own stream)
         if (tr_cap > 0)
@@ -2362,8 +2374,9 @@ struct Engine : EngineBase {
     }
 
     // ---- tracer particles (tracers.h; beyond the reference) ---------------------------------------------
-    double* tracer_frame_xyz(long f) const { return tr_ring + (size_t)f * 3 * (size_t)tr_cap; }
-    int* tracer_frame_status(long f) const { return (int*)(tr_ring + (size_t)tr_log_cap * 3 * (size_t)tr_cap) + (size_t)f * (size_t)tr_cap; }
+    // a ring slot is one frame's bytes, but the ring is laid out in two sections: every position frame, then every status frame
+    double* tracer_frame_xyz(long f) const { return (double*)tr_ring.base + (size_t)f * 3 * (size_t)tr_cap; }
+    int* tracer_frame_status(long f) const { return (int*)tracer_frame_xyz(tr_ring.at.cap) + (size_t)f * (size_t)tr_cap; }
 
     int tracer_config() override { return ensure_tracers(); }
 
@@ -2383,7 +2396,7 @@ struct Engine : EngineBase {
             tr_meta = nullptr;
             tr_cap = 0;
             tr_emit_gen = -1;
-            tr_log_gen = -1;                             // the frames are C slots wide: the ring goes with the pool
+            tr_ring.gen = -1;                            // the frames are C slots wide: the ring goes with the pool
             S->tracer_seeded = 0;
             tr_gen = S->tracer_gen;
             if (S->tracers > 0) {
@@ -2405,28 +2418,14 @@ struct Engine : EngineBase {
                 tr_cap = S->tracers;
             }
         }
-        if (tr_log_gen != S->tracer_log_gen || (tr_cap == 0 && tr_ring)) {
-            if (tr_ring) {
-                HIP_TRY(hipStreamSynchronize(S->stream));
-                HIP_TRY(hipFree(tr_ring));
+        if (tr_ring.gen != S->tracer_log_gen || (tr_cap == 0 && tr_ring.base)) {
+            const hipError_t e = tr_ring.setup(S->stream, S->tracer_log_gen, tr_cap > 0 ? S->tracer_log : 0, (size_t)tr_cap * fs::TRACER_FRAME_BYTES);
+            if (e != hipSuccess && !tr_ring.base) {      // no memory.  Likewise: the log is off until the option is set again
+                const int frames = S->tracer_log;
+                S->tracer_log = 0;
+                return fail(FS_ENOMEM, "tracer_log: %d frames of %d slots: %s (the option is 0 again)", frames, tr_cap, hipGetErrorString(e));
             }
-            tr_ring = nullptr;
-            tr_log_cap = 0;
-            tr_logged = 0;
-            tr_step.clear();
-            tr_log_gen = S->tracer_log_gen;
-            if (tr_cap > 0 && S->tracer_log > 0) {
-                const size_t bytes = (size_t)S->tracer_log * (size_t)tr_cap * fs::TRACER_FRAME_BYTES;
-                const hipError_t e = hipMalloc((void**)&tr_ring, bytes);
-                if (e != hipSuccess) {                   // likewise: the log is off until the option is set again
-                    const int frames = S->tracer_log;
-                    S->tracer_log = 0;
-                    return fail(FS_ENOMEM, "tracer_log: %d frames of %d slots: %s (the option is 0 again)", frames, tr_cap, hipGetErrorString(e));
-                }
-                HIP_TRY(hipMemsetAsync(tr_ring, 0, bytes, S->stream));
-                tr_log_cap = S->tracer_log;
-                tr_step.assign((size_t)tr_log_cap, 0);
-            }
+            HIP_TRY(e);
         }
         if (tr_cap > 0 && tr_emit_gen != S->tracer_emit_gen) {
             if (!S->tracer_emit.empty()) {
@@ -2453,15 +2452,15 @@ struct Engine : EngineBase {
         pass.n_emit = release ? (int)(S->tracer_emit.size() / 3) : 0;
         pass.first = (int)(S->tracer_seeded % tr_cap);
         pass.born = (int)S->steps_total;
-        const bool frame = snapshot && tr_log_cap > 0;
-        pass.frame_xyz = frame ? tracer_frame_xyz(tr_logged % tr_log_cap) : nullptr;
-        pass.frame_status = frame ? tracer_frame_status(tr_logged % tr_log_cap) : nullptr;
+        const bool frame = snapshot && tr_ring.on();
+        pass.frame_xyz = frame ? tracer_frame_xyz(tr_ring.at.next()) : nullptr;
+        pass.frame_status = frame ? tracer_frame_status(tr_ring.at.next()) : nullptr;
         {
             ScopedSpan sp(S, FAM_TRACERS);
             fs::launch_tracer_advance<T>(S->stream, g, pass, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], arr[slot[FS_OBS]]);
         }
         S->tracer_seeded += pass.n_emit;
-        if (frame) tr_step[(size_t)(tr_logged++ % tr_log_cap)] = S->steps_total;
+        if (frame) tr_ring.at.commit(S->steps_total);
     }
 
     int tracer_need(const char* who)
@@ -2514,7 +2513,7 @@ struct Engine : EngineBase {
         HIP_TRY(hipMemsetAsync(tr_xyz, 0, (size_t)tr_cap * 3 * sizeof(double), S->stream));
         HIP_TRY(hipMemsetAsync(tr_meta, 0, (size_t)tr_cap * fs::TRACER_META * sizeof(int), S->stream));
         S->tracer_seeded = 0;
-        tr_logged = 0;
+        tr_ring.at.drain();
         return FS_OK;
     }
 
@@ -2551,48 +2550,35 @@ struct Engine : EngineBase {
         if (S->comm.active()) return fail(FS_EINVAL, "fs_tracer_log: tracers need a single-GPU handle");
         int rc = ensure_tracers();
         if (rc) return rc;
-        const long n = tr_log_cap > 0 ? std::min<long>(tr_logged, tr_log_cap) : 0;
+        const long n = tr_ring.at.retained();
         if (n_frames) *n_frames = n;
-        if (n_dropped) *n_dropped = tr_logged - n;
+        if (n_dropped) *n_dropped = tr_ring.at.dropped();
         if (!xyz && !status) return FS_OK;
         if (max_frames < n) return fail(FS_EINVAL, "fs_tracer_log: %ld frames retained, room for %ld (pass both arrays NULL to ask)", n, max_frames);
-        const long first = tr_logged - n;
         if (n > 0) {
-            const long start = first % tr_log_cap, run = std::min<long>(n, tr_log_cap - start);
-            const size_t px = (size_t)tr_cap * 3, ps = (size_t)tr_cap;   // elements of one frame
-            if (xyz) {
-                HIP_TRY(hipMemcpyAsync(xyz, tracer_frame_xyz(start), (size_t)run * px * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-                if (n > run)
-                    HIP_TRY(hipMemcpyAsync(xyz + (size_t)run * px, tracer_frame_xyz(0), (size_t)(n - run) * px * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-            }
-            if (status) {
-                HIP_TRY(hipMemcpyAsync(status, tracer_frame_status(start), (size_t)run * ps * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-                if (n > run)
-                    HIP_TRY(hipMemcpyAsync(status + (size_t)run * ps, tracer_frame_status(0), (size_t)(n - run) * ps * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-            }
+            if (xyz) HIP_TRY(tr_ring.copy_out(S->stream, xyz, tracer_frame_xyz(0), (size_t)tr_cap * 3 * sizeof(double)));
+            if (status) HIP_TRY(tr_ring.copy_out(S->stream, status, tracer_frame_status(0), (size_t)tr_cap * sizeof(int32_t)));
             HIP_TRY(hipStreamSynchronize(S->stream));
         }
         if (steps)
-            for (long i = 0; i < n; ++i) steps[i] = tr_step[(size_t)((first + i) % tr_log_cap)];
-        tr_logged = 0;                                   // drained
+            for (long i = 0; i < n; ++i) steps[i] = tr_ring.at.step_of(i);
+        tr_ring.at.drain();
         return FS_OK;
     }
 
-    double* probe_slot(long k) const { return probe_ring + (size_t)k * (size_t)probe_n * fs::PROBE_VALUES; }
+    double* probe_slot(long k) const { return (double*)probe_ring.slot(k); }
 
     // set up the probe list and (re)allocate and clear the ring after fs_set_probes / fs_set_option("probe_log")
     int ensure_probe_ring()
     {
-        if (probe_gen == S->probe_gen) return FS_OK;
-        if (probe_idx || probe_ring) HIP_TRY(hipStreamSynchronize(S->stream));   // a queued record may still use what is freed here
-        if (probe_idx) HIP_TRY(hipFree(probe_idx));
-        if (probe_ring) HIP_TRY(hipFree(probe_ring));
+        if (probe_ring.gen == S->probe_gen) return FS_OK;
+        if (probe_idx) {
+            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued record may still use what is freed here
+            HIP_TRY(hipFree(probe_idx));
+        }
         probe_idx = nullptr;
-        probe_ring = nullptr;
-        probe_n = probe_cap = 0;
-        probe_logged = 0;
-        probe_step.clear();
-        probe_gen = S->probe_gen;
+        probe_n = 0;
+        HIP_TRY(probe_ring.setup(S->stream, S->probe_gen));   // off
         const int n = (int)(S->probes.size() / 3);
         if (n == 0 || S->probe_log <= 0) return FS_OK;
         // the owner of a probe is the rank that owns its global plane (z = 0: the first, z = D + 1: the last)
@@ -2603,15 +2589,11 @@ struct Engine : EngineBase {
             const bool mine = (zl >= 1 && zl <= g.D) || (z == 0 && sc.lo_wall) || (z == sc.Dglobal + 1 && sc.hi_wall);
             idx[(size_t)k] = mine ? (long)x + (long)y * g.sy + (long)zl * g.sz : -1;
         }
-        const size_t bytes = (size_t)S->probe_log * (size_t)n * fs::PROBE_VALUES * sizeof(double);
         HIP_TRY(hipMalloc((void**)&probe_idx, idx.size() * sizeof(long)));
-        HIP_TRY(hipMalloc((void**)&probe_ring, bytes));
         HIP_TRY(hipMemcpyAsync(probe_idx, idx.data(), idx.size() * sizeof(long), hipMemcpyHostToDevice, S->stream));
-        HIP_TRY(hipMemsetAsync(probe_ring, 0, bytes, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));        // `idx` goes out of scope
         probe_n = n;
-        probe_cap = S->probe_log;
-        probe_step.assign((size_t)probe_cap, 0);
+        HIP_TRY(probe_ring.setup(S->stream, S->probe_gen, S->probe_log, (size_t)n * fs::PROBE_VALUES * sizeof(double)));
         return FS_OK;
     }
 
@@ -2621,16 +2603,16 @@ struct Engine : EngineBase {
         {
             ScopedSpan sp(S, FAM_PROBES);
             fs::launch_probe_record<T>(S->stream, probe_n, probe_idx, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]],
-                                       arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], probe_slot(probe_logged % probe_cap));
+                                       arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], probe_slot(probe_ring.at.next()));
         }
-        probe_step[(size_t)(probe_logged++ % probe_cap)] = S->steps_total;
+        probe_ring.at.commit(S->steps_total);
     }
 
     int probe_sample() override
     {
         int rc = ensure_probe_ring();
         if (rc) return rc;
-        if (probe_cap == 0) return fail(FS_EINVAL, "fs_probe_sample: no probes are set (fs_set_probes), or option \"probe_log\" is 0");
+        if (!probe_ring.on()) return fail(FS_EINVAL, "fs_probe_sample: no probes are set (fs_set_probes), or option \"probe_log\" is 0");
         probe_record();
         return FS_OK;
     }
@@ -2639,21 +2621,16 @@ struct Engine : EngineBase {
     {
         int rc = ensure_probe_ring();
         if (rc) return rc;
-        const long n = probe_cap > 0 ? std::min<long>(probe_logged, probe_cap) : 0;
+        const long n = probe_ring.at.retained();
         if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = probe_logged - n;
+        if (n_dropped) *n_dropped = probe_ring.at.dropped();
         if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
         if (max_rows < n) return fail(FS_EINVAL, "fs_probe_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "probe records need the other slabs' planes; the FSNULL transport carries none");
         const size_t per = (size_t)probe_n * fs::PROBE_VALUES;   // one record
-        const long first = probe_logged - n;
         std::vector<double> mine((size_t)n * per), all;
-        if (n > 0) {                                     // the retained records are one run of ring slots, or two where it wraps
-            const long start = first % probe_cap, run = std::min<long>(n, probe_cap - start);
-            HIP_TRY(hipMemcpyAsync(mine.data(), probe_slot(start), (size_t)run * per * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-            if (run < n)
-                HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)run * per, probe_slot(0), (size_t)(n - run) * per * sizeof(double),
-                                       hipMemcpyDeviceToHost, S->stream));
+        if (n > 0) {
+            HIP_TRY(probe_ring.copy_out(S->stream, mine.data()));
             HIP_TRY(hipStreamSynchronize(S->stream));
         }
         if ((rc = gather_plane_records(mine, all, "probe records"))) return rc;
@@ -2668,12 +2645,12 @@ struct Engine : EngineBase {
         const size_t cols = 1 + per;
         for (long i = 0; i < n; ++i) {
             double* o = rows + (size_t)i * cols;
-            o[0] = (double)probe_step[(size_t)((first + i) % probe_cap)];
+            o[0] = (double)probe_ring.at.step_of(i);
             for (int k = 0; k < probe_n; ++k)
                 for (int j = 0; j < fs::PROBE_VALUES; ++j)
                     o[1 + (size_t)k * fs::PROBE_VALUES + j] = all[owner_off[(size_t)k] + (size_t)i * per + j];
         }
-        probe_logged = 0;                                // drained
+        probe_ring.at.drain();
         return FS_OK;
     }
 
@@ -2803,17 +2780,8 @@ struct Engine : EngineBase {
     // that a record in mid-step allocates nothing: the scratch images, the vortex array, the staging of a statistics source
     int ensure_image_ring()
     {
-        if (img_gen == S->image_gen) return img_cap > 0 ? ensure_image_scratch() : FS_OK;   // a new colour table
-        if (img_ring) {
-            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued frame may still use what is freed here
-            HIP_TRY(hipFree(img_ring));
-        }
-        img_ring = nullptr;
-        img_cap = 0;
-        img_frame_bytes = 0;
-        img_logged = 0;
-        img_step.clear();
-        img_gen = S->image_gen;
+        if (img_ring.gen == S->image_gen) return img_ring.on() ? ensure_image_scratch() : FS_OK;   // a new colour table
+        HIP_TRY(img_ring.setup(S->stream, S->image_gen));   // off, whatever fails below
         if (S->image_views.empty() || S->image_log <= 0) return FS_OK;
         if (S->comm.active()) return fail(FS_EINVAL, "the image log needs a single-GPU handle");
         int rc = ensure_image_scratch();
@@ -2826,19 +2794,16 @@ struct Engine : EngineBase {
             if ((v.source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (rc = ensure_vort("fs_image_views"))) return rc;
             if ((v.source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT && (rc = need_dense(stat_bytes()))) return rc;
         }
-        const hipError_t e = hipMalloc((void**)&img_ring, (size_t)S->image_log * bytes);
-        if (e != hipSuccess) return fail(FS_ENOMEM, "image_log: %d frames of %zu bytes: %s", S->image_log, bytes, hipGetErrorString(e));
-        HIP_TRY(hipMemsetAsync(img_ring, 0, (size_t)S->image_log * bytes, S->stream));
-        img_cap = S->image_log;
-        img_frame_bytes = bytes;
-        img_step.assign((size_t)img_cap, 0);
+        const hipError_t e = img_ring.setup(S->stream, S->image_gen, S->image_log, bytes);
+        if (e != hipSuccess && !img_ring.base) return fail(FS_ENOMEM, "image_log: %d frames of %zu bytes: %s", S->image_log, bytes, hipGetErrorString(e));
+        HIP_TRY(e);
         return FS_OK;
     }
 
     // one frame of the state as it is now into the next ring slot: every view's kernels, then its colouring
     int image_record()
     {
-        uint8_t* dst = img_ring + (size_t)(img_logged % img_cap) * img_frame_bytes;
+        uint8_t* dst = (uint8_t*)img_ring.slot(img_ring.at.next());
         for (const ImageView& v : S->image_views) {
             int c, r;
             fs::image_dims(v.axis, g.W, g.H, g.D, &c, &r);
@@ -2849,7 +2814,7 @@ struct Engine : EngineBase {
             fs::launch_image_colour(S->stream, (long)c * r, img_val, flag, v.vmin, v.vmax, v.alpha, img_table, img_table_n, dst);
             dst += 3 * (size_t)c * (size_t)r;
         }
-        img_step[(size_t)(img_logged++ % img_cap)] = S->steps_total;
+        img_ring.at.commit(S->steps_total);
         return FS_OK;
     }
 
@@ -2857,7 +2822,7 @@ struct Engine : EngineBase {
     {
         int rc = ensure_image_ring();
         if (rc) return rc;
-        if (img_cap == 0) return fail(FS_EINVAL, "fs_image_sample: no views are set (fs_image_views), or option \"image_log\" is 0");
+        if (!img_ring.on()) return fail(FS_EINVAL, "fs_image_sample: no views are set (fs_image_views), or option \"image_log\" is 0");
         return image_record();
     }
 
@@ -2865,47 +2830,31 @@ struct Engine : EngineBase {
     {
         int rc = ensure_image_ring();
         if (rc) return rc;
-        const long n = img_cap > 0 ? std::min<long>(img_logged, img_cap) : 0;
+        const long n = img_ring.at.retained();
         if (n_frames) *n_frames = n;
-        if (n_dropped) *n_dropped = img_logged - n;
+        if (n_dropped) *n_dropped = img_ring.at.dropped();
         if (!frames) return FS_OK;                       // sizes only: nothing drained
         if (max_frames < n) return fail(FS_EINVAL, "fs_image_log: %ld frames retained, room for %ld (pass frames = NULL to ask)", n, max_frames);
-        const long first = img_logged - n;
-        if (n > 0) {                                     // the retained frames are one run of ring slots, or two where it wraps
-            const long start = first % img_cap, run = std::min<long>(n, img_cap - start);
-            HIP_TRY(hipMemcpyAsync(frames, img_ring + (size_t)start * img_frame_bytes, (size_t)run * img_frame_bytes, hipMemcpyDeviceToHost, S->stream));
-            if (run < n)
-                HIP_TRY(hipMemcpyAsync(frames + (size_t)run * img_frame_bytes, img_ring, (size_t)(n - run) * img_frame_bytes,
-                                       hipMemcpyDeviceToHost, S->stream));
+        if (n > 0) {
+            HIP_TRY(img_ring.copy_out(S->stream, frames));
             HIP_TRY(hipStreamSynchronize(S->stream));
         }
         if (steps)
-            for (long i = 0; i < n; ++i) steps[i] = img_step[(size_t)((first + i) % img_cap)];
-        img_logged = 0;                                  // drained
+            for (long i = 0; i < n; ++i) steps[i] = img_ring.at.step_of(i);
+        img_ring.at.drain();
         return FS_OK;
     }
 
     // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
     // ring slot k, projection j: g.D plane records
-    double* force_slot(long k, int j) const { return force_ring + ((size_t)k * 2 + (size_t)j) * plane_doubles(); }
+    double* force_slot(long k, int j) const { return (double*)force_ring.slot(k) + (size_t)j * plane_doubles(); }
     size_t plane_doubles() const { return (size_t)fs::FORCE_REC * (size_t)g.D; }
 
     // (re)allocate and clear the ring after fs_set_option("force_log")
     int ensure_force_ring()
     {
-        if (force_gen == S->force_log_gen) return FS_OK;
-        if (force_ring) HIP_TRY(hipFree(force_ring));
-        force_ring = nullptr;
-        force_cap = 0;
-        force_logged = 0;
-        force_step.clear();
-        force_gen = S->force_log_gen;
-        if (S->force_log <= 0) return FS_OK;
-        const size_t bytes = (size_t)S->force_log * 2 * plane_doubles() * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&force_ring, bytes));
-        HIP_TRY(hipMemsetAsync(force_ring, 0, bytes, S->stream));
-        force_cap = S->force_log;
-        force_step.assign((size_t)force_cap, 0);
+        if (force_ring.gen == S->force_log_gen) return FS_OK;
+        HIP_TRY(force_ring.setup(S->stream, S->force_log_gen, S->force_log, 2 * plane_doubles() * sizeof(double)));
         return FS_OK;
     }
 
@@ -2961,18 +2910,15 @@ struct Engine : EngineBase {
     {
         int rc = ensure_force_ring();
         if (rc) return rc;
-        const long n = force_cap > 0 ? std::min<long>(force_logged, force_cap) : 0;
+        const long n = force_ring.at.retained();
         if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = force_logged - n;
+        if (n_dropped) *n_dropped = force_ring.at.dropped();
         if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
         if (max_rows < n) return fail(FS_EINVAL, "fs_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
         const size_t per = 2 * plane_doubles();   // one step: both projections
-        const long first = force_logged - n;
         std::vector<double> mine((size_t)n * per), all;
-        for (long i = 0; i < n; ++i)
-            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, force_slot((first + i) % force_cap, 0), per * sizeof(double),
-                                   hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(force_ring.copy_out(S->stream, mine.data()));
         HIP_TRY(hipStreamSynchronize(S->stream));
         if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
         const size_t blob = mine.size();
@@ -2982,7 +2928,7 @@ struct Engine : EngineBase {
                 combine_planes([&](int r, int zl) {
                     return &all[(size_t)r * blob + (size_t)i * per + (size_t)j * (per / 2) + (size_t)zl * fs::FORCE_REC]; }, s[j]);
             double* o = rows + (size_t)i * FS_FORCE_LOG_COLS;
-            o[0] = (double)force_step[(size_t)((first + i) % force_cap)];
+            o[0] = (double)force_ring.at.step_of(i);
             for (int k = 0; k < 3; ++k) {
                 o[1 + k] = s[0][k];
                 o[4 + k] = s[1][k];
@@ -2990,7 +2936,7 @@ struct Engine : EngineBase {
             o[7] = s[1][3];
             o[8] = s[1][4];
         }
-        force_logged = 0;                                // drained
+        force_ring.at.drain();
         return FS_OK;
     }
 
@@ -3084,13 +3030,13 @@ struct Engine : EngineBase {
         HIP_TRY(hipMemcpyAsync(body_bbox, bbox, sizeof bbox, hipMemcpyHostToDevice, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));       // `bbox` and the temporaries leave scope
         bodies_dirty = false;
-        body_ring_stale = true;
+        body_ring.gen = -1;
         return FS_OK;
     }
 
     // ring slot k, projection j: body_B + 1 whole-grid records
     size_t body_slot_doubles() const { return (size_t)(body_B + 1) * fs::BODY_REC; }
-    double* body_slot(long k, int j) const { return body_ring + ((size_t)k * 2 + (size_t)j) * body_slot_doubles(); }
+    double* body_slot(long k, int j) const { return (double*)body_ring.slot(k) + (size_t)j * body_slot_doubles(); }
 
     // "body_force_log" on: label anew if obs changed; (re)allocate and clear the ring after a relabelling,
     // fs_set_option("body_force_log") and ("moment_origin").  Off: nothing is launched or allocated.
@@ -3100,20 +3046,8 @@ struct Engine : EngineBase {
             int rc = ensure_bodies();
             if (rc) return rc;
         }
-        if (body_gen == S->body_log_gen && !body_ring_stale) return FS_OK;
-        if (body_ring) HIP_TRY(hipFree(body_ring));
-        body_ring = nullptr;
-        body_cap = 0;
-        body_logged = 0;
-        body_step.clear();
-        body_gen = S->body_log_gen;
-        body_ring_stale = false;
-        if (S->body_log <= 0) return FS_OK;
-        const size_t bytes = (size_t)S->body_log * 2 * body_slot_doubles() * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&body_ring, bytes));
-        HIP_TRY(hipMemsetAsync(body_ring, 0, bytes, S->stream));
-        body_cap = S->body_log;
-        body_step.assign((size_t)body_cap, 0);
+        if (body_ring.gen == S->body_log_gen) return FS_OK;
+        HIP_TRY(body_ring.setup(S->stream, S->body_log_gen, S->body_log, 2 * body_slot_doubles() * sizeof(double)));
         return FS_OK;
     }
 
@@ -3182,29 +3116,22 @@ struct Engine : EngineBase {
         if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
         int rc = ensure_body_ring();
         if (rc) return rc;
-        const long steps = body_cap > 0 ? std::min<long>(body_logged, body_cap) : 0;
+        const long steps = body_ring.at.retained();
         const long nrec = body_B + 1, n = steps * nrec;
         if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = body_logged - steps;
+        if (n_dropped) *n_dropped = body_ring.at.dropped();
         if (!rows) return FS_OK;                         // sizes only: nothing drained
         if (max_rows < n) return fail(FS_EINVAL, "fs_body_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
         const size_t per = 2 * body_slot_doubles();      // one step: both projections
-        const long first = body_logged - steps;
         std::vector<double> mine((size_t)steps * per);
-        // the retained steps are at most two runs of consecutive slots (where the ring wraps): at most two copies
-        for (long i = 0; i < steps;) {
-            const long s0 = (first + i) % body_cap, run = std::min<long>(steps - i, body_cap - s0);
-            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, body_slot(s0, 0), (size_t)run * per * sizeof(double),
-                                   hipMemcpyDeviceToHost, S->stream));
-            i += run;
-        }
+        HIP_TRY(body_ring.copy_out(S->stream, mine.data()));
         HIP_TRY(hipStreamSynchronize(S->stream));
         for (long i = 0; i < steps; ++i)
             for (long k = 0; k < nrec; ++k) {
                 const double* a = &mine[(size_t)i * per + (size_t)k * fs::BODY_REC];
                 const double* b = a + per / 2;
                 double* o = rows + ((size_t)i * nrec + (size_t)k) * FS_BODY_LOG_COLS;
-                o[0] = (double)body_step[(size_t)((first + i) % body_cap)];
+                o[0] = (double)body_ring.at.step_of(i);
                 o[1] = (double)k;
                 for (int c = 0; c < 6; ++c) {
                     o[2 + c] = a[c];
@@ -3213,7 +3140,7 @@ struct Engine : EngineBase {
                 o[14] = b[6];
                 o[15] = b[7];
             }
-        body_logged = 0;                                 // drained
+        body_ring.at.drain();
         return FS_OK;
     }
 
@@ -3221,7 +3148,7 @@ struct Engine : EngineBase {
     static constexpr int RES_SOLVES = FS_RESIDUAL_LOG_SOLVES;
     size_t res_plane_doubles() const { return (size_t)fs::RESIDUAL_REC * (size_t)g.D; }
     // ring slot k, solve j, when = 0 before the first sweep / 1 after the last: g.D plane records
-    double* res_slot(long k, int j, int when) const { return res_ring + (((size_t)k * RES_SOLVES + (size_t)j) * 2 + (size_t)when) * res_plane_doubles(); }
+    double* res_slot(long k, int j, int when) const { return (double*)res_ring.slot(k) + ((size_t)j * 2 + (size_t)when) * res_plane_doubles(); }
 
     int ensure_res_partial()
     {
@@ -3232,23 +3159,12 @@ struct Engine : EngineBase {
     // (re)allocate and clear the ring after fs_set_option("residual_log")
     int ensure_residual_ring()
     {
-        if (res_gen == S->residual_log_gen) return FS_OK;
-        if (res_ring) HIP_TRY(hipFree(res_ring));
-        res_ring = nullptr;
-        res_cap = 0;
-        res_logged = 0;
-        res_step.clear();
-        res_ran.clear();
-        res_gen = S->residual_log_gen;
+        if (res_ring.gen == S->residual_log_gen) return FS_OK;
+        HIP_TRY(res_ring.setup(S->stream, S->residual_log_gen));   // off, whatever fails below
         if (S->residual_log <= 0) return FS_OK;
         int rc = ensure_res_partial();
         if (rc) return rc;
-        const size_t bytes = (size_t)S->residual_log * RES_SOLVES * 2 * res_plane_doubles() * sizeof(double);
-        HIP_TRY(hipMalloc((void**)&res_ring, bytes));
-        HIP_TRY(hipMemsetAsync(res_ring, 0, bytes, S->stream));
-        res_cap = S->residual_log;
-        res_step.assign((size_t)res_cap, 0);
-        res_ran.assign((size_t)res_cap, 0u);
+        HIP_TRY(res_ring.setup(S->stream, S->residual_log_gen, S->residual_log, (size_t)RES_SOLVES * 2 * res_plane_doubles() * sizeof(double)));
         return FS_OK;
     }
 
@@ -3257,9 +3173,9 @@ struct Engine : EngineBase {
     // producer of x exchanged them (advection, inlet, the zeroed pressure), and so does the last pass of every solve.
     int log_residual(int k, int when, int b, int x, int rhs, double a, double c)
     {
-        if (k < 0 || res_cap <= 0 || !in_step) return FS_OK;
+        if (k < 0 || !res_ring.on() || !in_step) return FS_OK;
         ScopedSpan sp(S, FAM_RESIDUAL);
-        fs::launch_residual<T>(S->stream, g, b, arr[x], arr[rhs], flags, a, c, res_partial, res_slot(res_logged % res_cap, k, when));
+        fs::launch_residual<T>(S->stream, g, b, arr[x], arr[rhs], flags, a, c, res_partial, res_slot(res_ring.at.next(), k, when));
         if (when == 1) res_ran_now |= 1u << k;
         return FS_OK;
     }
@@ -3301,29 +3217,25 @@ struct Engine : EngineBase {
     {
         int rc = ensure_residual_ring();
         if (rc) return rc;
-        const long n = res_cap > 0 ? std::min<long>(res_logged, res_cap) : 0;
+        const long n = res_ring.at.retained();
         if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = res_logged - n;
+        if (n_dropped) *n_dropped = res_ring.at.dropped();
         if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
         if (max_rows < n) return fail(FS_EINVAL, "fs_residual_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
         const size_t rec = res_plane_doubles(), per = (size_t)RES_SOLVES * 2 * rec;   // one step: six solves, before and after
-        const long first = res_logged - n;
         std::vector<double> mine((size_t)n * per), all;
-        for (long i = 0; i < n; ++i)
-            HIP_TRY(hipMemcpyAsync(mine.data() + (size_t)i * per, res_slot((first + i) % res_cap, 0, 0), per * sizeof(double),
-                                   hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(res_ring.copy_out(S->stream, mine.data()));
         HIP_TRY(hipStreamSynchronize(S->stream));
         if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
         const size_t blob = mine.size();
         const double nan = std::nan("");
         for (long i = 0; i < n; ++i) {
             double* o = rows + (size_t)i * FS_RESIDUAL_LOG_COLS;
-            const size_t slot_i = (size_t)((first + i) % res_cap);
-            o[0] = (double)res_step[slot_i];
+            o[0] = (double)res_ring.at.step_of(i);
             for (int j = 0; j < RES_SOLVES; ++j) {
                 double* q = o + 1 + 5 * j;               // r0_sq, r_sq, r_max, rhs_sq, cells
-                if (!(res_ran[slot_i] >> j & 1u)) { q[0] = q[1] = q[2] = q[3] = nan; q[4] = 0.0; continue; }
+                if (!(res_ring.at.tag_of(i) >> j & 1u)) { q[0] = q[1] = q[2] = q[3] = nan; q[4] = 0.0; continue; }
                 double s[2][fs::RESIDUAL_REC];
                 for (int when = 0; when < 2; ++when)
                     combine_planes([&](int r, int zl) {
@@ -3336,7 +3248,7 @@ struct Engine : EngineBase {
                 q[4] = s[1][3];
             }
         }
-        res_logged = 0;                                  // drained
+        res_ring.at.drain();
         return FS_OK;
     }
 };
