@@ -52,6 +52,13 @@ TRACER_FREE, TRACER_ALIVE, TRACER_OUT, TRACER_HIT = range(4)
 TRACER_STATUS_NAMES = ["free", "alive", "out", "hit"]
 TRACER_EMITTERS_MAX = 4096
 TRACER_FRAME_BYTES = 28
+# FS_VOLUME_*: camera slots and log views of the volume renderer, entries of a view's parameters and of a camera, and the
+# most samples a ray may take through the box
+VOLUME_CAMERAS_MAX = 4
+VOLUME_VIEWS_MAX = 4
+VOLUME_PARAMS = 11      # vmin, vmax, opacity, step, t_min, obstacle r g b, background r g b
+VOLUME_CAMERA = 11      # eye[3], target[3], up[3], half_height, ortho
+VOLUME_SAMPLES_MAX = 16384
 
 
 class FluidsimError(RuntimeError):
@@ -139,6 +146,12 @@ _SIGNATURES = {
     "fs_tracer_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]),
     "fs_tracer_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long),
                                 C.POINTER(C.c_long)]),
+    "fs_volume_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "fs_volume_camera": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "fs_volume_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "fs_volume_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_volume_sample": (C.c_int, [C.c_void_p]),
+    "fs_volume_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "fs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fs_comm_selftest": (C.c_int, []),

@@ -18,6 +18,7 @@
 #include "forces.h"
 #include "bodies.h"
 #include "image.h"
+#include "volume.h"
 #include "tracers.h"
 #include "residual.h"
 #include "flow_stats.h"
@@ -68,8 +69,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -135,6 +136,11 @@ struct EngineBase {
     virtual int image_config() = 0;            // apply fs_image_views / fs_set_option("image_log"): allocate or free, clear
     virtual int image_sample() = 0;
     virtual int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
+    virtual int volume_rays(int slot, const double* rays, int cols, int rows) = 0;
+    virtual int volume_render(int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc) = 0;
+    virtual int volume_config() = 0;           // apply fs_volume_views / fs_volume_rays / fs_set_option("volume_log"): allocate or free, clear
+    virtual int volume_sample() = 0;
+    virtual int volume_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
     virtual int tracer_config() = 0;           // apply fs_set_option("tracers") / ("tracer_log"): allocate or free, clear
     virtual int tracer_seed(const double* xyz, long n) = 0;
     virtual int tracer_clear() = 0;
@@ -148,6 +154,12 @@ struct EngineBase {
 struct ImageView {
     int source, kind, axis, index;
     double vmin, vmax, alpha;
+};
+
+// one view of the volume log (fs_volume_views)
+struct VolumeLogView {
+    int source, slot;
+    double par[fs::VOLUME_PARAMS];
 };
 
 struct fs_sim {
@@ -229,6 +241,11 @@ struct fs_sim {
     long image_gen = 0;          // bumped by fs_image_views and fs_set_option("image_log"): the ring is set up anew, the log is cleared
     std::vector<uint8_t> image_table;   // fs_image_colormap: n RGB triples; empty = the built-in table
     long image_table_gen = 0;    // bumped by fs_image_colormap
+    int vol_cols[fs::VOLUME_CAMERAS_MAX] = {0, 0, 0, 0}, vol_rows[fs::VOLUME_CAMERAS_MAX] = {0, 0, 0, 0};   // the ray set of each camera slot, 0 = free
+    std::vector<VolumeLogView> volume_views;   // fs_volume_views
+    int volume_log = 0;          // "volume_log": frames the volume log keeps, 0 = off
+    long volume_every = 1;       // "volume_every": fs_step takes a frame when (steps_total - 1) % volume_every == 0
+    long volume_gen = 0;         // bumped by fs_volume_views, fs_set_option("volume_log") and a new ray set of a slot a view uses
     int tracers = 0;             // "tracers": slots of the tracer pool, 0 = off
     long tracer_gen = 0;         // bumped by fs_set_option("tracers"): pool and log are set up anew and cleared
     int tracer_log = 0;          // "tracer_log": snapshot frames the tracer log keeps, 0 = off
@@ -370,6 +387,15 @@ size_t image_frame_bytes(const fs_sim* s, const std::vector<ImageView>& views)
     return bytes;
 }
 
+// bytes of one frame of the volume log: the views' RGB images one after the other; `slot`, cols, rows: a slot about to change
+size_t volume_frame_bytes(const fs_sim* s, const std::vector<VolumeLogView>& views, int slot = -1, int cols = 0, int rows = 0)
+{
+    size_t bytes = 0;
+    for (const VolumeLogView& v : views)
+        bytes += v.slot == slot ? 3 * (size_t)cols * (size_t)rows : 3 * (size_t)s->vol_cols[v.slot] * (size_t)s->vol_rows[v.slot];
+    return bytes;
+}
+
 template <class T> T host_cbrt(T v);
 template <> float host_cbrt<float>(float v) { return std::cbrt(v); }     // std::cbrt(float), simulation.cpp:295
 template <> double host_cbrt<double>(double v) { return std::cbrt(v); }
@@ -461,6 +487,14 @@ struct Engine : EngineBase {
     int img_table_n = 0;
     long img_table_gen = -1;            // S->image_table_gen the device table holds
     LogRing img_ring;                   // for S->image_gen
+    // volume rendering (volume.h): the ray set of each camera slot, the staging images of fs_volume_render (grown on demand),
+    // and the per-step log, a device ring of frames (the views' RGB images one after the other).  The colour table is the
+    // image entries' (img_table).
+    double* vol_rays[fs::VOLUME_CAMERAS_MAX] = {nullptr, nullptr, nullptr, nullptr};
+    uint8_t* vol_rgb = nullptr;
+    double* vol_acc = nullptr;
+    size_t vol_room = 0;                // pixels the two staging images have room for
+    LogRing vol_ring;                   // for S->volume_gen
     // tracer particles (tracers.h): the pool (positions as the sampler's point list, four meta words per slot), the emitters'
     // points, and the snapshot log, a device ring of frames (all position frames, then all status frames)
     double* tr_xyz = nullptr;
@@ -612,9 +646,13 @@ struct Engine : EngineBase {
         if (tr_meta) hipFree(tr_meta);
         if (tr_emit) hipFree(tr_emit);
         if (tr_out) hipFree(tr_out);
+        for (double* q : vol_rays)
+            if (q) hipFree(q);
+        if (vol_rgb) hipFree(vol_rgb);
+        if (vol_acc) hipFree(vol_acc);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
             if (q) hipFree(q);
-        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring }) r->release();
+        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring }) r->release();
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1576,6 +1614,7 @@ struct Engine : EngineBase {
         if ((rc = ensure_probe_ring())) return rc;
         if ((rc = ensure_body_ring())) return rc;
         if ((rc = ensure_image_ring())) return rc;
+        if ((rc = ensure_volume_ring())) return rc;
         if ((rc = ensure_tracers())) return rc;
         res_ran_now = 0;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
@@ -1664,6 +1703,8 @@ struct Engine : EngineBase {
         if (probe_ring.on()) probe_record();
         // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
         if (img_ring.on() && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
+        // "volume_log": and a frame of the volume views (one launch per view, no host synchronisation, the step's own stream)
+        if (vol_ring.on() && (S->steps_total - 1) % S->volume_every == 0 && (rc = volume_record())) return rc;
         // "tracers": the particles move through the same state, the emitters release, a snapshot is taken (one launch, no host
         // synchronisation, the step's own stream)
         if (tr_cap > 0)
@@ -2845,6 +2886,143 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- volume rendering (volume.h; the reference's 3-D viewer, GUI/gl_widget.py, renders no volume) -------------------
+    // A slot's ray set: uploaded into a new array, then the old one goes (a queued frame may still read it: the stream is
+    // synchronised first).  cols = rows = 0 frees the slot.  The arguments are checked by fs_volume_rays.
+    int volume_rays(int slot, const double* rays, int cols, int rows) override
+    {
+        double* fresh = nullptr;
+        const size_t bytes = (size_t)cols * (size_t)rows * 6 * sizeof(double);
+        if (bytes > 0) {
+            const hipError_t e = hipMalloc((void**)&fresh, bytes);
+            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_volume_rays: %d x %d rays: %s", cols, rows, hipGetErrorString(e));
+            hipError_t c = hipMemcpyAsync(fresh, rays, bytes, hipMemcpyHostToDevice, S->stream);
+            if (c == hipSuccess) c = hipStreamSynchronize(S->stream);   // `rays` may be freed by the caller
+            if (c != hipSuccess) { hipFree(fresh); HIP_TRY(c); }
+        }
+        if (vol_rays[slot]) {
+            HIP_TRY(hipStreamSynchronize(S->stream));
+            HIP_TRY(hipFree(vol_rays[slot]));
+        }
+        vol_rays[slot] = fresh;
+        return FS_OK;
+    }
+
+    // one view of the state as it is now: one launch.  The arguments are checked; rgb / acc are device arrays, either may be null.
+    int volume_launch(const char* who, int source, int cam, const double* par, uint8_t* rgb, double* acc)
+    {
+        fs::VolumeView vw = {};
+        if (!fs::volume_params_ok(par, g.W, g.H, g.D, &vw.kmax)) return fail(FS_EINVAL, "%s: bad view parameters", who);
+        for (int k = 0; k < fs::VOLUME_PARAMS; ++k) vw.par[k] = par[k];
+        vw.n = img_table_n;
+        const T* field = nullptr;
+        const double* stat = nullptr;
+        const int rc = resolve_source(who, source, field, stat);
+        if (rc) return rc;
+        const T* obs = arr[slot[FS_OBS]];
+        const int cols = S->vol_cols[cam], rows = S->vol_rows[cam];
+        if (stat) fs::launch_volume<double, T>(S->stream, g, vw, cols, rows, vol_rays[cam], stat, obs, img_table, rgb, acc);
+        else fs::launch_volume<T, T>(S->stream, g, vw, cols, rows, vol_rays[cam], field, obs, img_table, rgb, acc);
+        return FS_OK;
+    }
+
+    int volume_render(int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc) override
+    {
+        const size_t npix = (size_t)S->vol_cols[slot] * (size_t)S->vol_rows[slot];
+        int rc = ensure_image_scratch();                 // the colour table
+        if (rc) return rc;
+        if (npix > vol_room) {
+            if (vol_rgb) {
+                HIP_TRY(hipStreamSynchronize(S->stream));
+                HIP_TRY(hipFree(vol_rgb));
+                HIP_TRY(hipFree(vol_acc));
+            }
+            vol_rgb = nullptr;
+            vol_acc = nullptr;
+            vol_room = 0;
+            hipError_t e = hipMalloc((void**)&vol_acc, npix * 4 * sizeof(double));
+            if (e == hipSuccess && (e = hipMalloc((void**)&vol_rgb, npix * 3)) != hipSuccess) {
+                hipFree(vol_acc);
+                vol_acc = nullptr;
+            }
+            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_volume_render: %zu pixels: %s", npix, hipGetErrorString(e));
+            vol_room = npix;
+        }
+        {
+            ScopedSpan sp(S, FAM_MISC);
+            if ((rc = volume_launch("fs_volume_render", source, slot, par, rgb ? vol_rgb : nullptr, acc ? vol_acc : nullptr))) return rc;
+        }
+        if (rgb) HIP_TRY(hipMemcpyAsync(rgb, vol_rgb, n_bytes, hipMemcpyDeviceToHost, S->stream));
+        if (acc) HIP_TRY(hipMemcpyAsync(acc, vol_acc, n_acc * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
+    int volume_config() override { return ensure_volume_ring(); }
+
+    // (re)allocate and clear the ring after fs_volume_views / fs_volume_rays / fs_set_option("volume_log"), and set up whatever a
+    // view needs, so that a record in mid-step allocates nothing: the colour table, the vortex array, the staging of a
+    // statistics source
+    int ensure_volume_ring()
+    {
+        if (vol_ring.gen == S->volume_gen) return vol_ring.on() ? ensure_image_scratch() : FS_OK;   // a new colour table
+        HIP_TRY(vol_ring.setup(S->stream, S->volume_gen));   // off, whatever fails below
+        if (S->volume_views.empty() || S->volume_log <= 0) return FS_OK;
+        if (S->comm.active()) return fail(FS_EINVAL, "the volume log needs a single-GPU handle");
+        int rc = ensure_image_scratch();
+        if (rc) return rc;
+        for (const VolumeLogView& v : S->volume_views) {
+            if ((v.source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (rc = ensure_vort("fs_volume_views"))) return rc;
+            if ((v.source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT && (rc = need_dense(stat_bytes()))) return rc;
+        }
+        const size_t bytes = volume_frame_bytes(S, S->volume_views);
+        const hipError_t e = vol_ring.setup(S->stream, S->volume_gen, S->volume_log, bytes);
+        if (e != hipSuccess && !vol_ring.base) return fail(FS_ENOMEM, "volume_log: %d frames of %zu bytes: %s", S->volume_log, bytes, hipGetErrorString(e));
+        HIP_TRY(e);
+        return FS_OK;
+    }
+
+    // one frame of the state as it is now into the next ring slot: one launch per view
+    int volume_record()
+    {
+        uint8_t* dst = (uint8_t*)vol_ring.slot(vol_ring.at.next());
+        for (const VolumeLogView& v : S->volume_views) {
+            ScopedSpan sp(S, FAM_VOLUME);
+            const int rc = volume_launch("the volume log", v.source, v.slot, v.par, dst, nullptr);
+            if (rc) return rc;
+            dst += 3 * (size_t)S->vol_cols[v.slot] * (size_t)S->vol_rows[v.slot];
+        }
+        vol_ring.at.commit(S->steps_total);
+        return FS_OK;
+    }
+
+    int volume_sample() override
+    {
+        int rc = ensure_volume_ring();
+        if (rc) return rc;
+        if (!vol_ring.on()) return fail(FS_EINVAL, "fs_volume_sample: no views are set (fs_volume_views), or option \"volume_log\" is 0");
+        return volume_record();
+    }
+
+    int volume_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) override
+    {
+        int rc = ensure_volume_ring();
+        if (rc) return rc;
+        const long n = vol_ring.at.retained();
+        if (n_frames) *n_frames = n;
+        if (n_dropped) *n_dropped = vol_ring.at.dropped();
+        if (!frames) return FS_OK;                       // sizes only: nothing drained
+        if (max_frames < n) return fail(FS_EINVAL, "fs_volume_log: %ld frames retained, room for %ld (pass frames = NULL to ask)", n, max_frames);
+        if (n > 0) {
+            HIP_TRY(vol_ring.copy_out(S->stream, frames));
+            HIP_TRY(hipStreamSynchronize(S->stream));
+        }
+        if (steps)
+            for (long i = 0; i < n; ++i) steps[i] = vol_ring.at.step_of(i);
+        vol_ring.at.drain();
+        return FS_OK;
+    }
+
     // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
     // ring slot k, projection j: g.D plane records
     double* force_slot(long k, int j) const { return (double*)force_ring.slot(k) + (size_t)j * plane_doubles(); }
@@ -3460,6 +3638,24 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (s->comm.active()) return fail(FS_EINVAL, "tracer_every: tracers need a single-GPU handle");
         if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "tracer_every: K >= 1");
         s->tracer_every = n;
+    } else if (k == "volume_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > 65536) return fail(FS_EINVAL, "volume_log: frames kept, 0 (off) .. 65536");
+        if ((size_t)n * volume_frame_bytes(s, s->volume_views) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "volume_log: %ld frames of %zu bytes exceed 1 GiB", n, volume_frame_bytes(s, s->volume_views));
+        if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "volume_log: volumes are rendered on a single-GPU handle");
+        s->volume_log = (int)n;
+        s->volume_gen++;
+        if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
+            hipSetDevice(s->device);
+            return s->eng->volume_config();
+        }
+    } else if (k == "volume_every") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "volume_every: K >= 1");
+        s->volume_every = n;
     } else if (k == "image_every") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -3604,6 +3800,8 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
         *out = (n == "body_count") ? b : c;
     }
     else if (n == "image_views") *out = (int)s->image_views.size();       // views set by fs_image_views
+    else if (n == "volume_views") *out = (int)s->volume_views.size();     // views set by fs_volume_views
+    else if (n == "volume_frame_bytes") *out = (int)volume_frame_bytes(s, s->volume_views);   // one frame of the volume log
     else if (n == "image_frame_bytes") *out = (int)image_frame_bytes(s, s->image_views);   // one frame of the image log
     else if (n == "tracer_capacity") *out = s->tracers;                    // slots of the tracer pool
     else if (n == "tracer_count") *out = (int)std::min<long>(s->tracer_seeded, s->tracers);   // slots a fetch returns
@@ -4097,6 +4295,114 @@ int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long*
     return s->eng->image_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
 }
 
+// ---- volume rendering -------------------------------------------------------------------------------------------------------
+namespace {
+bool volume_slot_used(const fs_sim* s, int slot)
+{
+    for (const VolumeLogView& v : s->volume_views)
+        if (v.slot == slot) return true;
+    return false;
+}
+// the checks and the bookkeeping around a slot's new ray set; `who`: the entry
+int volume_set_rays(fs_sim* s, const char* who, int slot, const double* rays, int cols, int rows)
+{
+    const bool used = volume_slot_used(s, slot);
+    if (cols == 0 && used) return fail(FS_EINVAL, "%s: slot %d is used by a view of the volume log (fs_volume_views)", who, slot);
+    if (used && (size_t)s->volume_log * volume_frame_bytes(s, s->volume_views, slot, cols, rows) > ((size_t)1 << 30))
+        return fail(FS_EINVAL, "%s: %d frames (\"volume_log\") of %zu bytes exceed 1 GiB", who, s->volume_log,
+                    volume_frame_bytes(s, s->volume_views, slot, cols, rows));
+    const int rc = s->eng->volume_rays(slot, rays, cols, rows);
+    if (rc) return rc;
+    s->vol_cols[slot] = cols;
+    s->vol_rows[slot] = rows;
+    if (!used) return FS_OK;
+    s->volume_gen++;                                     // a view uses the slot: the log is cleared
+    return s->eng->volume_config();
+}
+int volume_rays_args(fs_sim* s, const char* who, int slot, int cols, int rows, bool may_free)
+{
+    if (s->comm.active()) return fail(FS_EINVAL, "%s: volumes are rendered on a single-GPU handle", who);
+    if (slot < 0 || slot >= FS_VOLUME_CAMERAS_MAX) return fail(FS_EINVAL, "%s: slot %d (0 .. %d)", who, slot, FS_VOLUME_CAMERAS_MAX - 1);
+    if (may_free && cols == 0 && rows == 0) return FS_OK;
+    if (cols < 1 || cols > fs::VOLUME_SIZE_MAX || rows < 1 || rows > fs::VOLUME_SIZE_MAX)
+        return fail(FS_EINVAL, "%s: %d x %d rays (1 .. %d each%s)", who, cols, rows, fs::VOLUME_SIZE_MAX, may_free ? "; 0 x 0 frees the slot" : "");
+    return FS_OK;
+}
+}  // namespace
+
+int fs_volume_rays(fs_sim* s, int slot, const double* rays, int cols, int rows)
+{
+    ENGINE_OR_RETURN(s);
+    const int rc = volume_rays_args(s, "fs_volume_rays", slot, cols, rows, true);
+    if (rc) return rc;
+    if (cols > 0 && !rays) return fail(FS_EINVAL, "fs_volume_rays: null rays");
+    return volume_set_rays(s, "fs_volume_rays", slot, rays, cols, rows);
+}
+int fs_volume_camera(fs_sim* s, int slot, const double* cam, int cols, int rows)
+{
+    ENGINE_OR_RETURN(s);
+    const int rc = volume_rays_args(s, "fs_volume_camera", slot, cols, rows, false);
+    if (rc) return rc;
+    if (!cam) return fail(FS_EINVAL, "fs_volume_camera: null camera");
+    fs::VolumeCamera c;
+    if (!fs::volume_camera_basis(cam, c))
+        return fail(FS_EINVAL, "fs_volume_camera: every entry finite, half_height > 0, target != eye, and up not along the view direction");
+    std::vector<double> rays((size_t)cols * (size_t)rows * 6);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) fs::volume_camera_ray(c, cols, rows, i, j, &rays[6 * ((size_t)i * (size_t)cols + (size_t)j)]);
+    return volume_set_rays(s, "fs_volume_camera", slot, rays.data(), cols, rows);
+}
+int fs_volume_render(fs_sim* s, int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc)
+{
+    ENGINE_OR_RETURN(s);
+    if (s->comm.active()) return fail(FS_EINVAL, "fs_volume_render: volumes are rendered on a single-GPU handle");
+    if (slot < 0 || slot >= FS_VOLUME_CAMERAS_MAX) return fail(FS_EINVAL, "fs_volume_render: slot %d (0 .. %d)", slot, FS_VOLUME_CAMERAS_MAX - 1);
+    if (s->vol_cols[slot] == 0) return fail(FS_EINVAL, "fs_volume_render: slot %d holds no rays (fs_volume_rays, fs_volume_camera)", slot);
+    if (!par) return fail(FS_EINVAL, "fs_volume_render: null parameters");
+    if (!fs::volume_params_ok(par, s->W, s->H, s->D, nullptr))
+        return fail(FS_EINVAL, "fs_volume_render: vmin < vmax, opacity >= 0, step > 0 with (box diagonal) / step <= %d, 0 <= t_min < 1, colours in [0, 255], all finite", FS_VOLUME_SAMPLES_MAX);
+    if (!image_source_ok(source)) return fail(FS_EINVAL, "fs_volume_render: unknown source %d", source);
+    const size_t npix = (size_t)s->vol_cols[slot] * (size_t)s->vol_rows[slot];
+    if (rgb && n_bytes != 3 * npix)
+        return fail(FS_EINVAL, "fs_volume_render: the image has %d x %d x 3 bytes, the call has room for %zu", s->vol_cols[slot], s->vol_rows[slot], n_bytes);
+    if (acc && n_acc != 4 * npix)
+        return fail(FS_EINVAL, "fs_volume_render: the image has %d x %d x 4 values, the call has room for %zu", s->vol_cols[slot], s->vol_rows[slot], n_acc);
+    return s->eng->volume_render(source, slot, par, rgb, n_bytes, acc, n_acc);
+}
+int fs_volume_views(fs_sim* s, const int* spec, const double* par, int n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (n < 0 || n > FS_VOLUME_VIEWS_MAX) return fail(FS_EINVAL, "fs_volume_views: 0 .. %d views, got %d", FS_VOLUME_VIEWS_MAX, n);
+    if (n > 0 && (!spec || !par)) return fail(FS_EINVAL, "fs_volume_views: null views");
+    if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "fs_volume_views: volumes are rendered on a single-GPU handle");
+    std::vector<VolumeLogView> views((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        VolumeLogView& v = views[(size_t)k];
+        v.source = spec[2 * k];
+        v.slot = spec[2 * k + 1];
+        for (int j = 0; j < FS_VOLUME_PARAMS; ++j) v.par[j] = par[FS_VOLUME_PARAMS * k + j];
+        if (!image_source_ok(v.source)) return fail(FS_EINVAL, "fs_volume_views: view %d: unknown source %d", k, v.source);
+        if (v.slot < 0 || v.slot >= FS_VOLUME_CAMERAS_MAX) return fail(FS_EINVAL, "fs_volume_views: view %d: slot %d (0 .. %d)", k, v.slot, FS_VOLUME_CAMERAS_MAX - 1);
+        if (s->vol_cols[v.slot] == 0) return fail(FS_EINVAL, "fs_volume_views: view %d: slot %d holds no rays (fs_volume_rays, fs_volume_camera)", k, v.slot);
+        if (!fs::volume_params_ok(v.par, s->W, s->H, s->D, nullptr)) return fail(FS_EINVAL, "fs_volume_views: view %d: bad parameters (see fs_volume_render)", k);
+    }
+    if ((size_t)s->volume_log * volume_frame_bytes(s, views) > ((size_t)1 << 30))
+        return fail(FS_EINVAL, "fs_volume_views: %d frames (\"volume_log\") of %zu bytes exceed 1 GiB", s->volume_log, volume_frame_bytes(s, views));
+    s->volume_views.swap(views);
+    s->volume_gen++;
+    if (s->eng) {
+        hipSetDevice(s->device);
+        return s->eng->volume_config();
+    }
+    return FS_OK;
+}
+int fs_volume_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->volume_sample(); }
+int fs_volume_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->volume_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
+}
+
 // ---- tracer particles -----------------------------------------------------------------------------------------------------
 namespace {
 bool tracer_points_ok(const fs_sim* s, const double* xyz, long n, long* bad)
@@ -4250,6 +4556,7 @@ int fs_comm_init(fs_sim* s, int rank, int nranks, const void* id)
     if (nranks == 1) return FS_OK;
     if (s->body_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"body_force_log\" is on, and bodies are labelled on a single-GPU handle");
     if (s->image_log > 0 && !s->image_views.empty()) return fail(FS_EINVAL, "fs_comm_init: the image log is on, and images are taken on a single-GPU handle");
+    if (s->volume_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"volume_log\" is on, and volumes are rendered on a single-GPU handle");
     if (s->tracers > 0) return fail(FS_EINVAL, "fs_comm_init: option \"tracers\" is on, and tracers move on a single-GPU handle");
     hipSetDevice(s->device);
     if (s->comm.init(rank, nranks, id)) return fail(FS_ECOMM, "%s", s->comm.last_error());

@@ -121,6 +121,7 @@ class Simulation:
             raise FluidsimError(_lib.EHIP, (L.fs_last_error() or b"").decode(errors="replace"))
         self._h = C.c_void_p(self._h)
         self.precision = precision
+        self._volume_size = {}                               # camera slot -> (rows, cols) of its ray set
         self.dtype = np.float64 if precision == "fp64" else np.float32
         self.set_option("precision", precision)
         self.set_option("solver", solver)
@@ -583,6 +584,89 @@ class Simulation:
         images, at = [], 0
         for (_, kind, axis, index) in getattr(self, "_image_views", []):
             rows, cols = self._image_shape(kind, axis, index)
+            images.append(raw[:, at:at + 3 * rows * cols].reshape(n.value, rows, cols, 3).copy())
+            at += 3 * rows * cols
+        return (steps, images, dropped.value) if with_dropped else (steps, images)
+
+    # -- volume rendering (single GPU) -------------------------------------------------------------
+    @staticmethod
+    def _volume_par(vmin=0.0, vmax=1.0, opacity=1.0, step=0.5, t_min=0.01, obstacle=(128, 128, 128), background=(26, 26, 26)):
+        return np.array([vmin, vmax, opacity, step, t_min] + [float(c) for c in obstacle] + [float(c) for c in background],
+                        dtype=np.float64)
+
+    def volume_rays(self, slot, rays):
+        """Stores a ray set in camera slot `slot` (fs_volume_rays): (rows, cols, 6) float64, {ox, oy, oz, dx, dy, dz} per
+        pixel in the viewer's padded coordinates, row 0 the top of the image.  None frees the slot."""
+        if rays is None:
+            check(self._L.fs_volume_rays(self._h, int(slot), None, 0, 0))
+            self._volume_size.pop(int(slot), None)
+            return
+        r = np.ascontiguousarray(rays, dtype=np.float64)
+        if r.ndim != 3 or r.shape[2] != 6:
+            raise ValueError("expected (rows, cols, 6) rays")
+        check(self._L.fs_volume_rays(self._h, int(slot), r.ctypes.data_as(C.c_void_p), r.shape[1], r.shape[0]))
+        self._volume_size[int(slot)] = (r.shape[0], r.shape[1])
+
+    def volume_camera(self, slot, eye, target, up=(0.0, 1.0, 0.0), fov_deg=45.0, ortho_height=None, size=(512, 512)):
+        """Builds the rays of a pinhole camera (vertical field of view `fov_deg`) or, with `ortho_height` (the height of the
+        image plane in cells), of an orthographic one, on the host in fp64, into camera slot `slot` (fs_volume_camera).
+        `size` is (cols, rows).  The tangent is taken here; the library holds no trigonometry."""
+        half = 0.5 * float(ortho_height) if ortho_height is not None else float(np.tan(np.deg2rad(np.float64(fov_deg)) / 2.0))
+        cam = np.array(list(eye) + list(target) + list(up) + [half, 1.0 if ortho_height is not None else 0.0], dtype=np.float64)
+        if cam.size != _lib.VOLUME_CAMERA:
+            raise ValueError("eye, target and up are three numbers each")
+        cols, rows = int(size[0]), int(size[1])
+        check(self._L.fs_volume_camera(self._h, int(slot), cam.ctypes.data_as(C.c_void_p), cols, rows))
+        self._volume_size[int(slot)] = (rows, cols)
+
+    def volume_render(self, source, slot, with_acc=False, **par):
+        """One ray-marched image of `source` (as for sample()) through the rays of camera slot `slot` (fs_volume_render):
+        (rows, cols, 3) uint8; with_acc=True returns (rgb, acc), acc (rows, cols, 4) float64 = the composited colour and the
+        remaining transparency before the background is added.  Keywords: vmin, vmax, opacity, step, t_min, obstacle,
+        background (the two colours as three numbers in 0 .. 255)."""
+        if int(slot) not in self._volume_size:
+            raise ValueError("camera slot %d holds no rays (volume_camera, volume_rays)" % int(slot))
+        rows, cols = self._volume_size[int(slot)]
+        p = self._volume_par(**par)
+        rgb = np.empty((rows, cols, 3), dtype=np.uint8)
+        acc = np.empty((rows, cols, 4), dtype=np.float64) if with_acc else None
+        check(self._L.fs_volume_render(self._h, int(source), int(slot), p.ctypes.data_as(C.c_void_p),
+                                       rgb.ctypes.data_as(C.c_void_p), rgb.size,
+                                       acc.ctypes.data_as(C.c_void_p) if with_acc else None, acc.size if with_acc else 0))
+        return (rgb, acc) if with_acc else rgb
+
+    def set_volume_views(self, views):
+        """Sets the views of the per-step volume log (fs_volume_views): a list of up to VOLUME_VIEWS_MAX tuples (source,
+        slot[, dict of volume_render's keywords]); an empty list turns the log off.  Clears the log."""
+        spec = np.zeros((len(views), 2), dtype=np.intc)
+        par = np.zeros((len(views), _lib.VOLUME_PARAMS), dtype=np.float64)
+        for i, v in enumerate(views):
+            spec[i] = (int(v[0]), int(v[1]))
+            par[i] = self._volume_par(**(v[2] if len(v) > 2 else {}))
+        check(self._L.fs_volume_views(self._h, spec.ctypes.data_as(C.c_void_p), par.ctypes.data_as(C.c_void_p), len(views)))
+        self._volume_views = [int(row[1]) for row in spec]
+
+    volume_view_count = property(lambda s: s._geti("volume_views"))
+    volume_frame_bytes = property(lambda s: s._geti("volume_frame_bytes"))
+
+    def volume_sample(self):
+        """Takes one frame of the volume views from the state as it is now (fs_step does so by itself with volume_log=N)."""
+        check(self._L.fs_volume_sample(self._h))
+
+    def volume_log(self, with_dropped=False):
+        """Drains the per-step volume log (option volume_log=N; fs_volume_log): (steps, images) -- steps (F,) int64, and
+        for each view an (F, rows, cols, 3) uint8 array, oldest frame first.  with_dropped=True returns (steps, images,
+        number of frames the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_volume_log(self._h, None, None, 0, C.byref(n), C.byref(dropped)))
+        per = self.volume_frame_bytes
+        raw = np.zeros((n.value, per), dtype=np.uint8)
+        steps = np.zeros(n.value, dtype=np.int64)
+        check(self._L.fs_volume_log(self._h, raw.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p), n.value,
+                                    C.byref(n), C.byref(dropped)))
+        images, at = [], 0
+        for slot in getattr(self, "_volume_views", []):
+            rows, cols = self._volume_size[slot]
             images.append(raw[:, at:at + 3 * rows * cols].reshape(n.value, rows, cols, 3).copy())
             at += 3 * rows * cols
         return (steps, images, dropped.value) if with_dropped else (steps, images)

@@ -147,6 +147,38 @@ def slice_image(sim, field="density", z=None):
     return sim.image_rgb(source, "slice", 2, int(z), vmin=vmin, vmax=vmax, obstacle_alpha=SLICE_ALPHA)
 
 
+# the 3-D viewer's camera (GUI/gl_widget.py:26-28: distance, azimuth, elevation; :64: a 45 degree field of view), its clear
+# colour (:58, 0.1) and the gray of its obstacle mesh (GUI/utils.py:19-24, 0.5) as bytes
+VOLUME_CAMERA = {"azimuth": 45.0, "elevation": 30.0, "distance": 200.0, "fov_deg": 45.0}
+VOLUME_BACKGROUND = (26, 26, 26)
+VOLUME_OBSTACLE = (128, 128, 128)
+
+
+def orbit_eye(centre, azimuth, elevation, distance):
+    """Where the 3-D viewer's camera stands (GUI/gl_widget.py:71-74: a translation by -distance along z, then rotations by
+    the elevation about x and the azimuth about y, angles in degrees), orbiting `centre` instead of the origin; y is up."""
+    az, el = np.deg2rad(np.float64(azimuth)), np.deg2rad(np.float64(elevation))
+    d = np.float64(distance)
+    off = np.array([-d * np.cos(el) * np.sin(az), d * np.sin(el), d * np.cos(el) * np.cos(az)], dtype=np.float64)
+    return np.asarray(centre, dtype=np.float64).reshape(3) + off
+
+
+def volume_image(sim, field="density", azimuth=45.0, elevation=30.0, distance=200.0, size=(512, 512), slot=0, fov_deg=45.0,
+                 source=None, vmin=None, vmax=None, opacity=0.05, step=0.5, t_min=0.01, obstacle=VOLUME_OBSTACLE,
+                 background=VOLUME_BACKGROUND):
+    """A ray-marched 3-D view of a live `Simulation`, rendered on the device: `field` ("density", "v_x", "v_y", "v_z": the
+    2-D viewer's colour ranges) or any `source` of sample() with vmin / vmax, seen by the reference GUI's camera (its
+    orbit and defaults, GUI/gl_widget.py:26-28 and 64-76) looking at the centre of the box; obstacles are shaded gray
+    surfaces.  `size` is (cols, rows); returns (rows, cols, 3) uint8.  Replaces the rays of camera slot `slot`."""
+    src, lo, hi = SLICE_RANGES[field] if source is None else (int(source), 0.0, 1.0)
+    lo = lo if vmin is None else vmin
+    hi = hi if vmax is None else vmax
+    centre = np.array([sim.width + 1, sim.height + 1, sim.depth + 1], dtype=np.float64) * 0.5
+    sim.volume_camera(slot, orbit_eye(centre, azimuth, elevation, distance), centre, (0.0, 1.0, 0.0), fov_deg=fov_deg, size=size)
+    return sim.volume_render(src, slot, vmin=lo, vmax=hi, opacity=opacity, step=step, t_min=t_min, obstacle=obstacle,
+                             background=background)
+
+
 def write_png(path, rgb):
     """Writes an (rows, cols, 3) uint8 image as an uncompressed 8-bit RGB PNG (fs_image_png; needs no GPU)."""
     import ctypes as C

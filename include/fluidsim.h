@@ -125,6 +125,9 @@ int fs_destroy(fs_sim* s);
  *                 keep the last N snapshots of the pool (fs_tracer_log); "tracer_every" K >= 1 (default 1): a snapshot every
  *                 Kth step.  Setting "tracers" (re)allocates and clears the pool and the log, setting "tracer_log" the log.
  *                 May be changed at any time.  Single GPU only.
+ *   "volume_log"  N >= 0 (at most 65536): keep the last N frames of the volume views (fs_volume_views, fs_volume_log); 0 (default)
+ *                 = off, and the step launches and allocates nothing for it.  "volume_every" K >= 1 (default 1): a frame every
+ *                 Kth step.  Setting "volume_log" (re)allocates and clears the log.  May be changed at any time.  Single GPU only.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -245,7 +248,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * statistics, 0 with the feature off) "probes" (one launch per record of the point probes, 0 with the feature off) "body_forces"
  * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off) "images"
  * (one launch counted per rendered view of the image log, 0 with the feature off) "tracers" (one launch per advance of the tracer
- * particles, in fs_step or by fs_tracer_advance, 0 with the feature off).  Events are recorded on the handle's own stream. */
+ * particles, in fs_step or by fs_tracer_advance, 0 with the feature off) "volume" (one launch per rendered view of the volume log, 0
+ * with the feature off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -728,6 +732,91 @@ int fs_tracer_advance(fs_sim* s);
 int fs_tracer_fetch(fs_sim* s, double* xyz, int32_t* meta, long max, long* n);
 int fs_tracer_sample(fs_sim* s, int source, int mode, double* out, long n);
 int fs_tracer_log(fs_sim* s, double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped);
+
+/* ---- volume rendering (the picture the reference's 3-D viewer, GUI/gl_widget.py, has no way to draw: it shows streamlines and
+ *      the obstacle mesh from a camera orbiting the box, gl_widget.py:26-28 and 64-76; a ray-marched view of a field is beyond it) ----
+ *
+ * A direct volume rendering of any source of fs_sample through an arbitrary set of rays: one HIP kernel, one thread per ray,
+ * trilinear samples composited front to back with early termination, obstacles as shaded opaque surfaces.  It hands over
+ * cols * rows * 3 bytes instead of a volume.  Everything is fp64; every written operation is rounded once, in exactly this
+ * order, without contraction; the march uses + - * / and comparisons only.  A pixel is a pure function of its ray, the
+ * parameters, the colour table and the cells it touches: launch shape cannot change a bit.
+ * COORDINATES are the viewer's, as for fs_sample: indices into the padded array, x first; the box is [0, w+1] x [0, h+1] x
+ * [0, d+1].  N_a below is the interior extent of axis a (w, h, d).
+ *
+ * RAYS.  A camera slot (0 .. FS_VOLUME_CAMERAS_MAX - 1) holds a ray set of cols x rows rays, 1 <= cols, rows <= 2048, on the
+ * device until it is replaced: rays[6 * (r * cols + c) + ..] = {ox, oy, oz, dx, dy, dz}, row 0 first (the top of the image).
+ * Any ray set is legal; length along a ray is measured in units of |d|.
+ * fs_volume_rays stores the given rays; cols = rows = 0 frees the slot (FS_EINVAL while a view of the log uses it).
+ * fs_volume_camera builds them on the host, with + - * / and sqrt only (the library holds no trigonometry):
+ * cam[FS_VOLUME_CAMERA] = {eye[3], target[3], up[3], half_height, ortho}.  half_height > 0 is the half height of the image
+ * plane: at unit distance for a perspective camera (tan(fov / 2)), in cells for an orthographic one (ortho != 0).
+ *     F = target - eye              f_a = F_a / sqrt((F_x F_x + F_y F_y) + F_z F_z)
+ *     R = f x up = (f_y up_z - f_z up_y, f_z up_x - f_x up_z, f_x up_y - f_y up_x)        r_a = R_a / sqrt((R.R)), summed as above
+ *     u = r x f, the same pattern
+ *     pixel (i, j), row i, column j:   sx = (((2 (j + 0.5)) / cols - 1) * half_height) * (cols / rows)
+ *                                      sy = (1 - (2 (i + 0.5)) / rows) * half_height
+ *     perspective:   o = eye,   V_a = (f_a + sx r_a) + sy u_a,   d_a = V_a / sqrt((V.V))
+ *     orthographic:  o_a = (eye_a + sx r_a) + sy u_a,   d = f
+ * A non-finite entry, half_height <= 0, or F.F or R.R zero or not finite is FS_EINVAL.
+ * Replacing the rays of a slot that a view of the log uses clears the log.
+ *
+ * PARAMETERS of a view: par[FS_VOLUME_PARAMS] = {vmin, vmax, opacity, step, t_min, obst_r, obst_g, obst_b, back_r, back_g,
+ * back_b}, all finite: vmin < vmax; opacity >= 0; step > 0; 0 <= t_min < 1; the six colours in [0, 255]; and with diag =
+ * sqrt((((w+1)^2 + (h+1)^2) + (d+1)^2)) and q = diag / step: q <= FS_VOLUME_SAMPLES_MAX.  Anything else is FS_EINVAL.
+ * KMAX = (long)q + 2 is the march's loop limit: more samples than a ray with |d| >= 1 can take through the box (a ray with
+ * |d| < 1 is cut off there), so no ray can spin.
+ *
+ * ONE RAY.  An INVALID ray -- a component of o or d not finite, or d = 0 -- and a ray that MISSES give acc = {0, 0, 0, 1}.
+ * Box: t0 = 0, t1 = +inf; per axis a, in the order x, y, z:  d_a == 0: the ray misses unless 0 <= o_a <= N_a + 1;  otherwise
+ *     ta = (0 - o_a) / d_a,  tb = ((N_a + 1) - o_a) / d_a,  t0 = max(t0, min(ta, tb)),  t1 = min(t1, max(ta, tb)).
+ * The ray misses unless t0 < t1.
+ * March: T = 1, C = (0, 0, 0); for k = 0, 1, .. KMAX - 1:
+ *     tk = t0 + ((double)k + 0.5) * step; stop when !(tk < t1)                  (no running sum)
+ *     p_a = o_a + tk * d_a, clamped to [0, N_a + 1]
+ *     the nearest cell is i_a = (int)(p_a + 0.5); S(cell) = 1 where obs > 0.5 (image_solid), else 0.
+ *     SOLID SAMPLE, if S(i) = 1:
+ *         g_x = S(i_x + 1, i_y, i_z) - S(i_x - 1, i_y, i_z), likewise g_y, g_z; a neighbour outside the padded array counts 0
+ *         n2 = g.g;  shade = 1 if n2 == 0, else s = 0.3 + 0.7 * (|(g_x d_x + g_y d_y) + g_z d_z| * RN[n2]), shade = s < 1 ? s : 1,
+ *         RN[1 .. 3] = 1, 0.7071067811865476, 0.5773502691896257
+ *         C_c = C_c + T * (obst_c * shade);  T = 0;  stop.
+ *     FLUID SAMPLE otherwise: v = FS_SAMPLE_LINEAR of the source at p, exactly as fs_sample defines it (the clamped p is
+ *     always inside).  If v is not NaN:
+ *         cl = v < vmin ? vmin : (v > vmax ? vmax : v);  tn = (cl - vmin) / (vmax - vmin);  ao = (opacity * tn) * step;
+ *         a = ao < 1 ? ao : 1;  if a > 0:  col = table[k], k the colour index of v under COLOURING above (the handle's table,
+ *         fs_image_colormap);  w = T * a;  C_c = C_c + w * col_c;  T = T * (1 - a).
+ *     Then stop if T < t_min.
+ * Outputs: acc = {C_r, C_g, C_b, T}, before the background is added; byte_c = (uint8) min(255, (C_c + T * back_c) + 0.5).
+ *
+ * fs_volume_render: one image of the state as it is now through the rays of `slot`: rgb[rows * cols * 3] bytes and
+ * acc[rows * cols * 4] doubles; either may be NULL; n_bytes / n_acc must be those counts (FS_EINVAL otherwise, and for an empty
+ * slot).  SOURCES are exactly those of fs_sample, with its errors.  It changes no field.
+ *
+ * THE VOLUME LOG, shaped like the image log.  fs_volume_views sets n = 0 .. FS_VOLUME_VIEWS_MAX views: spec[2 k + ..] =
+ * {source, slot}, par[FS_VOLUME_PARAMS * k + ..] the view's parameters, all validated at the call (the slot must hold rays); it
+ * replaces the list and clears the log.  A FRAME is the views' RGB images one after the other in list order.  Options
+ * (fs_set_option, any time): "volume_log" = N, 0 (default: off, a step launches and allocates nothing for it) .. 65536 frames
+ * kept; "volume_every" = K >= 1 (default 1).  Setting "volume_log", the views or the rays of a slot in use reallocates and
+ * clears the ring; each is FS_EINVAL if N * (bytes of one frame) would exceed 1 GiB.  fs_step takes a frame at the sample point
+ * of the image log -- after advect(0, dens, buffer) (simulation.cpp:136), before the frame dump -- when (steps_total - 1) % K
+ * == 0, into a device ring on the step's own stream, by one launch per view, without a host synchronisation.
+ * fs_volume_sample takes one frame of the state as it is now.  fs_volume_log drains the log exactly as fs_image_log does.
+ * fs_get_int "volume_frame_bytes" and "volume_views" report the frame size and the view count; timing family "volume" counts
+ * one launch per rendered view of the log, 0 with the feature off.
+ * Single-GPU handles only: every entry here and a "volume_log" above 0 are FS_EINVAL on a z-slab handle, and so is fs_comm_init
+ * on a handle whose "volume_log" is on.
+ */
+#define FS_VOLUME_CAMERAS_MAX 4
+#define FS_VOLUME_VIEWS_MAX 4
+#define FS_VOLUME_PARAMS 11
+#define FS_VOLUME_CAMERA 11        /* entries of fs_volume_camera's cam[] */
+#define FS_VOLUME_SAMPLES_MAX 16384
+int fs_volume_rays(fs_sim* s, int slot, const double* rays, int cols, int rows);
+int fs_volume_camera(fs_sim* s, int slot, const double* cam, int cols, int rows);
+int fs_volume_render(fs_sim* s, int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc);
+int fs_volume_views(fs_sim* s, const int* spec, const double* par, int n);
+int fs_volume_sample(fs_sim* s);
+int fs_volume_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

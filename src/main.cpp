@@ -51,6 +51,13 @@
 //                  run's frames where they fit 256 MiB and is drained at the end; a longer run is driven step by step
 //                  (fs_run_one, frame dumps through fs_dump_frame, without run()'s console lines) and the ring is drained
 //                  whenever it is full.  Single GPU.
+//   --volume DIR   render a ray-marched 3-D view of the density on the device after every step (option "volume_log",
+//                  fs_volume_camera, fs_volume_views) and write it as uncompressed PNGs DIR/<step>.png (fs_image_png);
+//                  --volume-view AZ,EL,DIST the 3-D viewer's orbit about the box centre in degrees and cells (default 45,30,200:
+//                  GUI/gl_widget.py:26-28; 45 degree field of view, y up), --volume-size CxR the image (default 512x512),
+//                  --volume-range LO,HI the colour range (default 0,0.01), --volume-opacity K the opacity per cell at HI
+//                  (default 0.05), --volume-every K takes every Kth step (steps 1, K+1, ...).  The ring is sized and drained
+//                  as for --images.  Single GPU.
 //   --tracers C    tracer particles: a pool of C slots (option "tracers"); --tracer-emitters FILE sets the emitters, a text file
 //                  with one point `x y z` per line in the viewer's padded index space (0.5 .. N + 0.5 on each axis), `#`
 //                  starts a comment; --tracer-every K releases one particle per emitter every Kth step (steps 1, K+1, ...;
@@ -378,6 +385,24 @@ int write_images(fs_sim* sim, const std::string& dir, const std::vector<int>& sp
     return 0;
 }
 
+// drains the volume log (one view of cols x rows) into DIR/<step>.png
+int write_volumes(fs_sim* sim, const std::string& dir, int cols, int rows)
+{
+    long n = 0, dropped = 0;
+    if (fs_volume_log(sim, nullptr, nullptr, 0, &n, &dropped)) return 1;
+    if (n == 0) return 0;
+    const size_t frame_bytes = 3 * (size_t)cols * (size_t)rows;
+    std::vector<uint8_t> frames((size_t)n * frame_bytes);
+    std::vector<long> steps((size_t)n);
+    if (fs_volume_log(sim, frames.data(), steps.data(), n, &n, &dropped)) return 1;
+    if (dropped) fprintf(stderr, "simulation.out: %ld volume frames were overwritten before they were written\n", dropped);
+    for (long i = 0; i < n; ++i) {
+        const std::string path = dir + "/" + std::to_string(steps[(size_t)i]) + ".png";
+        if (fs_image_png(&frames[(size_t)i * frame_bytes], cols, rows, path.c_str())) return 1;
+    }
+    return 0;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "simulation.out: %s: %s\n", what, fs_last_error());
@@ -401,6 +426,10 @@ int main(int argc, char** argv)
     long tracers = 0, tracer_every = 1;
     bool tracer_every_given = false;
     long image_every = 1;
+    std::string volume_dir;
+    double volume_view[3] = {45.0, 30.0, 200.0}, volume_range[2] = {0.0, 0.01}, volume_opacity = 0.05;
+    int volume_cols = 512, volume_rows = 512;
+    long volume_every = 1;
     int dump_every = 1;
     std::vector<int> view_spec;
     std::vector<double> view_range;
@@ -425,6 +454,12 @@ int main(int argc, char** argv)
             view_range.insert(view_range.end(), rg, rg + 3);
             return true;
         }
+        if (key == "volume") { volume_dir = val; return true; }
+        if (key == "volume-view") return sscanf(val, "%lf,%lf,%lf", &volume_view[0], &volume_view[1], &volume_view[2]) == 3;
+        if (key == "volume-size") return sscanf(val, "%dx%d", &volume_cols, &volume_rows) == 2;
+        if (key == "volume-range") return sscanf(val, "%lf,%lf", &volume_range[0], &volume_range[1]) == 2;
+        if (key == "volume-opacity") { volume_opacity = atof(val); return true; }
+        if (key == "volume-every") { volume_every = atol(val); return volume_every >= 1; }
         if (key == "dump-dir") { options.push_back({ "dump_dir", val }); return true; }
         if (key == "precision") { options.push_back({ "precision", val }); return true; }
         if (key == "solver") { options.push_back({ "solver", val }); return true; }
@@ -451,7 +486,8 @@ int main(int argc, char** argv)
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
-                                        "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out" };
+                                        "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
+                                        "volume-range", "volume-opacity", "volume-every" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -505,7 +541,7 @@ int main(int argc, char** argv)
         if (read_points(tracer_emitters_path.c_str(), pts)) return 2;
         if (fs_tracer_emitters(sim, pts.data(), (long)(pts.size() / 3), tracer_every)) return die("fs_tracer_emitters");
     }
-    bool stepwise = false;                               // --images: the run's frames do not fit the ring
+    bool stepwise = false;                               // --images, --volume: the run's frames do not fit the ring
     long image_ring = 0;
     if (!images_dir.empty()) {
         if (view_spec.empty()) {                         // the 2-D viewer's density and v_x frames (gui.py:271-279)
@@ -523,6 +559,28 @@ int main(int argc, char** argv)
         stepwise = wanted > room;
         if (fs_set_option(sim, "image_every", std::to_string(image_every).c_str())) return die("image_every");
         if (fs_set_option(sim, "image_log", std::to_string(image_ring).c_str())) return die("image_log");
+    }
+    long volume_ring = 0;
+    if (!volume_dir.empty()) {
+        // the 3-D viewer's orbit (GUI/gl_widget.py:71-74) about the box centre, y up; the library takes tan(fov / 2)
+        const double rad = 3.14159265358979323846 / 180.0, az = volume_view[0] * rad, el = volume_view[1] * rad, dist = volume_view[2];
+        const double centre[3] = { 0.5 * (width + 1), 0.5 * (height + 1), 0.5 * (depth + 1) };
+        const double cam[FS_VOLUME_CAMERA] = { centre[0] - dist * std::cos(el) * std::sin(az), centre[1] + dist * std::sin(el),
+                                               centre[2] + dist * std::cos(el) * std::cos(az), centre[0], centre[1], centre[2],
+                                               0.0, 1.0, 0.0, std::tan(22.5 * rad), 0.0 };
+        mkdir(volume_dir.c_str(), 0777);
+        if (fs_volume_camera(sim, 0, cam, volume_cols, volume_rows)) return die("fs_volume_camera");
+        const int vspec[2] = { FS_DENS, 0 };
+        const double vpar[FS_VOLUME_PARAMS] = { volume_range[0], volume_range[1], volume_opacity, 0.5, 0.01, 128.0, 128.0, 128.0,
+                                                26.0, 26.0, 26.0 };
+        if (fs_volume_views(sim, vspec, vpar, 1)) return die("fs_volume_views");
+        const long frame_bytes = 3L * volume_cols * volume_rows;
+        const long wanted = iter > 0 ? (iter - 1) / volume_every + 1 : 0;
+        const long room = std::max(1L, std::min(65536L, (256L << 20) / std::max(1L, frame_bytes)));
+        volume_ring = std::max(1L, std::min(wanted, room));
+        stepwise = stepwise || wanted > room;
+        if (fs_set_option(sim, "volume_every", std::to_string(volume_every).c_str())) return die("volume_every");
+        if (fs_set_option(sim, "volume_log", std::to_string(volume_ring).c_str())) return die("volume_log");
     }
     for (const Stl& s : stls) {
         int rc = fs_load_stl(sim, s.path.c_str(), s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], s.v[5], s.v[6], nullptr);
@@ -542,8 +600,14 @@ int main(int argc, char** argv)
             if (fs_run_one(sim)) return die("fs_run_one");
             if (dump_every > 0 && (i + 1) % dump_every == 0 && fs_dump_frame(sim)) return die("fs_dump_frame");
             long kept = 0;
-            if (fs_image_log(sim, nullptr, nullptr, 0, &kept, nullptr)) return die("fs_image_log");
-            if (kept == image_ring && write_images(sim, images_dir, view_spec)) return die("writing the images");
+            if (!images_dir.empty()) {
+                if (fs_image_log(sim, nullptr, nullptr, 0, &kept, nullptr)) return die("fs_image_log");
+                if (kept == image_ring && write_images(sim, images_dir, view_spec)) return die("writing the images");
+            }
+            if (!volume_dir.empty()) {
+                if (fs_volume_log(sim, nullptr, nullptr, 0, &kept, nullptr)) return die("fs_volume_log");
+                if (kept == volume_ring && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
+            }
         }
         if (dump_every == -1 && fs_dump_frame(sim)) return die("fs_dump_frame");
     }
@@ -554,6 +618,7 @@ int main(int argc, char** argv)
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
+    if (!volume_dir.empty() && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
     if (!tracer_out_path.empty() && write_tracers(sim, tracer_out_path.c_str())) return die("fs_tracer_fetch");
     int mean_samples = 0;
     if (!mean_dir.empty()) {
