@@ -35,6 +35,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1868,15 +1869,15 @@ struct Engine : EngineBase {
         if (npts > ((size_t)1 << 29))                    // 2 x 4 GiB of points and velocities: split the call instead
             return fail(FS_ENOMEM, "%ld seeds x %d steps is more than one call should integrate; lower density or max_length", ncand, max_length);
         double *d_seeds = nullptr, *d_pts = nullptr, *d_vel = nullptr;
-        int *d_count = nullptr, *d_cand = nullptr;
-        int rc = FS_OK;
+        int *d_count = nullptr, *d_cand = nullptr, *d_nan = nullptr;
+        int rc = FS_OK, any_nan = 0;
         std::vector<double> pts, vel;
         std::vector<int> count((size_t)ncand * 2);
         double mx[3][3];
         do {
             if (hipMalloc((void**)&d_seeds, seeds.size() * 8) != hipSuccess || hipMalloc((void**)&d_pts, npts * 8) != hipSuccess ||
                 hipMalloc((void**)&d_vel, npts * 8) != hipSuccess || hipMalloc((void**)&d_count, count.size() * 4) != hipSuccess ||
-                hipMalloc((void**)&d_cand, cand.size() * 4) != hipSuccess) {
+                hipMalloc((void**)&d_cand, cand.size() * 4) != hipSuccess || hipMalloc((void**)&d_nan, 4) != hipSuccess) {
                 rc = fail(FS_ENOMEM, "streamline buffers");
                 break;
             }
@@ -1886,18 +1887,22 @@ struct Engine : EngineBase {
                 hipMemcpyAsync(d_cand, cand.data(), cand.size() * 4, hipMemcpyHostToDevice, S->stream) != hipSuccess) { rc = fail(FS_EHIP, "seed upload"); break; }
             fs::launch_streamlines<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], obs, p, d_seeds, d_cand,
                                       (int)ncand, d_count, d_pts, d_vel);
+            if (hipMemsetAsync(d_nan, 0, 4, S->stream) != hipSuccess) { rc = fail(FS_EHIP, "streamline flag"); break; }
+            fs::launch_any_nan<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], d_nan);
             if (hipMemcpyAsync(count.data(), d_count, count.size() * 4, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
+                hipMemcpyAsync(&any_nan, d_nan, 4, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
                 hipMemcpyAsync(pts.data(), d_pts, npts * 8, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
                 hipMemcpyAsync(vel.data(), d_vel, npts * 8, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
                 hipStreamSynchronize(S->stream) != hipSuccess) { rc = fail(FS_EHIP, "streamline kernel or copy failed"); break; }
             for (int k = 0; k < 3; ++k)
                 if ((rc = stats_of(arr[slot[FS_VX + k]], mx[k]))) break;
         } while (0);
-        hipFree(d_seeds); hipFree(d_pts); hipFree(d_vel); hipFree(d_count); hipFree(d_cand);
+        hipFree(d_seeds); hipFree(d_pts); hipFree(d_vel); hipFree(d_count); hipFree(d_cand); hipFree(d_nan);
         if (rc) return rc;
-        // np.max([vx, vy, vz]) + 1e-6 in the arrays' own precision (float32 for the reference's dumps)
+        // np.max([vx, vy, vz]) + 1e-6 in the arrays' own precision (float32 for the reference's dumps).  np.max is NaN
+        // if any cell is; the maximum of the field statistics skips NaN (the reference's own loop), hence the flag.
         const T vmax = (T)std::fmax(std::fmax(mx[0][2], mx[1][2]), mx[2][2]);
-        const double denom = (double)(T)(vmax + (T)1e-6);
+        const double denom = any_nan ? std::numeric_limits<double>::quiet_NaN() : (double)(T)(vmax + (T)1e-6);
         auto norm3 = [](double a, double b, double c) { return std::sqrt((a * a + b * b) + c * c); };
         std::vector<double> line, lvel;
         for (long sd = 0; sd < ncand; ++sd) {
@@ -1924,9 +1929,15 @@ struct Engine : EngineBase {
                 near = p.lo[0] <= line[3 * i] && line[3 * i] <= p.hi[0] && p.lo[1] <= line[3 * i + 1] && line[3 * i + 1] <= p.hi[1] &&
                        p.lo[2] <= line[3 * i + 2] && line[3 * i + 2] <= p.hi[2];
             if (!near) continue;
-            double max_speed = 0.0;                                      // :198-205
-            for (int i = 0; i < n; ++i) max_speed = std::fmax(max_speed, norm3(lvel[3 * i], lvel[3 * i + 1], lvel[3 * i + 2]));
-            S->sl_norm.push_back(std::fmin(max_speed / denom, 1.0));
+            // :198-205 with Python's max and min: max keeps its first element unless a later one compares greater,
+            // min(r, 1.0) is r unless 1.0 < r -- a NaN ratio stays NaN
+            double max_speed = norm3(lvel[0], lvel[1], lvel[2]);
+            for (int i = 1; i < n; ++i) {
+                const double sp = norm3(lvel[3 * i], lvel[3 * i + 1], lvel[3 * i + 2]);
+                if (sp > max_speed) max_speed = sp;
+            }
+            const double ratio = max_speed / denom;
+            S->sl_norm.push_back(1.0 < ratio ? 1.0 : ratio);
             S->sl_points.insert(S->sl_points.end(), line.begin(), line.end());
             S->sl_offsets.push_back((long)(S->sl_points.size() / 3));
         }

@@ -25,6 +25,11 @@ struct StreamParams {
 template <class T>
 void launch_obs_bbox(hipStream_t st, const GridDesc& g, const T* obs, int* box);
 
+// sets *flag (device memory, zeroed by the caller) to 1 if any cell of the three padded arrays, ghost
+// layer included, is NaN: what makes np.max([vx, vy, vz]) NaN (utils.py:139).
+template <class T>
+void launch_any_nan(hipStream_t st, const GridDesc& g, const T* a, const T* b, const T* c, int* flag);
+
 // One thread per candidate seed.  Seed id = (iz * ny + iy) * nx + ix, the order of the loops at
 // utils.py:141-143; `cand` lists, in that order, the ids that pass the bounding-box cull (done by
 // the caller: it is arithmetic on the seed coordinates only).  seeds: nx + ny + nz doubles (x seeds,

@@ -42,6 +42,29 @@ void launch_obs_bbox(hipStream_t st, const GridDesc& g, const T* obs, int* box)
 template void launch_obs_bbox<float>(hipStream_t, const GridDesc&, const float*, int*);
 template void launch_obs_bbox<double>(hipStream_t, const GridDesc&, const double*, int*);
 
+// np.max([vx, vy, vz]) is NaN as soon as one cell of the three padded arrays is (utils.py:139); the
+// maximum of the field statistics skips NaN, so the colour's denominator asks here.  Every thread that
+// finds one stores the same 1.
+template <class T>
+__global__ void any_nan_kernel(GridDesc g, const T* __restrict__ a, const T* __restrict__ b, const T* __restrict__ c, int* flag)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y * blockDim.y + threadIdx.y;
+    const int z = blockIdx.z;
+    if (x > g.W + 1 || y > g.H + 1) return;
+    const long i = (long)x + (long)y * g.sy + (long)z * g.sz;
+    if (isnan(a[i]) || isnan(b[i]) || isnan(c[i])) *flag = 1;
+}
+
+template <class T>
+void launch_any_nan(hipStream_t st, const GridDesc& g, const T* a, const T* b, const T* c, int* flag)
+{
+    dim3 block(64, 4), grid((g.W + 2 + 63) / 64, (g.H + 2 + 3) / 4, g.D + 2);
+    hipLaunchKernelGGL((any_nan_kernel<T>), grid, block, 0, st, g, a, b, c, flag);
+}
+template void launch_any_nan<float>(hipStream_t, const GridDesc&, const float*, const float*, const float*, int*);
+template void launch_any_nan<double>(hipStream_t, const GridDesc&, const double*, const double*, const double*, int*);
+
 // _interpolate_scalar, utils.py:40-76
 template <class T>
 __device__ double interp(const GridDesc& g, const T* __restrict__ f, const StreamParams& p, double x, double y, double z)

@@ -31,7 +31,8 @@ def generate_streamlines(vx, vy, vz, obs_data, max_length=100, density=30, proxi
     sim.set(_lib.VX, np.ascontiguousarray(np.transpose(vx, back), dtype=np.float32))
     sim.set(_lib.VY, np.ascontiguousarray(np.transpose(vy, back), dtype=np.float32))
     sim.set(_lib.VZ, np.ascontiguousarray(np.transpose(vz, back), dtype=np.float32))
-    sim.set_mask(np.ascontiguousarray(np.transpose(obs_data, back) > 0.5))
+    # the array itself, not a mask of it: the reference interpolates what it was given (utils.py:110)
+    sim.set(_lib.OBS, np.ascontiguousarray(np.transpose(obs_data, back), dtype=np.float32))
     lines, norm = sim.streamlines(density=density, proximity=proximity, max_length=max_length, step_size=step_size,
                                   vel_change_threshold=vel_change_threshold)
     if cmap is None:

@@ -267,14 +267,18 @@ int fs_time_sweeps(fs_sim* s, int b, int field, int prev, float a, float c, int 
  * max_length = INTEGRATION_STEPS (100), step_size = INTEGRATION_STEP_SIZE (0.2),
  * vel_change_threshold = VELOCITY_CHANGE_THRESHOLD (0.1).  Coordinates are the viewer's: indices
  * into the padded arrays, x first.  Lines come in the reference's seed order (z, y, x loops).
+ * FS_OBS is read as the array it is, as the viewer reads its file: the box and the seed test take
+ * cells > 0.5, a line stops where the trilinear interpolation of the array passes 0.5.
  * The result stays in the handle until the next call; *n_lines / *n_points (may be NULL) receive
  * its size.  Single-GPU handles only. */
 int fs_streamlines(fs_sim* s, int density, double proximity, int max_length, double step_size,
                    double vel_change_threshold, long* n_lines, long* n_points);
 /* Copies the last result: offsets[n_lines + 1] (index of each line's first point), points
  * [3 * n_points] (x, y, z per point), norm_speed[n_lines] -- the number the viewer hands to its
- * colour map, min(max speed along the line / (max(vx, vy, vz) + 1e-6), 1)  (utils.py:198-205).
- * Any of the three may be NULL. */
+ * colour map, min(max speed along the line / (max(vx, vy, vz) + 1e-6), 1)  (utils.py:198-205), with numpy's max
+ * over the three padded arrays, ghost layer included, and Python's min: NaN if any cell of them is NaN, 0 if
+ * the largest is +Inf.  Any of the three may be NULL; after a call that was refused the result is empty
+ * (n_lines = 0: the single offset 0). */
 int fs_streamlines_fetch(fs_sim* s, long* offsets, double* points, double* norm_speed);
 
 /* The obstacle mesh the reference's viewer builds on the CPU for the frame it shows --
