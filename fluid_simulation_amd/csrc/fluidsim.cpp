@@ -35,6 +35,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <limits>
 #include <string>
 #include <type_traits>
@@ -3891,8 +3892,17 @@ int fs_load_stl(fs_sim* s, const char* stl_file, float scale, float rot_x, float
     ENGINE_OR_RETURN(s);
     if (!stl_file) return fail(FS_EINVAL, "null path");
     fs::VoxelResult vr;
-    int rc = fs::voxelize_stl(s->stream, stl_file, s->W, s->H, s->D, scale, rot_x, rot_y, rot_z, translate_x,
+    int rc;
+    try {                                                  // the parser and the setup allocate: nothing may leave a C function
+        rc = fs::voxelize_stl(s->stream, stl_file, s->W, s->H, s->D, scale, rot_x, rot_y, rot_z, translate_x,
                               translate_y, translate_z, s->voxel_seed, s->quiet, &vr);
+    } catch (const std::exception& e) {                    // std::bad_alloc, std::length_error: host memory for the mesh
+        fs::voxelize_free(&vr);
+        return fail(FS_ENOMEM, "voxelizer: %s", e.what());
+    } catch (...) {
+        fs::voxelize_free(&vr);
+        return fail(FS_ENOMEM, "voxelizer: unknown exception");
+    }
     if (rc) {                                              // every exit releases the voxelizer's device buffers
         const std::string msg = vr.error;
         fs::voxelize_free(&vr);

@@ -193,7 +193,9 @@ int fs_set_velocity(fs_sim* s, int x, int y, int z, float ax, float ay, float az
  * the GPU.  A missing or empty STL prints the reference's message, leaves the tunnel
  * unchanged and returns FS_EIO (the reference returns void and carries on,
  * object_loader.cpp:282-285; callers that want that behaviour ignore the code).
- * On success *added (may be NULL) receives the "Added N obstacle points" count. */
+ * On success *added (may be NULL) receives the "Added N obstacle points" count.
+ * A truncated binary file keeps its complete records and nothing is sized by its count
+ * field; host memory that runs out while the mesh is read is FS_ENOMEM, never an exception. */
 int fs_load_stl(fs_sim* s, const char* stl_file, float scale, float rot_x, float rot_y, float rot_z,
                 float translate_x, float translate_y, float translate_z, long* added);
 

@@ -462,16 +462,17 @@ static size_t stl_read(const char* path, tri_t** out)
         uint32_t cnt = 0;
         fseek(fp, 80, SEEK_SET);
         if (fread(&cnt, 4, 1, fp) != 1) { fclose(fp); return 0; }
-        t = (tri_t*)malloc((size_t)cnt * sizeof(tri_t) + 1);
+        /* complete records only: stop at the first short one, and size nothing by the count field (a corrupt one
+         * names up to 2^32 - 1 records); csrc/voxelize_math.h read_stl keeps the same rule */
         for (uint32_t i = 0; i < cnt; ++i) {
-            float rec[12]; uint16_t attr;
-            size_t got = fread(rec, 4, 12, fp);
-            got += fread(&attr, 2, 1, fp);
-            /* a short read leaves the reference pushing whatever it has; clean files only */
-            (void)got;
-            t[n].a = (vec3){ rec[3], rec[4], rec[5] };
-            t[n].b = (vec3){ rec[6], rec[7], rec[8] };
-            t[n].c = (vec3){ rec[9], rec[10], rec[11] };
+            unsigned char rec[50];
+            if (fread(rec, 1, 50, fp) != 50) break;
+            float v[9];
+            memcpy(v, rec + 12, sizeof v);
+            if (n == cap) { cap = cap ? cap * 2 : 1024; t = (tri_t*)realloc(t, cap * sizeof(tri_t)); }
+            t[n].a = (vec3){ v[0], v[1], v[2] };
+            t[n].b = (vec3){ v[3], v[4], v[5] };
+            t[n].c = (vec3){ v[6], v[7], v[8] };
             ++n;
         }
     } else {
@@ -549,6 +550,28 @@ static float lcg_unit(uint32_t* st)
     return r * (1.0f - 0.1f) + 0.1f;
 }
 
+/* Test-only view into the voxelizer (tests/test_voxel_cases_cpu.py, tests/test_voxelize_cpu.py): the parser alone, the
+ * sample count and the number of surviving samples of the last cr_load_stl, and, when a buffer is armed, one record of
+ * twelve 32-bit words per surviving sample in stream order: sample index n = (i*ns + j)*ns + k, the jittered point (3
+ * floats), the direction (3 floats), the crossing count, the packed cell x + y*(W+2) + z*(W+2)*(H+2), or -1 when the sample
+ * has even parity or maps outside the grid, and the three cell coordinates before the range test (0 at even parity). */
+static uint32_t* vox_trace = NULL;
+static long vox_trace_cap = 0, vox_trace_n = 0, vox_last_kept = 0;
+static int vox_last_ns = -1;
+void cr_voxel_trace(uint32_t* buf, long cap_records) { vox_trace = buf; vox_trace_cap = cap_records; vox_trace_n = 0; }
+long cr_voxel_trace_count(void) { return vox_trace_n; }
+int cr_voxel_last_ns(void) { return vox_last_ns; }
+long cr_voxel_last_kept(void) { return vox_last_kept; }
+/* triangles of the file, 9 floats each, into out[0 .. 9*cap); returns the file's triangle count */
+long cr_stl_triangles(const char* path, float* out, long cap)
+{
+    tri_t* t = NULL;
+    size_t n = stl_read(path, &t);
+    for (size_t i = 0; i < n && (long)i < cap; ++i) memcpy(out + 9 * i, &t[i], 9 * sizeof(float));
+    free(t);
+    return (long)n;
+}
+
 static float max3f(float a, float b, float c) { float m = a > b ? a : b; return m > c ? m : c; }
 static float min3f(float a, float b, float c) { float m = a < b ? a : b; return m < c ? m : c; }
 
@@ -609,6 +632,8 @@ long cr_load_stl(cr_sim* s, const char* path, float scale, float rot_x, float ro
 
     uint32_t st = lcg_seed(seed);
     long added = 0;
+    vox_last_ns = ns;
+    vox_last_kept = 0;
     for (int i = 0; i < ns; ++i)
         for (int j = 0; j < ns; ++j)
             for (int k = 0; k < ns; ++k) {
@@ -624,13 +649,27 @@ long cr_load_stl(cr_sim* s, const char* path, float scale, float rot_x, float ro
                 vec3 dir; dir.x = lcg_unit(&st); dir.y = lcg_unit(&st); dir.z = lcg_unit(&st);   /* :422 */
                 int crossings = 0;
                 for (size_t t = 0; t < nt; ++t) crossings += ray_hits(p, dir, &rt[t]);
-                if ((crossings & 1) == 0) continue;
-                int sx = (int)((p.x - 0.0f) * gscale + cx + tr_x);   /* :432-434, C truncation */
-                int sy = (int)((p.y - 0.0f) * gscale + cy + tr_y);
-                int sz = (int)((p.z - 0.0f) * gscale + cz + tr_z);
-                if (sx >= 1 && sx <= W && sy >= 1 && sy <= H && sz >= 1 && sz <= D) {
-                    cr_add_obstacle(s, sx, sy, sz);
-                    ++added;
+                int32_t cellid = -1, sxyz[3] = { 0, 0, 0 };
+                if (crossings & 1) {
+                    int sx = (int)((p.x - 0.0f) * gscale + cx + tr_x);   /* :432-434, C truncation */
+                    int sy = (int)((p.y - 0.0f) * gscale + cy + tr_y);
+                    int sz = (int)((p.z - 0.0f) * gscale + cz + tr_z);
+                    sxyz[0] = sx; sxyz[1] = sy; sxyz[2] = sz;
+                    if (sx >= 1 && sx <= W && sy >= 1 && sy <= H && sz >= 1 && sz <= D) {
+                        cr_add_obstacle(s, sx, sy, sz);
+                        ++added;
+                        cellid = sx + sy * (W + 2) + sz * (W + 2) * (H + 2);
+                    }
+                }
+                ++vox_last_kept;
+                if (vox_trace && vox_trace_n < vox_trace_cap) {
+                    uint32_t* w = vox_trace + 12 * vox_trace_n++;
+                    w[0] = (uint32_t)(((long)i * ns + j) * ns + k);
+                    memcpy(w + 1, &p, 12);
+                    memcpy(w + 4, &dir, 12);
+                    w[7] = (uint32_t)crossings;
+                    memcpy(w + 8, &cellid, 4);
+                    memcpy(w + 9, sxyz, 12);
                 }
             }
     free(occ); free(rt); free(raw);

@@ -168,6 +168,33 @@ class Oracle(_Sim):
                           C.c_float(translate[0]), C.c_float(translate[1]), C.c_float(translate[2]),
                           C.c_uint(seed), restype=C.c_long)
 
+    # -- test-only view into the voxelizer (cpu_ref.c, "Test-only view") ----------------
+    TRACE_DTYPE = np.dtype([("n", "<u4"), ("p", "<f4", 3), ("dir", "<f4", 3), ("crossings", "<u4"), ("cell", "<i4"),
+                            ("xyz", "<i4", 3)])
+
+    def load_stl_traced(self, path, max_records, **kw):
+        """load_stl, and one TRACE_DTYPE record per surviving sample, in stream order -> (added, ns, kept, records);
+        records holds the first max_records of the kept samples."""
+        buf = np.zeros(max(1, int(max_records)), dtype=self.TRACE_DTYPE)
+        self.lib.cr_voxel_trace(buf.ctypes.data_as(C.c_void_p), C.c_long(int(max_records)))
+        try:
+            added = self.load_stl(path, **kw)
+            self.lib.cr_voxel_trace_count.restype = C.c_long
+            self.lib.cr_voxel_last_kept.restype = C.c_long
+            n = int(self.lib.cr_voxel_trace_count())
+            ns, kept = int(self.lib.cr_voxel_last_ns()), int(self.lib.cr_voxel_last_kept())
+        finally:
+            self.lib.cr_voxel_trace(None, C.c_long(0))
+        return added, (ns if added >= 0 else None), (kept if added >= 0 else None), buf[:n]
+
+    def stl_triangles(self, path, cap=1 << 16):
+        """The oracle's parser alone -> float32 (n, 9) of the file's triangles (a missing file gives none)."""
+        out = np.zeros((cap, 9), dtype=np.float32)
+        self.lib.cr_stl_triangles.restype = C.c_long
+        n = int(self.lib.cr_stl_triangles(C.c_char_p(os.fsencode(path)), out.ctypes.data_as(C.c_void_p), C.c_long(cap)))
+        assert 0 <= n <= cap
+        return out[:n].copy()
+
     def dump_frame(self, directory, append=True):
         rc = self._call("dump_frame", C.c_char_p(os.fsencode(directory)), C.c_int(1 if append else 0), restype=C.c_int)
         if rc:
