@@ -122,6 +122,7 @@ _SIGNATURES = {
     "fs_flow_stats_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_vortex_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fs_confine_vorticity": (C.c_int, [C.c_void_p, C.c_double]),
     "fs_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_isosurface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_sample_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -23,6 +23,7 @@
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
+#include "confine.h"
 #include "sample.h"
 #include "step_ring.h"
 
@@ -71,8 +72,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -121,6 +122,7 @@ struct EngineBase {
     virtual int flow_stats_dump(const char* dir) = 0;
     virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int vortex_dump(const char* dir) = 0;
+    virtual int confine_vorticity(double eps) = 0;
     virtual int isosurface(int source, double level) = 0;
     virtual int sample_points(const double* xyz, long n) = 0;
     virtual int sample(int source, int mode, double* out, long n) = 0;
@@ -186,6 +188,8 @@ struct fs_sim {
     // "zero_start" / "fuse_project_advect": -1 = auto, 0, 1.  What auto means is decided by measurement.
     int zero_start = -1;         // project(): the divergence pass does not zero p in memory, the first pass of the solve takes zeros
     int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
+    double confinement = 0.0;    // "vorticity_confinement": strength of the confinement pass at the start of a step, 0 = off
+    long n_confine = 0;          // confinement passes done, inside steps and by fs_confine_vorticity (fs_get_int)
     long n_zero_start = 0, n_project_advect = 0;   // projections / steps that took those paths (fs_get_int)
     int overlap = -1;            // z-slabs, how a pass and its halo exchange are scheduled: 0 the pass, then the exchange; 1 boundary
                                  // planes first, their exchange on the communication stream while the interior is computed; 2 boundary
@@ -1600,6 +1604,42 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- vorticity confinement (confine.h; beyond the reference) -----------------------------------------
+    // One pass of strength eps > 0 over the velocities as they are: out of place into three pool arrays, which become the
+    // velocities (the kernel also does what set_bounds(1 / 2 / 3) would do afterwards).  One launch.
+    int confine_pass(const char* who, double eps)
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "%s: vorticity confinement needs a single GPU handle (its stencil reaches two planes into the other slabs)", who);
+        int rc = ensure_flags();
+        if (rc) return rc;
+        const int V[3] = { FS_VX, FS_VY, FS_VZ };
+        for (int f : V)
+            if ((rc = unalias(f))) return rc;
+        int res[3] = { -1, -1, -1 };
+        for (int k = 0; k < 3; ++k)
+            if ((res[k] = acquire()) < 0) {
+                for (int j = 0; j < k; ++j) held[res[j]] = false;
+                return fail(FS_ENOMEM, "array pool exhausted");
+            }
+        const double k = (double)S->dt * eps;
+        {
+            ScopedSpan sp(S, FAM_CONFINE);
+            fs::launch_confine<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], flags, arr[res[0]], arr[res[1]],
+                                  arr[res[2]], k);
+        }
+        for (int a = 0; a < 3; ++a) adopt(V[a], res[a]);
+        ++S->n_confine;
+        return FS_OK;
+    }
+    int confine_vorticity(double eps) override
+    {
+        if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FS_EINVAL, "fs_confine_vorticity: epsilon must be finite and >= 0");
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_confine_vorticity: vorticity confinement needs a single GPU handle");
+        if (eps == 0.0) return FS_OK;
+        if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
+        return confine_pass("fs_confine_vorticity", eps);
+    }
+
     // ---- step (simulation.cpp:96-150) ---------------------------------------------------
     int step() override
     {
@@ -1619,6 +1659,8 @@ struct Engine : EngineBase {
         if ((rc = ensure_volume_ring())) return rc;
         if ((rc = ensure_tracers())) return rc;
         res_ran_now = 0;
+        // "vorticity_confinement": the pass comes before everything the reference's step does
+        if (S->confinement > 0.0 && (rc = confine_pass("fs_step", S->confinement))) return rc;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
@@ -3663,6 +3705,11 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
             hipSetDevice(s->device);
             return s->eng->volume_config();
         }
+    } else if (k == "vorticity_confinement") {
+        char* end = nullptr;
+        const double e = strtod(value, &end);
+        if (end == value || *end || !std::isfinite(e) || !(e >= 0.0)) return fail(FS_EINVAL, "vorticity_confinement: a finite strength >= 0 (0 = off)");
+        s->confinement = e;
     } else if (k == "volume_every") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -3819,6 +3866,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "tracer_count") *out = (int)std::min<long>(s->tracer_seeded, s->tracers);   // slots a fetch returns
     else if (n == "tracer_seeded") *out = (int)std::min<long>(s->tracer_seeded, 2147483647L);   // particles seeded or released since the pool was cleared, saturating
     else if (n == "tracer_emitters") *out = (int)(s->tracer_emit.size() / 3);
+    else if (n == "confinement_passes") *out = (int)std::min<long>(s->n_confine, 2147483647L);   // confinement passes done, in steps and by fs_confine_vorticity
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -3838,6 +3886,7 @@ int fs_get_float(fs_sim* s, const char* name, float* out)
     if (!s || !name || !out) return fail(FS_EINVAL, "null argument");
     std::string n = name;
     if (n == "dt") *out = s->dt; else if (n == "diff") *out = s->diff; else if (n == "visc") *out = s->visc;
+    else if (n == "vorticity_confinement") *out = (float)s->confinement;
     else if (n.size() == 11 && n.compare(0, 7, "overlap") == 0 && n.compare(8, 3, "_ms") == 0 && n[7] >= '0' && n[7] <= '7')
         *out = (float)s->overlap_ms[n[7] - '0'];   // "overlap<k>_ms": slowest rank's ms per pass of candidate k = overlap mode + 4 * (CU mask on), 0 = not timed
     else return fail(FS_EINVAL, "unknown float member '%s'", name);
@@ -4214,6 +4263,11 @@ int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_si
     ENGINE_OR_RETURN(s);
     if (!dst) return fail(FS_EINVAL, "null buffer");
     return s->eng->vortex_field(which, dst, n_elems, elem_size);
+}
+int fs_confine_vorticity(fs_sim* s, double epsilon)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->confine_vorticity(epsilon);
 }
 int fs_vortex_dump(fs_sim* s, const char* dir)
 {

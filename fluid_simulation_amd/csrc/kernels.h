@@ -218,4 +218,13 @@ template <class T>
 void launch_vortex(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int which, const T* vx,
                    const T* vy, const T* vz, const uint8_t* flags, T* out);
 
+// Vorticity confinement (confine.h has the arithmetic, confine.hip the fused z-marching kernel).  One pass over the velocities
+// vx, vy, vz (read only, planes 0..D+1) into ox, oy, oz, three other arrays of the fields' layout: every target cell takes
+// v + k * (N x omega), the other interior cells their stored values, and the three arrays come out as set_bounds(1 / 2 / 3)
+// would leave them -- ghost faces from the new values, solid cells and their fluid neighbours zeroed.  The twelve box edges
+// of the results are not written or take +0.0.  Single GPU (g.zh == 1, both z walls physical).
+template <class T>
+void launch_confine(hipStream_t st, const GridDesc& g, const T* vx, const T* vy, const T* vz, const uint8_t* flags, T* ox, T* oy,
+                    T* oz, double k);
+
 }  // namespace fs

@@ -462,6 +462,12 @@ class Simulation:
         vort_x, vort_y, vort_z, vort_sq and q .bin (fs_vortex_dump; collective on z-slabs)."""
         check(self._L.fs_vortex_dump(self._h, os.fsencode(dir)))
 
+    def confine_vorticity(self, eps):
+        """One vorticity-confinement pass over the velocities now, of strength `eps` >= 0 (fs_confine_vorticity; single-GPU
+        handles): v += dt * eps * (N x omega) in every fluid cell, N the unit vector up the gradient of |omega|, then the
+        boundary handling of set_bounds.  The option vorticity_confinement=eps makes every step begin with such a pass."""
+        check(self._L.fs_confine_vorticity(self._h, float(eps)))
+
     def isosurface(self, source, level):
         """The triangle mesh of {source > level} over the padded box (fs_isosurface; single-GPU handles): `source` is a
         field selector (DENS .. BUFFER) or ISO_VORTEX | VORTEX_*.  Returns (vertices (n, 3) float32 in the viewer's

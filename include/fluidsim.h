@@ -166,12 +166,18 @@ int fs_destroy(fs_sim* s);
  *   "split_density_solve" "1" (default) | "0": run half of the density solve (simulation.cpp:135) between the first
  *                 projection and the velocity advection, so that the reach of each advection gather reaches the host
  *                 without stalling the device (same passes, same order, same bits);
- *   "debug_poison_gather" "1": fill the gathered advection source with NaN patterns before each gather (tests).
+ *   "debug_poison_gather" "1": fill the gathered advection source with NaN patterns before each gather (tests);
+ *   "vorticity_confinement" "<eps>": a decimal number, finite and >= 0; "0" (default) = off.  With eps > 0 every fs_step
+ *                 begins with one confinement pass of that strength (see "vorticity confinement" below), before the inlet
+ *                 forcing of simulation.cpp:103-105; the step then proceeds exactly as without it.  NOT the reference's
+ *                 arithmetic.  May be changed at any time; single-GPU handles only (fs_step on a handle with a
+ *                 communicator is FS_EINVAL while eps > 0).  fs_get_float "vorticity_confinement" answers it.
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
  * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
  * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count", and
- * "tracer_capacity" "tracer_count" "tracer_seeded" "tracer_emitters" (see the tracer particles below).
+ * "tracer_capacity" "tracer_count" "tracer_seeded" "tracer_emitters" (see the tracer particles below), and
+ * "confinement_passes" (confinement passes done so far, inside steps and by fs_confine_vorticity).
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -251,7 +257,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * (one launch counted per logged projection record of "body_force_log" and per fs_body_force call, 0 with the feature off) "images"
  * (one launch counted per rendered view of the image log, 0 with the feature off) "tracers" (one launch per advance of the tracer
  * particles, in fs_step or by fs_tracer_advance, 0 with the feature off) "volume" (one launch per rendered view of the volume log, 0
- * with the feature off).  Events are recorded on the handle's own stream. */
+ * with the feature off) "confinement" (one launch per vorticity-confinement pass, in fs_step or by fs_confine_vorticity, 0
+ * with the option off).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -546,6 +553,40 @@ int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_si
 int fs_vortex_dump(fs_sim* s, const char* dir);
 int fs_isosurface(fs_sim* s, int source, double level, long* n_vertices, long* n_triangles);
 int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles);
+
+/* ---- vorticity confinement (beyond the reference: it has no body force of this kind, no file:line counterpart) ----
+ *
+ * Fedkiw, Stam and Jensen's remedy (2001) for the vortices that semi-Lagrangian advection smears out: a body force
+ * eps * h * (N x omega) that pushes velocity back into the vortex cores, N the unit vector up the gradient of |omega|.
+ * INPUTS: v_x, v_y, v_z as stored -- padded, ghosts and solid cells as they are -- and obs; dt; a strength eps >= 0.
+ * All arithmetic is fp64 on the stored values widened, for fp32 and fp64 handles alike, one rounding per written operation,
+ * in exactly this order, without contraction.  A TARGET cell is an interior cell (1..w, 1..h, 1..d) with obs != 1.
+ * CURL: omega = (WX, WY, WZ) of a target cell exactly as under "vortex identification" above (cell units).
+ * MAGNITUDE: m = sqrt((WX*WX + WY*WY) + WZ*WZ), the correctly rounded square root.
+ * NEIGHBOUR MAGNITUDES: for each of the six face neighbours n of a target cell c, m_n is the neighbour's m where the neighbour
+ * is a target cell, else the cell's own m_c (a zero-gradient extension at walls and solids).  "Is a target cell" is read from
+ * the cell's flag byte: the neighbour is interior and its obs == 0, which for a mask of 0 and 1 is the same thing.  No omega
+ * is ever needed in a ghost or solid cell, so nothing outside the padded box is read.
+ * GRADIENT: ex = 0.5 * (m_xp - m_xm), ey and ez likewise; e2 = (ex*ex + ey*ey) + ez*ez.
+ * DEGENERATE CASE: if !(e2 > 0) -- zero, underflow, NaN -- the cell keeps its three stored values bit for bit (-0.0 too).
+ * FORCE: otherwise len = sqrt(e2), N = (ex / len, ey / len, ez / len) with correctly rounded divisions, and
+ *     f = N x omega = (Ny*WZ - Nz*WY, Nz*WX - Nx*WZ, Nx*WY - Ny*WX),   each component two rounded products and one subtraction.
+ * UPDATE: k = (double)dt * eps, computed on the host and rounded once;  v_a' = (T)((double)v_a + k * f_a) for a = x, y, z, T the
+ * handle's precision.  This is eps * h * (N x omega) * dt with omega in cell units: the cell size h cancels.
+ * Every cell's update reads only the old fields (the pass is out of place).  Non-target cells keep their stored values.
+ * BOUNDARIES: afterwards v_x, v_y, v_z are exactly as fs_set_bounds(1, FS_VX), (2, FS_VY), (3, FS_VZ) would leave them: ghost
+ * faces recomputed from the new values, then solid cells and fluid cells beside a solid zeroed.
+ * A uniform shear has constant m, so e2 == 0 and the pass leaves its interior alone; a zero field likewise.  The effect on a
+ * flow is not monotone in eps: start near 0.25 and look at fs_vortex_field.
+ *
+ * fs_confine_vorticity: one such pass now, with the given strength, whatever the option "vorticity_confinement" says.  One
+ * fused z-marching HIP kernel (timing family "confinement"), three result arrays from the handle's own array pool; nothing is
+ * allocated.  epsilon == 0 is a no-op that launches nothing; a negative or non-finite epsilon is FS_EINVAL.  Works under
+ * every solver mode and both precisions.  Single GPU only: on a handle with a communicator (the FSNULL one included) it is
+ * FS_EINVAL -- the stencil needs two halo planes of three fields.  With the option off a step launches and allocates nothing
+ * for it.  fs_get_int "confinement_passes" counts the passes done, those inside steps included.
+ */
+int fs_confine_vorticity(fs_sim* s, double epsilon);
 
 /* ---- point probes and field sampling (beyond the reference: it evaluates a field off the grid only inside advect) ----
  *

@@ -66,6 +66,8 @@
 //                  as CSV: slot,source,born,moves,status,x,y,z with the positions as %.17g (they read back exactly).
 //                  --tracer-emitters and --tracer-out need --tracers, --tracer-every needs --tracer-emitters: anything
 //                  else is refused.  Single GPU.
+//   --confinement EPS  vorticity confinement: every step begins with one confinement pass of strength EPS (option
+//                  "vorticity_confinement"; a decimal number >= 0, 0 = off; include/fluidsim.h has the definition).  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -481,13 +483,14 @@ int main(int argc, char** argv)
         if (key == "tracer-out") { tracer_out_path = val; return true; }
         if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
+        if (key == "confinement") { options.push_back({ "vorticity_confinement", val }); return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
                                         "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
-                                        "volume-range", "volume-opacity", "volume-every" };
+                                        "volume-range", "volume-opacity", "volume-every", "confinement" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
