@@ -12,7 +12,21 @@
 // reference's output.  What is guaranteed (tests/test_surface.py): the mesh is closed and
 // consistently oriented (every edge is used by exactly two triangles, in opposite directions,
 // normals pointing from solid to fluid), every vertex lies on a grid edge at the 0.5 crossing,
-// and the result is deterministic.
+// and the result is deterministic.  What IS pinned is the library's own order and placement
+// (include/fluidsim.h, fs_isosurface; tests/surface_model.py restates both in numpy and
+// tests/test_gpu_surface_cases.py compares the kernels with it byte for byte):
+//
+// ORDER.  Vertices: the grid points in memory order of the padded array (z outer, y, x inner); at
+// each point its owned crossing edges in axis order x, y, z -- the edge from point c towards +axis
+// is owned by c.  Triangles: the cubes in the same memory order of their lowest corner (x <= W,
+// y <= H, z <= D); within a cube the triangles of surface_case in table order, the three indices
+// in table order.
+//
+// DEGENERATE.  In T, t = (level - v0) / (v1 - v0).  If v0 or v1 is not finite, or
+// !(t >= 0 && t <= 1), then t = 0.5, the edge's midpoint (what the obstacle mesh has everywhere).
+// Every vertex of every mesh is therefore finite and on its edge.  (NaN counts as outside, so a
+// NaN cell does have crossing edges; +-Inf end points give Inf / Inf; level - v0 and v1 - v0 can
+// both overflow in fp32.)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -36,7 +50,9 @@ struct SurfaceResult {
 
 // Iso-surface of a field (`obs` at 0.5 for the obstacle mesh; fs_isosurface passes any field and level): the mesh of
 // value > level over the padded box (0..W+1) x (0..H+1) x (0..D+1), NaN outside, the vertex on a crossing edge at
-// t = (level - v0) / (v1 - v0) computed in T.  Synchronises the stream (the host needs the counts to size the
+// t = (level - v0) / (v1 - v0) computed in T (0.5 where DEGENERATE above says so), vertices and triangles in the
+// ORDER above; an empty mesh (no crossing edge: a level above or below everything, +-Inf, NaN) is nverts = ntris = 0.
+// Synchronises the stream (the host needs the counts to size the
 // output).  Returns 0, or a negative FS_* code with `err` set.  Free the result with surface_free.
 template <class T>
 int extract_surface(hipStream_t st, const GridDesc& g, const T* obs, T level, SurfaceResult* out, const char** err);

@@ -1,8 +1,11 @@
 // surface.hip -- see surface.h.  Marching cubes over a padded field array at a level (the obstacle
 // array at 0.5, or any field at any level): one vertex per grid edge whose end points lie on
 // different sides of the level (placed by linear interpolation; obs is 0/1, so at the edge's
-// midpoint), triangles from a 256-entry case table.  "Inside" (the text below says solid) = value > level;
-// NaN is outside.
+// midpoint; also at the midpoint where an end point is not finite or the interpolation leaves
+// [0, 1] -- DEGENERATE in surface.h), triangles from a 256-entry case table.  "Inside" (the text
+// below says solid) = value > level; NaN is outside.  The order of vertices and triangles is part
+// of the contract (ORDER in surface.h): tests/test_gpu_surface_cases.py compares both arrays byte
+// for byte with a numpy restatement.
 //
 // The table is not copied from anywhere: it is constructed at first use (build_table) from the
 // geometry of the cube -- on every cube face the crossing points are joined by segments, the
@@ -276,7 +279,12 @@ __global__ __launch_bounds__(256) void surf_vertex_kernel(GridDesc g, const T* _
         for (int a = 0; a < 3; ++a) {
             if (!(m & (1u << a))) continue;
             const T v1 = obs[c + (a == 0 ? 1 : a == 1 ? g.sy : g.sz)];
-            const float t = (float)((level - v0) / (v1 - v0));   // linear interpolation to the level, in T: in [0, 1] as v0, v1 straddle it
+            // linear interpolation to the level, in T.  DEGENERATE (surface.h): an end point that is not finite (NaN is
+            // outside, so it has crossing edges; Inf / Inf) or a quotient outside [0, 1] (both differences overflow:
+            // NaN) puts the vertex at the edge's midpoint, so every vertex is finite and on its edge
+            T tt = (level - v0) / (v1 - v0);
+            if (!isfinite(v0) || !isfinite(v1) || !(tt >= (T)0 && tt <= (T)1)) tt = (T)0.5;
+            const float t = (float)tt;
             verts[3 * (long)k + 0] = (float)x + (a == 0 ? t : 0.0f);
             verts[3 * (long)k + 1] = (float)y + (a == 1 ? t : 0.0f);
             verts[3 * (long)k + 2] = (float)z + (a == 2 ? t : 0.0f);

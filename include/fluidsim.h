@@ -296,8 +296,9 @@ int fs_streamlines_fetch(fs_sim* s, long* offsets, double* points, double* norm_
  * one vertex per grid edge on which obs crosses 0.5 (linear interpolation; for a 0/1 mask the edge
  * midpoint), in the viewer's coordinates (indices into the padded array, x first).  Closed, oriented
  * with normals from solid to fluid.  PARITY UNPINNED against scikit-image (vertex / triangle order and
- * the cut of ambiguous cubes may differ; see csrc/surface.h).  The result stays in the handle until
- * the next call.  Single-GPU handles only. */
+ * the cut of ambiguous cubes may differ; see csrc/surface.h); the library's own vertex and triangle
+ * order and its placement of vertices beside non-finite values are fixed: ORDER and DEGENERATE under
+ * fs_isosurface below.  The result stays in the handle until the next call.  Single-GPU handles only. */
 int fs_obstacle_surface(fs_sim* s, long* n_vertices, long* n_triangles);
 /* Copies the last result: vertices[3 * n_vertices] (x, y, z), triangles[3 * n_triangles] (vertex
  * indices).  Either may be NULL. */
@@ -536,10 +537,21 @@ int fs_flow_stats_dump(fs_sim* s, const char* dir);
  * fs_isosurface: the triangle mesh of {value > level} of a source over the padded box, by the marching-cubes extractor of
  * fs_obstacle_surface: the same cube cases, vertex ownership, orientation (normals point from inside to outside) and
  * int-range check.  `source` is a field selector 0 .. FS_NFIELDS - 1, or FS_ISO_VORTEX | FS_VORTEX_* (the field is computed
- * first).  The level is rounded to the handle's precision, L.  NaN counts as outside.  A vertex on the grid edge from point c
- * towards +axis lies at (float)coord + (float)t, t = (L - v0) / (v1 - v0) computed in the handle's precision (finite and in
- * [0, 1], because the end points straddle L).  The mesh is closed when no cell on the padded boundary is inside; for
- * vortex sources with level >= 0 that always holds.  The handle keeps the result in a slot of its own: a later
+ * first).  The level is rounded to the handle's precision, L.  NaN counts as outside, and so does a value equal to L.  A vertex
+ * on the grid edge from point c towards +axis lies at (float)coord + (float)t along that axis, t = (L - v0) / (v1 - v0) computed
+ * in the handle's precision, v0 the value at c.
+ * DEGENERATE: if v0 or v1 is not finite, or !(t >= 0 && t <= 1), then t = 0.5, the edge's midpoint -- what the obstacle mesh
+ * has everywhere.  (A NaN cell is outside, so it has crossing edges; +-Inf end points give Inf / Inf; L - v0 and v1 - v0 can
+ * both overflow in fp32.)  Every vertex of every mesh is therefore finite and on its edge.  Vertices may coincide: v0 == L is
+ * outside and gives t = 0, the grid point itself, for each of its crossing edges; the triangles between them have no area.
+ * ORDER, of fs_isosurface and fs_obstacle_surface alike: the vertices follow the grid points in memory order of the padded array
+ * (z outer, y, x inner), at each point its owned crossing edges in axis order x, y, z -- the edge from point c towards +axis is
+ * owned by c.  The triangles follow the cubes in the same memory order of their lowest corner (x <= W, y <= H, z <= D), within
+ * a cube the triangles of fs_surface_case_table in table order, the three indices in table order.  (PARITY UNPINNED against
+ * scikit-image stays true: this is the library's own order, restated in tests/surface_model.py.)
+ * Without a crossing edge -- a level above or below every value, +-Inf or NaN on a finite field -- the mesh is empty: 0 vertices,
+ * 0 triangles.  The mesh is closed when no cell on the padded boundary is inside (for vortex sources with level >= 0 that
+ * always holds); otherwise it is open along the faces of the padded box and nowhere else.  The handle keeps the result in a slot of its own: a later
  * fs_obstacle_surface does not replace it, nor the reverse.  fs_isosurface(FS_OBS, 0.5) is fs_obstacle_surface's mesh, byte
  * for byte.  Single-GPU handles only (slab handles: FS_EINVAL).
  * fs_isosurface_fetch: copies the last result, as fs_obstacle_surface_fetch does.

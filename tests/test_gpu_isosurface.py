@@ -89,7 +89,14 @@ def test_nan_is_outside_and_an_empty_mesh(F):
     m = inside.astype(bool)
     crossing = int((m[:, :, 1:] != m[:, :, :-1]).sum() + (m[:, 1:, :] != m[:, :-1, :]).sum() + (m[1:, :, :] != m[:-1, :, :]).sum())
     assert not m[5, 7, 9] and len(verts) == crossing
-    verts, faces = sim.isosurface(F.DENS, 5.0)                            # nothing is above 5
+    # DEGENERATE (include/fluidsim.h): every vertex is finite, and the six around the NaN cell are their edges' midpoints
+    assert np.all(np.isfinite(verts))
+    assert m[5, 7, 8] and m[5, 7, 10] and m[5, 6, 9] and m[5, 8, 9] and m[4, 7, 9] and m[6, 7, 9]
+    rows = {tuple(v) for v in verts.tolist()}
+    for mid in ((8.5, 7, 5), (9.5, 7, 5), (9, 6.5, 5), (9, 7.5, 5), (9, 7, 4.5), (9, 7, 5.5)):
+        assert mid in rows, mid
+    assert faces.min() >= 0 and faces.max() < len(verts) and len(np.unique(faces)) == len(verts)
+    verts, faces = sim.isosurface(F.DENS, 5.0)                           # nothing is above 5
     assert verts.shape == (0, 3) and faces.shape == (0, 3)
     sim.close()
 

@@ -49,29 +49,16 @@ def fields(u, v, w, obs):
 def iso_vertices(field, level):
     """The vertices of the iso-surface {field > level} of a padded (z, y, x) array in the handle's precision (the array's
     dtype): one per grid edge whose end points lie on different sides, at (float32)coord + (float32)t along the edge's
-    axis, t = (L - v0) / (v1 - v0) in that precision.  Returns (n, 3) float32 rows (x, y, z), sorted, and for each the
-    unit step from the inside end to the outside end."""
+    axis, t = (L - v0) / (v1 - v0) in that precision, 0.5 where the DEGENERATE rule of include/fluidsim.h says so -- the
+    definition of tests/surface_model.py, which this calls.  Returns (n, 3) float32 rows (x, y, z), sorted, and for each
+    the unit step from the inside end to the outside end."""
+    import surface_model as S
     a = np.asarray(field)
-    T = a.dtype.type
-    L = T(level)
-    inside = a > L                                           # NaN is outside
-    rows, outward = [], []
-    for axis, xyz in ((2, 0), (1, 1), (0, 2)):                # array axis, coordinate index
-        lo = [slice(None)] * 3
-        hi = [slice(None)] * 3
-        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
-        cross = inside[tuple(lo)] != inside[tuple(hi)]
-        zz, yy, xx = np.nonzero(cross)
-        v0, v1 = a[tuple(lo)][cross], a[tuple(hi)][cross]
-        with np.errstate(all="ignore"):
-            t = ((L - v0) / (v1 - v0)).astype(np.float32)
-        p = np.stack([xx, yy, zz], axis=1).astype(np.float32)
-        p[:, xyz] = p[:, xyz] + t
-        rows.append(p)
-        o = np.zeros((len(xx), 3))
-        o[:, xyz] = np.where(inside[tuple(lo)][cross], 1.0, -1.0)
-        outward.append(o)
-    rows, outward = np.concatenate(rows), np.concatenate(outward)
+    rows, _ = S.mesh(a, level)
+    own = S.vertex_owners(a, level)
+    assert len(own) == len(rows)
+    outward = np.zeros((len(rows), 3))
+    outward[np.arange(len(rows)), own[:, 3]] = np.where(S.inside_of(a, level)[own[:, 2], own[:, 1], own[:, 0]], 1.0, -1.0)
     order = np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0]))
     return rows[order], outward[order]
 
