@@ -8,14 +8,18 @@ from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_
                    STAT_UU, STAT_UV, STAT_UW, STAT_VV, STAT_VW, STAT_WW, ISO_VORTEX, VORTEX_NAMES, VORTEX_Q, VORTEX_W2, VORTEX_WX,
                    VORTEX_WY, VORTEX_WZ, PROBE_MAX, PROBE_NAMES, PROBE_VALUES, SAMPLE_FLUID, SAMPLE_LINEAR, SAMPLE_NEAREST,
                    SAMPLE_STAT, IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN, IMAGE_VIEWS_MAX, TRACER_ALIVE, TRACER_EMITTERS_MAX,
-                   TRACER_FRAME_BYTES, TRACER_FREE, TRACER_HIT, TRACER_OUT, TRACER_STATUS_NAMES, BODY_COLS, BODY_INFO_COLS, BODY_LOG_COLS, BODY_MAX, FluidsimError)
+                   TRACER_FRAME_BYTES, TRACER_FREE, TRACER_HIT, TRACER_OUT, TRACER_STATUS_NAMES, BODY_COLS, BODY_INFO_COLS, BODY_LOG_COLS, BODY_MAX,
+                   MONITOR_COLS, MONITOR_LOG_COLS, MONITOR_PROFILE_COLS, MONITOR_STATIONS_MAX, FluidsimError)
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
-                         solve_reduction, BODY_INFO_DTYPE, BODY_LOG_DTYPE, pressure_moment, shift_moment)
+                         solve_reduction, BODY_INFO_DTYPE, BODY_LOG_DTYPE, pressure_moment, shift_moment,
+                         MONITOR_LOG_NAMES, MONITOR_NAMES, MONITOR_PROFILE_NAMES, monitor_cfl)
 
 __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_force", "FORCE_LOG_DTYPE", "FluidsimError",
            "RESIDUAL_LOG_DTYPE", "solve_reduction",
            "BODY_INFO_DTYPE", "BODY_LOG_DTYPE", "pressure_moment", "shift_moment", "BODY_MAX", "BODY_COLS", "BODY_INFO_COLS",
            "BODY_LOG_COLS",
+           "MONITOR_COLS", "MONITOR_PROFILE_COLS", "MONITOR_STATIONS_MAX", "MONITOR_LOG_COLS", "MONITOR_NAMES",
+           "MONITOR_PROFILE_NAMES", "MONITOR_LOG_NAMES", "monitor_cfl",
            "FIELD_NAMES", "STAT_NAMES",
            "STAT_MEAN_DENS", "STAT_MEAN_VX", "STAT_MEAN_VY", "STAT_MEAN_VZ", "STAT_MEAN_P", "STAT_UU", "STAT_VV", "STAT_WW",
            "STAT_UV", "STAT_UW", "STAT_VW", "STAT_PP", "STAT_TKE", "STAT_RAW",

@@ -24,6 +24,10 @@ BODY_LOG_COLS = 16      # FS_BODY_LOG_COLS: step, body, S1xyz, M1xyz, S2xyz, M2x
 RESIDUAL_COLS = 4       # FS_RESIDUAL_COLS: sum r^2, sum x0^2, max |r|, free cells
 RESIDUAL_LOG_SOLVES = 6     # FS_RESIDUAL_LOG_SOLVES: diffuse v_x, v_y, v_z, projection 1, projection 2, diffuse density
 RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, r_sq, r_max, rhs_sq, cells
+MONITOR_COLS = 16           # FS_MONITOR_COLS: the flow monitor's PLANE / WHOLE record
+MONITOR_PROFILE_COLS = 5    # FS_MONITOR_PROFILE_COLS: cells, sum u, sum u*u, sum p, sum q*u of one x
+MONITOR_STATIONS_MAX = 8    # FS_MONITOR_STATIONS_MAX
+MONITOR_LOG_COLS = 57       # FS_MONITOR_LOG_COLS: step, the whole record, then the profile row of each of 8 stations
 # FS_STAT_*: selectors of fs_flow_stats_field -- the five means, the seven (co)variances, the turbulence kinetic energy;
 # STAT_RAW or-ed in returns the raw sum instead
 (STAT_MEAN_DENS, STAT_MEAN_VX, STAT_MEAN_VY, STAT_MEAN_VZ, STAT_MEAN_P,
@@ -123,6 +127,9 @@ _SIGNATURES = {
     "fs_vortex_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_confine_vorticity": (C.c_int, [C.c_void_p, C.c_double]),
+    "fs_flow_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fs_monitor_sample": (C.c_int, [C.c_void_p]),
+    "fs_monitor_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_isosurface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_sample_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -20,6 +20,7 @@
 #include "image.h"
 #include "volume.h"
 #include "tracers.h"
+#include "monitor.h"
 #include "residual.h"
 #include "flow_stats.h"
 #include "vortex.h"
@@ -72,8 +73,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -123,6 +124,9 @@ struct EngineBase {
     virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int vortex_dump(const char* dir) = 0;
     virtual int confine_vorticity(double eps) = 0;
+    virtual int flow_monitor(double* out16, double* per_plane, double* x_profile) = 0;
+    virtual int monitor_sample() = 0;
+    virtual int monitor_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
     virtual int isosurface(int source, double level) = 0;
     virtual int sample_points(const double* xyz, long n) = 0;
     virtual int sample(int source, int mode, double* out, long n) = 0;
@@ -252,6 +256,11 @@ struct fs_sim {
     int volume_log = 0;          // "volume_log": frames the volume log keeps, 0 = off
     long volume_every = 1;       // "volume_every": fs_step takes a frame when (steps_total - 1) % volume_every == 0
     long volume_gen = 0;         // bumped by fs_volume_views, fs_set_option("volume_log") and a new ray set of a slot a view uses
+    int monitor_log = 0;         // "monitor_log": records the flow-monitor log keeps, 0 = off
+    long monitor_every = 1;      // "monitor_every": fs_step takes a record when (steps_total - 1) % monitor_every == 0
+    long monitor_gen = 0;        // bumped by fs_set_option("monitor_log") and ("monitor_stations"): the ring is reallocated and cleared
+    int monitor_nstations = 0;   // "monitor_stations": how many are set
+    fs::MonitorStations monitor_stations = {{0, 0, 0, 0, 0, 0, 0, 0}};   // their x indices, 0 = unused
     int tracers = 0;             // "tracers": slots of the tracer pool, 0 = off
     long tracer_gen = 0;         // bumped by fs_set_option("tracers"): pool and log are set up anew and cleared
     int tracer_log = 0;          // "tracer_log": snapshot frames the tracer log keeps, 0 = off
@@ -522,6 +531,10 @@ struct Engine : EngineBase {
     double* body_planes = nullptr;      // plane records of the last launch: g.D x (BODY_MAX + 1) x BODY_REC (stream-ordered reuse)
     double* body_total = nullptr;       // fs_body_force: the whole-grid records
     LogRing body_ring;                  // for S->body_log_gen, -1 after a relabelling: the ring is set up anew, the log is cleared
+    // flow monitor (monitor.h): the workspace of its three launches (allocated at the first record, stream-ordered reuse) and
+    // the per-step log, a device ring of records of MON_RESULT doubles (the whole record, then the stations' profile rows)
+    double* mon_ws = nullptr;
+    LogRing mon_ring;                   // for S->monitor_gen
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -656,9 +669,10 @@ struct Engine : EngineBase {
             if (q) hipFree(q);
         if (vol_rgb) hipFree(vol_rgb);
         if (vol_acc) hipFree(vol_acc);
+        if (mon_ws) hipFree(mon_ws);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
             if (q) hipFree(q);
-        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring }) r->release();
+        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring, &mon_ring }) r->release();
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -1658,6 +1672,7 @@ struct Engine : EngineBase {
         if ((rc = ensure_image_ring())) return rc;
         if ((rc = ensure_volume_ring())) return rc;
         if ((rc = ensure_tracers())) return rc;
+        if ((rc = ensure_monitor_ring())) return rc;
         res_ran_now = 0;
         // "vorticity_confinement": the pass comes before everything the reference's step does
         if (S->confinement > 0.0 && (rc = confine_pass("fs_step", S->confinement))) return rc;
@@ -1743,6 +1758,8 @@ struct Engine : EngineBase {
         if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
             (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
             return rc;
+        // "monitor_log": the same state is a record of the flow monitor (three launches, no host synchronisation, the step's own stream)
+        if (mon_ring.on() && (S->steps_total - 1) % S->monitor_every == 0) monitor_record();
         // "probe_log": the same state is a record of the probes (one launch, no host synchronisation, the step's own stream)
         if (probe_ring.on()) probe_record();
         // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
@@ -3376,6 +3393,92 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
+    // ---- flow monitor (monitor.h; beyond the reference) --------------------------------------------------------
+    int ensure_monitor_ws()
+    {
+        if (!mon_ws) HIP_TRY(hipMalloc((void**)&mon_ws, fs::monitor_workspace_doubles(g) * sizeof(double)));
+        return FS_OK;
+    }
+
+    // (re)allocate and clear the ring after fs_set_option("monitor_log") / ("monitor_stations")
+    int ensure_monitor_ring()
+    {
+        if (mon_ring.gen == S->monitor_gen) return FS_OK;
+        HIP_TRY(mon_ring.setup(S->stream, S->monitor_gen));   // off, whatever fails below
+        if (S->monitor_log <= 0) return FS_OK;
+        if (S->comm.active()) return fail(FS_EINVAL, "monitor_log: the flow monitor needs a single-GPU handle");
+        int rc = ensure_monitor_ws();
+        if (rc) return rc;
+        HIP_TRY(mon_ring.setup(S->stream, S->monitor_gen, S->monitor_log, (size_t)fs::MON_RESULT * sizeof(double)));
+        return FS_OK;
+    }
+
+    // one record of the state as it is now into `result` (a ring slot or the workspace's result slot)
+    void monitor_launch(double* result)
+    {
+        ScopedSpan sp(S, FAM_MONITOR);
+        fs::launch_monitor<T>(S->stream, g, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]],
+                              arr[slot[FS_PRESSURE]], flags, S->monitor_stations, mon_ws, result);
+    }
+    void monitor_record()
+    {
+        monitor_launch((double*)mon_ring.slot(mon_ring.at.next()));
+        mon_ring.at.commit(S->steps_total);
+    }
+
+    int monitor_sample() override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_monitor_sample: the flow monitor needs a single-GPU handle");
+        int rc = ensure_flags();
+        if (rc) return rc;
+        if ((rc = ensure_monitor_ring())) return rc;
+        if (!mon_ring.on()) return fail(FS_EINVAL, "fs_monitor_sample: option \"monitor_log\" is 0");
+        monitor_record();
+        return FS_OK;
+    }
+
+    int flow_monitor(double* out16, double* per_plane, double* x_profile) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_flow_monitor: the flow monitor needs a single-GPU handle");
+        int rc = ensure_flags();
+        if (rc) return rc;
+        if ((rc = ensure_monitor_ws())) return rc;
+        const fs::MonitorPlan pl = fs::monitor_plan(g.W, g.H, g.D);
+        monitor_launch(mon_ws + pl.result_off);
+        // planes, profile and result lie one behind the other (monitor_plan.h)
+        std::vector<double> host((size_t)(pl.doubles - pl.planes_off));
+        HIP_TRY(hipMemcpyAsync(host.data(), mon_ws + pl.planes_off, host.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        if (out16) memcpy(out16, host.data() + (pl.result_off - pl.planes_off), fs::MON_PLANE * sizeof(double));
+        if (per_plane) memcpy(per_plane, host.data(), (size_t)g.D * fs::MON_PLANE * sizeof(double));
+        if (x_profile) memcpy(x_profile, host.data() + (pl.profile_off - pl.planes_off), (size_t)g.W * fs::MON_PROFILE * sizeof(double));
+        return FS_OK;
+    }
+
+    int monitor_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_monitor_log: the flow monitor needs a single-GPU handle");
+        int rc = ensure_monitor_ring();
+        if (rc) return rc;
+        const long n = mon_ring.at.retained();
+        if (n_rows) *n_rows = n;
+        if (n_dropped) *n_dropped = mon_ring.at.dropped();
+        if (!rows) return FS_OK;                         // sizes only: nothing drained
+        if (max_rows < n) return fail(FS_EINVAL, "fs_monitor_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        std::vector<double> mine((size_t)n * fs::MON_RESULT);
+        if (n > 0) {
+            HIP_TRY(mon_ring.copy_out(S->stream, mine.data()));
+            HIP_TRY(hipStreamSynchronize(S->stream));
+        }
+        for (long i = 0; i < n; ++i) {
+            double* o = rows + (size_t)i * FS_MONITOR_LOG_COLS;
+            o[0] = (double)mon_ring.at.step_of(i);
+            memcpy(o + 1, &mine[(size_t)i * fs::MON_RESULT], fs::MON_RESULT * sizeof(double));
+        }
+        mon_ring.at.drain();
+        return FS_OK;
+    }
+
     // ---- residual of the linear solves (residual.h; beyond the reference) ------------------------------------
     static constexpr int RES_SOLVES = FS_RESIDUAL_LOG_SOLVES;
     size_t res_plane_doubles() const { return (size_t)fs::RESIDUAL_REC * (size_t)g.D; }
@@ -3705,6 +3808,34 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
             hipSetDevice(s->device);
             return s->eng->volume_config();
         }
+    } else if (k == "monitor_log") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (s->comm.active()) return fail(FS_EINVAL, "monitor_log: the flow monitor needs a single-GPU handle");
+        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "monitor_log: records kept, 0 (off) .. 1048576");
+        s->monitor_log = (int)n;
+        s->monitor_gen++;
+    } else if (k == "monitor_every") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (s->comm.active()) return fail(FS_EINVAL, "monitor_every: the flow monitor needs a single-GPU handle");
+        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "monitor_every: K >= 1");
+        s->monitor_every = n;
+    } else if (k == "monitor_stations") {
+        if (s->comm.active()) return fail(FS_EINVAL, "monitor_stations: the flow monitor needs a single-GPU handle");
+        fs::MonitorStations st = {{0, 0, 0, 0, 0, 0, 0, 0}};
+        int n = 0;
+        for (const char* q = value; *q;) {
+            char* end = nullptr;
+            const long x = strtol(q, &end, 10);
+            if (end == q || (*end != ',' && *end != '\0') || (*end == ',' && end[1] == '\0') || x < 1 || x > s->W || n == fs::MON_STATIONS)
+                return fail(FS_EINVAL, "monitor_stations: \"x1,x2,...\", up to %d indices in 1 .. %d (\"\" = none)", fs::MON_STATIONS, s->W);
+            st.x[n++] = (int)x;
+            q = *end ? end + 1 : end;
+        }
+        s->monitor_stations = st;
+        s->monitor_nstations = n;
+        s->monitor_gen++;
     } else if (k == "vorticity_confinement") {
         char* end = nullptr;
         const double e = strtod(value, &end);
@@ -3867,6 +3998,9 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "tracer_seeded") *out = (int)std::min<long>(s->tracer_seeded, 2147483647L);   // particles seeded or released since the pool was cleared, saturating
     else if (n == "tracer_emitters") *out = (int)(s->tracer_emit.size() / 3);
     else if (n == "confinement_passes") *out = (int)std::min<long>(s->n_confine, 2147483647L);   // confinement passes done, in steps and by fs_confine_vorticity
+    else if (n == "monitor_log") *out = s->monitor_log;
+    else if (n == "monitor_every") *out = (int)s->monitor_every;
+    else if (n == "monitor_stations") *out = s->monitor_nstations;        // how many stations are set
     else if (n == "flow_stats_samples") *out = (int)s->flow_stats_n;      // samples in the flow statistics since the last reset
     else return fail(FS_EINVAL, "unknown int member '%s'", name);
     return FS_OK;
@@ -4264,6 +4398,18 @@ int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_si
     if (!dst) return fail(FS_EINVAL, "null buffer");
     return s->eng->vortex_field(which, dst, n_elems, elem_size);
 }
+int fs_flow_monitor(fs_sim* s, double out[16], double* per_plane, double* x_profile)
+{
+    ENGINE_OR_RETURN(s);
+    if (!out) return fail(FS_EINVAL, "null argument");
+    return s->eng->flow_monitor(out, per_plane, x_profile);
+}
+int fs_monitor_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->monitor_sample(); }
+int fs_monitor_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->monitor_log_fetch(rows, max_rows, n_rows, n_dropped);
+}
 int fs_confine_vorticity(fs_sim* s, double epsilon)
 {
     ENGINE_OR_RETURN(s);
@@ -4632,6 +4778,7 @@ int fs_comm_init(fs_sim* s, int rank, int nranks, const void* id)
     if (s->body_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"body_force_log\" is on, and bodies are labelled on a single-GPU handle");
     if (s->image_log > 0 && !s->image_views.empty()) return fail(FS_EINVAL, "fs_comm_init: the image log is on, and images are taken on a single-GPU handle");
     if (s->volume_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"volume_log\" is on, and volumes are rendered on a single-GPU handle");
+    if (s->monitor_log > 0) return fail(FS_EINVAL, "fs_comm_init: option \"monitor_log\" is on, and the flow monitor needs a single-GPU handle");
     if (s->tracers > 0) return fail(FS_EINVAL, "fs_comm_init: option \"tracers\" is on, and tracers move on a single-GPU handle");
     hipSetDevice(s->device);
     if (s->comm.init(rank, nranks, id)) return fail(FS_ECOMM, "%s", s->comm.last_error());

@@ -66,6 +66,22 @@ def _residual_dict(out, pp):
     return r
 
 
+# The 16 numbers of a flow-monitor record (include/fluidsim.h, "flow monitor"), the 5 of an x-profile row, and the 57
+# columns of Simulation.monitor_log(): step, the whole record, then the profile row of each of the 8 stations.
+MONITOR_NAMES = ("cells", "nonfinite", "sum_q", "sum_u", "sum_v", "sum_w", "sum_e", "sum_p", "max_abs_u", "max_abs_v",
+                 "max_abs_w", "max_e", "min_q", "max_q", "min_p", "max_p")
+MONITOR_PROFILE_NAMES = ("cells", "sum_u", "sum_uu", "sum_p", "sum_qu")
+MONITOR_LOG_NAMES = (("step",) + MONITOR_NAMES +
+                     tuple("s%d_%s" % (k, n) for k in range(_lib.MONITOR_STATIONS_MAX) for n in MONITOR_PROFILE_NAMES))
+
+
+def monitor_cfl(dt, width, height, depth, max_abs_u, max_abs_v, max_abs_w):
+    """The Courant numbers of a flow-monitor record: ((double)dt * N) * max |.| per axis, the length of the advection
+    back-trace in cells; `dt` as the handle stores it (fp32)."""
+    dt = float(np.float32(dt))
+    return ((dt * int(width)) * float(max_abs_u), (dt * int(height)) * float(max_abs_v), (dt * int(depth)) * float(max_abs_w))
+
+
 def pressure_force(s, frontal, dt, speed, width, height, depth):
     """Force and force coefficients of raw pressure sums (include/fluidsim.h, "pressure force on the obstacles"):
     F = S * h^2 / dt with h = 1 / cbrt(width * height * depth), and C = 2 * S / (dt * speed^2 * N_front), N_front =
@@ -151,6 +167,8 @@ class Simulation:
             value = "1" if value else "0"
         elif key == "moment_origin" and not isinstance(value, str):
             value = ",".join(repr(float(v)) for v in value)
+        elif key == "monitor_stations" and not isinstance(value, str):
+            value = ",".join(str(int(v)) for v in value)
         check(self._L.fs_set_option(self._h, key.encode(), str(value).encode()))
 
     # -- public data members of the reference class (simulation.h:44-54) ---------------
@@ -418,6 +436,45 @@ class Simulation:
         red = solve_reduction(raw)
         for k in range(_lib.RESIDUAL_LOG_SOLVES):
             rows["reduction_%d" % k] = red[:, k]
+        return (rows, dropped.value) if with_dropped else rows
+
+    def flow_monitor(self, per_plane=False, x_profile=False):
+        """The flow monitor's record of the state as it is now (fs_flow_monitor; single-GPU handles; changes nothing): a
+        dict of MONITOR_NAMES -> float over the target cells (interior, not solid), "values" the same 16 numbers as an
+        array, "cfl" = (cfl_x, cfl_y, cfl_z) = ((double)dt * N) * max |.|, "kinetic_energy" = 0.5 * sum_e * h^3 with
+        h = 1 / cbrt(w*h*d); per_plane=True adds "per_plane" (depth, 16), x_profile=True "x_profile" (width, 5:
+        MONITOR_PROFILE_NAMES).  Every sum has one written order (include/fluidsim.h)."""
+        out = np.zeros(_lib.MONITOR_COLS, dtype=np.float64)
+        pp = np.zeros((self.depth, _lib.MONITOR_COLS), dtype=np.float64) if per_plane else None
+        xp = np.zeros((self.width, _lib.MONITOR_PROFILE_COLS), dtype=np.float64) if x_profile else None
+        check(self._L.fs_flow_monitor(self._h, out.ctypes.data, None if pp is None else pp.ctypes.data,
+                                      None if xp is None else xp.ctypes.data))
+        r = {name: float(out[k]) for k, name in enumerate(MONITOR_NAMES)}
+        r["values"] = out
+        w, h, d = self.width, self.height, self.depth
+        r["cfl"] = monitor_cfl(self.dt, w, h, d, out[8], out[9], out[10])
+        cell = 1.0 / float(np.cbrt(float(w * h * d)))
+        r["kinetic_energy"] = 0.5 * float(out[6]) * (cell * cell * cell)
+        if pp is not None:
+            r["per_plane"] = pp
+        if xp is not None:
+            r["x_profile"] = xp
+        return r
+
+    def monitor_sample(self):
+        """Appends a flow-monitor record of the state as it is now to the log (fs_step does so by itself with
+        monitor_log=N, every monitor_every-th step)."""
+        check(self._L.fs_monitor_sample(self._h))
+
+    def monitor_log(self, with_dropped=False):
+        """Drains the flow-monitor log (options monitor_log=N, monitor_every=K, monitor_stations="x1,x2,.."; fs_monitor_log):
+        one row per retained record, oldest first, (n, 57) float64 with the columns MONITOR_LOG_NAMES -- step, the whole
+        record, the x-profile row of each station (NaN for an unused one).  with_dropped=True returns (rows, number of
+        records the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_monitor_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        rows = np.zeros((n.value, _lib.MONITOR_LOG_COLS), dtype=np.float64)
+        check(self._L.fs_monitor_log(self._h, rows.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
         return (rows, dropped.value) if with_dropped else rows
 
     def flow_stats(self, which, raw=False, dtype=None):

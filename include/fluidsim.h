@@ -128,6 +128,11 @@ int fs_destroy(fs_sim* s);
  *   "volume_log"  N >= 0 (at most 65536): keep the last N frames of the volume views (fs_volume_views, fs_volume_log); 0 (default)
  *                 = off, and the step launches and allocates nothing for it.  "volume_every" K >= 1 (default 1): a frame every
  *                 Kth step.  Setting "volume_log" (re)allocates and clears the log.  May be changed at any time.  Single GPU only.
+ *   "monitor_log" N >= 0 (at most 1048576): keep the last N records of the flow monitor (fs_flow_monitor, fs_monitor_log); 0
+ *                 (default) = off, and the step launches and allocates nothing for it.  "monitor_every" K >= 1 (default 1): a
+ *                 record every Kth step.  "monitor_stations" "x1,x2,..." (up to 8 indices in 1..w, "" = none): the x whose
+ *                 profile rows a record carries.  Setting "monitor_log" or "monitor_stations" (re)allocates and clears the log.
+ *                 May be changed at any time.  Single GPU only.
  * Per-handle tuning keys that never change results (kernel selection and launch shapes):
  *   "sweep_fuse"  "1" one solver sweep per pass over memory, "2" two, "3" (default) two or three: the
  *                 three-sweep kernel (fp32, rows up to 512 cells) is timed against the two-sweep one
@@ -177,7 +182,8 @@ int fs_destroy(fs_sim* s);
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
  * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count", and
  * "tracer_capacity" "tracer_count" "tracer_seeded" "tracer_emitters" (see the tracer particles below), and
- * "confinement_passes" (confinement passes done so far, inside steps and by fs_confine_vorticity).
+ * "confinement_passes" (confinement passes done so far, inside steps and by fs_confine_vorticity), and "monitor_log"
+ * "monitor_every" "monitor_stations" (the number of stations set).
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -258,7 +264,8 @@ int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
  * (one launch counted per rendered view of the image log, 0 with the feature off) "tracers" (one launch per advance of the tracer
  * particles, in fs_step or by fs_tracer_advance, 0 with the feature off) "volume" (one launch per rendered view of the volume log, 0
  * with the feature off) "confinement" (one launch per vorticity-confinement pass, in fs_step or by fs_confine_vorticity, 0
- * with the option off).  Events are recorded on the handle's own stream. */
+ * with the option off) "monitor" (one launch counted per record of the flow monitor, by the log or on demand, 0 with the
+ * feature unused).  Events are recorded on the handle's own stream. */
 int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launches);
 int fs_reset_timing(fs_sim* s);
 
@@ -876,6 +883,61 @@ int fs_volume_render(fs_sim* s, int source, int slot, const double* par, uint8_t
 int fs_volume_views(fs_sim* s, const int* spec, const double* par, int n);
 int fs_volume_sample(fs_sim* s);
 int fs_volume_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped);
+
+/* ---- flow monitor (beyond the reference: its run() prints sum / min / max of whole padded arrays, simulation.cpp:73-93) ----
+ *
+ * Is the run still finite, what is the Courant number, is mass conserved between inlet and outlet, how much kinetic energy is
+ * in the box, what is the momentum deficit in the wake: the integrals and extrema of the state, per plane, whole and per x,
+ * each sum in one written order, so that a restatement in any language gives the same bits.
+ * STATE: the values as stored, q = dens, u, v, w = v_x, v_y, v_z, p = FS_PRESSURE.  A TARGET cell is an interior cell (1..w,
+ * 1..h, 1..d) with obs != 1 (read from the cell's flag byte).  Ghost cells and solid cells contribute no term, whatever they hold.
+ * ARITHMETIC: fp64 on the stored values widened, for fp32 and fp64 handles alike; every written operation is rounded once,
+ * without contraction (the library is built with -ffp-contract=off).  Products are (double)a * (double)b, which is exact on
+ * fp32 handles.  e = (u*u + v*v) + w*w.
+ * COLUMN record, one per (z, x), over the target cells of the rows y = 1..h in increasing y: the sums, each from +0.0,
+ *     cells, nonfinite, sum q, sum u, sum v, sum w, sum e, sum p, sum (u*u), sum (q*u)
+ * where a cell is nonfinite if any of its five values is NaN or +-Inf; the running maxima max |u|, max |v|, max |w|, max e, each
+ * from 0 by "if (a > m) m = a", so that a NaN never replaces the running value; and min q, max q, min p, max p, from +Inf and
+ * -Inf, by "if (a < m) m = a" and "if (a > m) m = a".
+ * PLANE record (FS_MONITOR_COLS = 16 numbers) per global plane z:
+ *     { cells, nonfinite, sum q, sum u, sum v, sum w, sum e, sum p, max |u|, max |v|, max |w|, max e, min q, max q, min p, max p }
+ * the sums are the column sums added over x = 1..w in increasing x from +0.0, the extrema the extrema of the columns' extrema
+ * by the same rules from the same starts.
+ * WHOLE record: the plane sums added in increasing z from +0.0, the extrema of the planes' extrema.
+ * X-PROFILE (FS_MONITOR_PROFILE_COLS = 5 numbers) per x = 1..w: { cells, sum u, sum (u*u), sum p, sum (q*u) }, the column sums
+ * of that x added in increasing z from +0.0.  sum u is the volume flux through the plane x in cell units (times h^2
+ * physically, h = 1 / cbrt(w*h*d)): with walls and solids at rest it is the same at every x of a divergence-free flow.
+ * sum (u*u) + sum p is the momentum flux a wake survey needs, sum (q*u) the smoke flux.
+ * EMPTY SET (no target cell): sums 0, the four maxima 0, each min +Inf, each max -Inf.
+ * Every number is a pure function of the five arrays and the flags: launch shape, tuning and timing cannot change a bit (no
+ * floating-point atomics; partial results are stored and added in the written order).
+ * DERIVED by the caller, in fp64: cfl_x = ((double)dt * w) * max |u|, cfl_y = ((double)dt * h) * max |v|, cfl_z =
+ * ((double)dt * d) * max |w| -- the length of the advection back-trace in cells (simulation.cpp:384-386); the kinetic energy
+ * per unit density 0.5 * sum e * h^3.
+ *
+ * fs_flow_monitor: the records of the state as it is now; changes nothing.  out = the WHOLE record; per_plane (may be NULL)
+ * receives 16 * d doubles, plane 1 first; x_profile (may be NULL) 5 * w doubles, x = 1 first.  Three launches: a streaming pass
+ * (lanes along x, each walking its column in y: 21 bytes per cell on an fp32 handle) into a workspace of 18 * w * d doubles
+ * that is allocated at the first use, never inside a later step; planes and profile; the whole record.
+ * Option "monitor_log" = N: fs_step takes such a record when (steps so far - 1) % "monitor_every" == 0, after the density
+ * advection of simulation.cpp:136 and before the frame dump, on the step's own stream without a host synchronisation.
+ * "monitor_stations" = "x1,x2,...": up to FS_MONITOR_STATIONS_MAX indices in 1..w whose X-PROFILE rows a record carries.
+ * fs_monitor_sample: appends a record of the state now (FS_EINVAL while the log is off), for callers who drive the passes
+ * themselves; its step number is that of the last completed step.
+ * fs_monitor_log: the retained records, oldest first, FS_MONITOR_LOG_COLS = 57 doubles each: { step, the 16 numbers of the
+ * WHOLE record, then 5 numbers for each of 8 stations }, an unused station 5 x NaN.  Step numbering, rows = NULL, max_rows too
+ * small and *n_dropped exactly as for fs_force_log; a fetch drains the log.
+ * Timing family "monitor": one launch counted per record.  Single GPU only: on a handle with a communicator (the FSNULL one
+ * included) the three entries and the three options are FS_EINVAL ("single-GPU"), and fs_comm_init on a handle whose
+ * "monitor_log" is on is FS_EINVAL.  Plane records are per global z so that slabs can follow.
+ */
+#define FS_MONITOR_COLS 16
+#define FS_MONITOR_PROFILE_COLS 5
+#define FS_MONITOR_STATIONS_MAX 8
+#define FS_MONITOR_LOG_COLS 57
+int fs_flow_monitor(fs_sim* s, double out[16], double* per_plane, double* x_profile);
+int fs_monitor_sample(fs_sim* s);
+int fs_monitor_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
 
 /* ---- multi-GPU z-slabs (one process per GPU; RCCL halo exchange over xGMI) -------- */
 

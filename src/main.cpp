@@ -68,6 +68,11 @@
 //                  else is refused.  Single GPU.
 //   --confinement EPS  vorticity confinement: every step begins with one confinement pass of strength EPS (option
 //                  "vorticity_confinement"; a decimal number >= 0, 0 = off; include/fluidsim.h has the definition).  Single GPU.
+//   --monitor FILE log the flow monitor's record after every step (option "monitor_log": integrals and extrema of the state over
+//                  the fluid cells, each sum in one written order; include/fluidsim.h has the definition) and write it to FILE
+//                  as CSV: fs_monitor_log's columns, then cfl_x, cfl_y, cfl_z = ((double)dt * N) * max |.|, numbers as %.17g
+//                  (they read back exactly).  --monitor-every K takes every Kth step (steps 1, K+1, ...), --monitor-stations
+//                  LIST ("x1,x2,...", up to 8 indices in 1..w) adds the x-profile rows of those planes.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -229,6 +234,30 @@ int write_residuals(fs_sim* sim, const char* path)
             fprintf(fp, ",%.17g", q[0] != 0.0 ? std::sqrt(q[1] / q[0]) : (double)NAN);
         }
         fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
+// the flow-monitor log of the run -> CSV (the columns of Simulation.monitor_log() in the Python package, then the Courant numbers)
+int write_monitor(fs_sim* sim, const char* path, int width, int height, int depth, float dt)
+{
+    long n = 0, dropped = 0;
+    if (fs_monitor_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * FS_MONITOR_LOG_COLS);
+    if (fs_monitor_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    if (dropped) fprintf(stderr, "simulation.out: %ld monitor records were overwritten before they were written\n", dropped);
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step,cells,nonfinite,sum_q,sum_u,sum_v,sum_w,sum_e,sum_p,max_abs_u,max_abs_v,max_abs_w,max_e,min_q,max_q,min_p,max_p");
+    for (int k = 0; k < FS_MONITOR_STATIONS_MAX; ++k) fprintf(fp, ",s%d_cells,s%d_sum_u,s%d_sum_uu,s%d_sum_p,s%d_sum_qu", k, k, k, k, k);
+    fprintf(fp, ",cfl_x,cfl_y,cfl_z\n");
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * FS_MONITOR_LOG_COLS];
+        fprintf(fp, "%ld", (long)r[0]);
+        for (int k = 1; k < FS_MONITOR_LOG_COLS; ++k) fprintf(fp, ",%.17g", r[k]);
+        fprintf(fp, ",%.17g,%.17g,%.17g\n", ((double)dt * width) * r[9], ((double)dt * height) * r[10], ((double)dt * depth) * r[11]);
     }
     const bool ok = fclose(fp) == 0;
     if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
@@ -432,6 +461,8 @@ int main(int argc, char** argv)
     double volume_view[3] = {45.0, 30.0, 200.0}, volume_range[2] = {0.0, 0.01}, volume_opacity = 0.05;
     int volume_cols = 512, volume_rows = 512;
     long volume_every = 1;
+    std::string monitor_path;
+    long monitor_every = 1;
     int dump_every = 1;
     std::vector<int> view_spec;
     std::vector<double> view_range;
@@ -484,13 +515,16 @@ int main(int argc, char** argv)
         if (key == "mean-from") { options.push_back({ "flow_stats_start", val }); return true; }
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         if (key == "confinement") { options.push_back({ "vorticity_confinement", val }); return true; }
+        if (key == "monitor") { monitor_path = val; return true; }
+        if (key == "monitor-every") { monitor_every = atol(val); return monitor_every >= 1; }
+        if (key == "monitor-stations") { options.push_back({ "monitor_stations", val }); return true; }
         return false;
     };
     static const char* const keys[] = { "grid", "steps", "acc", "speed", "dt", "diff", "stl", "dump-every", "dump-dir",
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
                                         "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
-                                        "volume-range", "volume-opacity", "volume-every", "confinement" };
+                                        "volume-range", "volume-opacity", "volume-every", "confinement", "monitor", "monitor-every", "monitor-stations" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -529,6 +563,10 @@ int main(int argc, char** argv)
     if (!forces_path.empty()) options.push_back({ "force_log", std::to_string(iter) });
     if (!body_forces_path.empty()) options.push_back({ "body_force_log", std::to_string(iter) });
     if (!residuals_path.empty()) options.push_back({ "residual_log", std::to_string(iter) });
+    if (!monitor_path.empty()) {
+        options.push_back({ "monitor_every", std::to_string(monitor_every) });
+        options.push_back({ "monitor_log", std::to_string(std::min(1048576L, iter > 0 ? (iter - 1) / monitor_every + 1 : 0L)) });
+    }
     if (!mean_dir.empty()) options.push_back({ "flow_stats", mean_moments ? "moments" : "mean" });
     std::vector<int> probe_cells;
     if (!probes_path.empty()) {
@@ -619,6 +657,7 @@ int main(int argc, char** argv)
     if (!forces_path.empty() && write_forces(sim, forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_force_log");
     if (!body_forces_path.empty() && write_body_forces(sim, body_forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_body_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
+    if (!monitor_path.empty() && write_monitor(sim, monitor_path.c_str(), width, height, depth, dt)) return die("fs_monitor_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
     if (!volume_dir.empty() && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
