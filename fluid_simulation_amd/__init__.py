@@ -13,12 +13,13 @@ from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
                          solve_reduction, BODY_INFO_DTYPE, BODY_LOG_DTYPE, pressure_moment, shift_moment,
                          MONITOR_LOG_NAMES, MONITOR_NAMES, MONITOR_PROFILE_NAMES, monitor_cfl)
+from . import inflow  # noqa: F401  (host-side helpers of Simulation.set_inflow)
 
 __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_force", "FORCE_LOG_DTYPE", "FluidsimError",
            "RESIDUAL_LOG_DTYPE", "solve_reduction",
            "BODY_INFO_DTYPE", "BODY_LOG_DTYPE", "pressure_moment", "shift_moment", "BODY_MAX", "BODY_COLS", "BODY_INFO_COLS",
            "BODY_LOG_COLS",
-           "MONITOR_COLS", "MONITOR_PROFILE_COLS", "MONITOR_STATIONS_MAX", "MONITOR_LOG_COLS", "MONITOR_NAMES",
+           "inflow", "MONITOR_COLS", "MONITOR_PROFILE_COLS", "MONITOR_STATIONS_MAX", "MONITOR_LOG_COLS", "MONITOR_NAMES",
            "MONITOR_PROFILE_NAMES", "MONITOR_LOG_NAMES", "monitor_cfl",
            "FIELD_NAMES", "STAT_NAMES",
            "STAT_MEAN_DENS", "STAT_MEAN_VX", "STAT_MEAN_VY", "STAT_MEAN_VZ", "STAT_MEAN_P", "STAT_UU", "STAT_VV", "STAT_WW",

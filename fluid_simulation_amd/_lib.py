@@ -27,6 +27,8 @@ RESIDUAL_LOG_COLS = 31      # FS_RESIDUAL_LOG_COLS: step, then per solve r0_sq, 
 MONITOR_COLS = 16           # FS_MONITOR_COLS: the flow monitor's PLANE / WHOLE record
 MONITOR_PROFILE_COLS = 5    # FS_MONITOR_PROFILE_COLS: cells, sum u, sum u*u, sum p, sum q*u of one x
 MONITOR_STATIONS_MAX = 8    # FS_MONITOR_STATIONS_MAX
+INFLOW_EDDIES_MAX = 65536   # FS_INFLOW_EDDIES_MAX: eddies of the inflow generator
+INFLOW_KNOTS_MAX = 4096     # FS_INFLOW_KNOTS_MAX: knots of its gust schedule
 MONITOR_LOG_COLS = 57       # FS_MONITOR_LOG_COLS: step, the whole record, then the profile row of each of 8 stations
 # FS_STAT_*: selectors of fs_flow_stats_field -- the five means, the seven (co)variances, the turbulence kinetic energy;
 # STAT_RAW or-ed in returns the raw sum instead
@@ -127,6 +129,10 @@ _SIGNATURES = {
     "fs_vortex_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_confine_vorticity": (C.c_int, [C.c_void_p, C.c_double]),
+    "fs_inflow_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fs_inflow_gust": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_inflow_plane": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_size_t]),
+    "fs_inflow_eddies": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_size_t]),
     "fs_flow_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fs_monitor_sample": (C.c_int, [C.c_void_p]),
     "fs_monitor_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),

@@ -25,6 +25,7 @@
 #include "flow_stats.h"
 #include "vortex.h"
 #include "confine.h"
+#include "inflow.h"
 #include "sample.h"
 #include "step_ring.h"
 
@@ -32,6 +33,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -73,8 +75,8 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_COUNT };
+const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 
@@ -124,6 +126,8 @@ struct EngineBase {
     virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int vortex_dump(const char* dir) = 0;
     virtual int confine_vorticity(double eps) = 0;
+    virtual int inflow_plane(long step, double* out) = 0;
+    virtual int inflow_eddies(long step, double* out) = 0;
     virtual int flow_monitor(double* out16, double* per_plane, double* x_profile) = 0;
     virtual int monitor_sample() = 0;
     virtual int monitor_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
@@ -194,6 +198,17 @@ struct fs_sim {
     int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
     double confinement = 0.0;    // "vorticity_confinement": strength of the confinement pass at the start of a step, 0 = off
     long n_confine = 0;          // confinement passes done, inside steps and by fs_confine_vorticity (fs_get_int)
+    // turbulent inflow (inflow.h): with "inflow" on, fs_step writes the x = 1 face from these instead of (speed, 0, 0)
+    bool inflow = false;
+    int inflow_n = 0;            // "inflow_eddies"
+    double inflow_sigma = 4.0, inflow_rms = 0.0;   // "inflow_sigma", "inflow_rms"
+    double inflow_convect = -1.0;   // "inflow_convect": cells per step, < 0 = "auto" (dt * width * speed)
+    uint64_t inflow_seed = 1;
+    std::vector<double> inflow_mean, inflow_scale;   // fs_inflow_profile: h x d each, empty = speed everywhere / 1 everywhere
+    std::vector<double> gust_t, gust_f;              // fs_inflow_gust: the knots
+    long inflow_gen = 0;         // bumped by fs_inflow_profile: the maps are uploaded anew
+    long n_inflow = 0;           // planes written by steps ("inflow_passes")
+    double inflow_convect_now() const { return inflow_convect < 0.0 ? ((double)dt * (double)W) * (double)speed : inflow_convect; }
     long n_zero_start = 0, n_project_advect = 0;   // projections / steps that took those paths (fs_get_int)
     int overlap = -1;            // z-slabs, how a pass and its halo exchange are scheduled: 0 the pass, then the exchange; 1 boundary
                                  // planes first, their exchange on the communication stream while the interior is computed; 2 boundary
@@ -535,6 +550,12 @@ struct Engine : EngineBase {
     // the per-step log, a device ring of records of MON_RESULT doubles (the whole record, then the stations' profile rows)
     double* mon_ws = nullptr;
     LogRing mon_ring;                   // for S->monitor_gen
+    // turbulent inflow (inflow.h): the two maps as uploaded for S->inflow_gen (null = not given), the eddy table of the step
+    // being written (room for inflow_cap entries), the result of fs_inflow_plane / fs_inflow_eddies; all stream-ordered reuse
+    double *inflow_dmean = nullptr, *inflow_dscale = nullptr, *inflow_out = nullptr, *inflow_dbg = nullptr;
+    fs::InflowEntry* inflow_tab = nullptr;
+    int inflow_cap = 0;
+    long inflow_up_gen = -1;
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -670,6 +691,8 @@ struct Engine : EngineBase {
         if (vol_rgb) hipFree(vol_rgb);
         if (vol_acc) hipFree(vol_acc);
         if (mon_ws) hipFree(mon_ws);
+        for (void* q : { (void*)inflow_dmean, (void*)inflow_dscale, (void*)inflow_out, (void*)inflow_dbg, (void*)inflow_tab })
+            if (q) hipFree(q);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
             if (q) hipFree(q);
         for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring, &mon_ring }) r->release();
@@ -1654,6 +1677,92 @@ struct Engine : EngineBase {
         return confine_pass("fs_confine_vorticity", eps);
     }
 
+    // ---- turbulent inflow (inflow.h; beyond the reference) -----------------------------------------------
+    // the parameters as they stand; FS_EINVAL where they do not make a finite amplitude or step t is out of range
+    int inflow_params(const char* who, long t, fs::InflowParams* p) const
+    {
+        p->seed = S->inflow_seed;
+        p->n = S->inflow_n;
+        p->h = g.H;
+        p->d = g.D;
+        p->sigma = S->inflow_sigma;
+        p->convect = S->inflow_convect_now();
+        p->amp = fs::inflow_amplitude(p->n, p->h, p->d, p->sigma, S->inflow_rms);
+        if (!std::isfinite(p->amp)) return fail(FS_EINVAL, "%s: the eddies' amplitude u_rms * sqrt(V / (N sigma^3)) is not finite", who);
+        if (!std::isfinite(p->convect) || !(p->convect >= 0.0)) return fail(FS_EINVAL, "%s: the convection dt * width * speed is negative or not finite", who);
+        if (!fs::inflow_step_ok(t, p->sigma, p->convect)) return fail(FS_EINVAL, "%s: step %ld is negative or beyond 2^53 eddy generations", who, t);
+        return FS_OK;
+    }
+    // the maps on the device as fs_inflow_profile last left them, and room in the table for the eddies
+    int ensure_inflow()
+    {
+        if (inflow_up_gen != S->inflow_gen) {
+            const size_t bytes = (size_t)g.H * (size_t)g.D * sizeof(double);
+            const std::vector<double>* host[2] = { &S->inflow_mean, &S->inflow_scale };
+            double** dev[2] = { &inflow_dmean, &inflow_dscale };
+            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued plane may still read the old maps
+            for (int k = 0; k < 2; ++k) {
+                if (host[k]->empty()) {
+                    if (*dev[k]) HIP_TRY(hipFree(*dev[k]));
+                    *dev[k] = nullptr;
+                    continue;
+                }
+                if (!*dev[k]) HIP_TRY(hipMalloc((void**)dev[k], bytes));
+                HIP_TRY(hipMemcpy(*dev[k], host[k]->data(), bytes, hipMemcpyHostToDevice));
+            }
+            inflow_up_gen = S->inflow_gen;
+        }
+        if (S->inflow_n > inflow_cap) {
+            HIP_TRY(hipStreamSynchronize(S->stream));
+            if (inflow_tab) HIP_TRY(hipFree(inflow_tab));
+            inflow_tab = nullptr;
+            inflow_cap = 0;
+            HIP_TRY(hipMalloc((void**)&inflow_tab, (size_t)S->inflow_n * sizeof(fs::InflowEntry)));
+            inflow_cap = S->inflow_n;
+        }
+        return FS_OK;
+    }
+    // the plane of step t: into the three velocities' x = 1 face, or (out not null) as 3 x d x h doubles into out
+    void inflow_launch(const fs::InflowParams& p, long t, double* out)
+    {
+        const double gust = fs::inflow_gust(S->gust_t.data(), S->gust_f.data(), (int)S->gust_t.size(), t);
+        ScopedSpan sp(S, FAM_INFLOW);
+        fs::launch_inflow_table(S->stream, p, t, inflow_tab, nullptr);
+        fs::launch_inflow_plane<T>(S->stream, g, p, inflow_tab, gust, (double)S->speed, inflow_dmean, inflow_dscale, arr[slot[FS_VX]],
+                                   arr[slot[FS_VY]], arr[slot[FS_VZ]], out);
+    }
+    int inflow_plane(long t, double* out) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_inflow_plane: the inflow generator needs a single-GPU handle");
+        fs::InflowParams p;
+        int rc = inflow_params("fs_inflow_plane", t, &p);
+        if (rc) return rc;
+        if ((rc = ensure_inflow())) return rc;
+        const size_t bytes = (size_t)3 * g.H * g.D * sizeof(double);
+        if (!inflow_out) HIP_TRY(hipMalloc((void**)&inflow_out, bytes));
+        inflow_launch(p, t, inflow_out);
+        HIP_TRY(hipMemcpyAsync(out, inflow_out, bytes, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+    int inflow_eddies(long t, double* out) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_inflow_eddies: the inflow generator needs a single-GPU handle");
+        fs::InflowParams p;
+        int rc = inflow_params("fs_inflow_eddies", t, &p);
+        if (rc) return rc;
+        if (p.n <= 0) return FS_OK;
+        const size_t bytes = (size_t)fs::INFLOW_EDDIES_MAX * 6 * sizeof(double);
+        if (!inflow_dbg) HIP_TRY(hipMalloc((void**)&inflow_dbg, bytes));
+        {
+            ScopedSpan sp(S, FAM_INFLOW);
+            fs::launch_inflow_table(S->stream, p, t, nullptr, inflow_dbg);
+        }
+        HIP_TRY(hipMemcpyAsync(out, inflow_dbg, (size_t)p.n * 6 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        return FS_OK;
+    }
+
     // ---- step (simulation.cpp:96-150) ---------------------------------------------------
     int step() override
     {
@@ -1673,13 +1782,22 @@ struct Engine : EngineBase {
         if ((rc = ensure_volume_ring())) return rc;
         if ((rc = ensure_tracers())) return rc;
         if ((rc = ensure_monitor_ring())) return rc;
+        fs::InflowParams inflow_p;
+        if (S->inflow) {
+            if (S->comm.active()) return fail(FS_EINVAL, "fs_step: the inflow generator (option \"inflow\") needs a single-GPU handle");
+            if ((rc = inflow_params("fs_step", S->steps_total, &inflow_p))) return rc;
+            if ((rc = ensure_inflow())) return rc;
+        }
         res_ran_now = 0;
         // "vorticity_confinement": the pass comes before everything the reference's step does
         if (S->confinement > 0.0 && (rc = confine_pass("fs_step", S->confinement))) return rc;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
-        {
+        if (S->inflow) {                                 // "inflow": the face from the inflow generator, at step number steps_total
+            inflow_launch(inflow_p, S->steps_total, nullptr);
+            ++S->n_inflow;
+        } else {
             ScopedSpan sp(S, FAM_MISC);
             fs::launch_inlet_velocity<T>(S->stream, g, sc, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]],
                                          (T)(float)S->speed);   // :103-105
@@ -3841,6 +3959,31 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         const double e = strtod(value, &end);
         if (end == value || *end || !std::isfinite(e) || !(e >= 0.0)) return fail(FS_EINVAL, "vorticity_confinement: a finite strength >= 0 (0 = off)");
         s->confinement = e;
+    } else if (k == "inflow") {
+        if (v != "on" && v != "off") return fail(FS_EINVAL, "inflow: on | off");
+        s->inflow = (v == "on");
+    } else if (k == "inflow_eddies") {
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end || n < 0 || n > fs::INFLOW_EDDIES_MAX) return fail(FS_EINVAL, "inflow_eddies: 0 .. %d", fs::INFLOW_EDDIES_MAX);
+        s->inflow_n = (int)n;
+    } else if (k == "inflow_sigma" || k == "inflow_rms" || k == "inflow_convect") {
+        if (k == "inflow_convect" && v == "auto") {
+            s->inflow_convect = -1.0;
+        } else {
+            char* end = nullptr;
+            const double x = strtod(value, &end);
+            const double least = (k == "inflow_sigma") ? 1.0 : 0.0;
+            if (end == value || *end || !std::isfinite(x) || !(x >= least))
+                return fail(FS_EINVAL, "%s: a finite number >= %g%s", key, least, k == "inflow_convect" ? ", or auto" : "");
+            (k == "inflow_sigma" ? s->inflow_sigma : k == "inflow_rms" ? s->inflow_rms : s->inflow_convect) = x;
+        }
+    } else if (k == "inflow_seed") {
+        char* end = nullptr;
+        errno = 0;
+        const unsigned long long x = strtoull(value, &end, 0);
+        if (end == value || *end || errno || value[0] == '-') return fail(FS_EINVAL, "inflow_seed: an unsigned 64-bit number");
+        s->inflow_seed = (uint64_t)x;
     } else if (k == "volume_every") {
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -3997,6 +4140,9 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "tracer_count") *out = (int)std::min<long>(s->tracer_seeded, s->tracers);   // slots a fetch returns
     else if (n == "tracer_seeded") *out = (int)std::min<long>(s->tracer_seeded, 2147483647L);   // particles seeded or released since the pool was cleared, saturating
     else if (n == "tracer_emitters") *out = (int)(s->tracer_emit.size() / 3);
+    else if (n == "inflow") *out = s->inflow ? 1 : 0;
+    else if (n == "inflow_eddies") *out = s->inflow_n;
+    else if (n == "inflow_passes") *out = (int)std::min<long>(s->n_inflow, 2147483647L);   // inlet planes the steps wrote through the inflow generator
     else if (n == "confinement_passes") *out = (int)std::min<long>(s->n_confine, 2147483647L);   // confinement passes done, in steps and by fs_confine_vorticity
     else if (n == "monitor_log") *out = s->monitor_log;
     else if (n == "monitor_every") *out = (int)s->monitor_every;
@@ -4021,6 +4167,9 @@ int fs_get_float(fs_sim* s, const char* name, float* out)
     std::string n = name;
     if (n == "dt") *out = s->dt; else if (n == "diff") *out = s->diff; else if (n == "visc") *out = s->visc;
     else if (n == "vorticity_confinement") *out = (float)s->confinement;
+    else if (n == "inflow_sigma") *out = (float)s->inflow_sigma;
+    else if (n == "inflow_rms") *out = (float)s->inflow_rms;
+    else if (n == "inflow_convect") *out = (float)s->inflow_convect_now();   // what "auto" stands for now
     else if (n.size() == 11 && n.compare(0, 7, "overlap") == 0 && n.compare(8, 3, "_ms") == 0 && n[7] >= '0' && n[7] <= '7')
         *out = (float)s->overlap_ms[n[7] - '0'];   // "overlap<k>_ms": slowest rank's ms per pass of candidate k = overlap mode + 4 * (CU mask on), 0 = not timed
     else return fail(FS_EINVAL, "unknown float member '%s'", name);
@@ -4414,6 +4563,48 @@ int fs_confine_vorticity(fs_sim* s, double epsilon)
 {
     ENGINE_OR_RETURN(s);
     return s->eng->confine_vorticity(epsilon);
+}
+int fs_inflow_profile(fs_sim* s, const double* u, const double* rms, size_t n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (s->comm.active()) return fail(FS_EINVAL, "fs_inflow_profile: the inflow generator needs a single-GPU handle");
+    const size_t want = (size_t)s->H * (size_t)s->D;
+    if (n != want) return fail(FS_EINVAL, "fs_inflow_profile: %zu values given, the inlet plane has height * depth = %zu", n, want);
+    for (const double* q : { u, rms })
+        for (size_t i = 0; q && i < n; ++i)
+            if (!std::isfinite(q[i])) return fail(FS_EINVAL, "fs_inflow_profile: entry %zu of the %s map is not finite", i, q == u ? "mean" : "scale");
+    if (u) s->inflow_mean.assign(u, u + n); else s->inflow_mean.clear();
+    if (rms) s->inflow_scale.assign(rms, rms + n); else s->inflow_scale.clear();
+    s->inflow_gen++;
+    return FS_OK;
+}
+int fs_inflow_gust(fs_sim* s, const double* steps, const double* factor, int n)
+{
+    if (!s) return fail(FS_EINVAL, "null handle");
+    if (n < 0 || n > fs::INFLOW_KNOTS_MAX) return fail(FS_EINVAL, "fs_inflow_gust: 0 .. %d knots", fs::INFLOW_KNOTS_MAX);
+    if (n > 0 && (!steps || !factor)) return fail(FS_EINVAL, "null argument");
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(steps[i]) || !std::isfinite(factor[i])) return fail(FS_EINVAL, "fs_inflow_gust: knot %d is not finite", i);
+        if (i > 0 && !(steps[i] > steps[i - 1])) return fail(FS_EINVAL, "fs_inflow_gust: the step numbers must be strictly increasing (knot %d)", i);
+    }
+    s->gust_t.assign(steps, steps + n);
+    s->gust_f.assign(factor, factor + n);
+    return FS_OK;
+}
+int fs_inflow_plane(fs_sim* s, long step, double* out, size_t n)
+{
+    ENGINE_OR_RETURN(s);
+    if (!out) return fail(FS_EINVAL, "null buffer");
+    if (n != (size_t)3 * s->H * s->D) return fail(FS_EINVAL, "fs_inflow_plane: room for %zu values, the plane has 3 * height * depth = %zu", n, (size_t)3 * s->H * s->D);
+    return s->eng->inflow_plane(step, out);
+}
+int fs_inflow_eddies(fs_sim* s, long step, double* out, size_t n)
+{
+    ENGINE_OR_RETURN(s);
+    if (n != (size_t)6 * s->inflow_n) return fail(FS_EINVAL, "fs_inflow_eddies: room for %zu values, there are 6 * %d", n, s->inflow_n);
+    if (n == 0) return FS_OK;
+    if (!out) return fail(FS_EINVAL, "null buffer");
+    return s->eng->inflow_eddies(step, out);
 }
 int fs_vortex_dump(fs_sim* s, const char* dir)
 {

@@ -227,4 +227,16 @@ template <class T>
 void launch_confine(hipStream_t st, const GridDesc& g, const T* vx, const T* vy, const T* vz, const uint8_t* flags, T* ox, T* oy,
                     T* oz, double k);
 
+// Turbulent inflow (inflow.h has the arithmetic, inflow.hip the two kernels).  launch_inflow_table: the entries of the p.n eddies
+// at step t into tab (where not null) and their ex, ey, ez and three signs into eddies (p.n x 6, where not null); nothing where
+// p.n == 0.  launch_inflow_plane: the x = 1 face, cells 1..H x 1..D, from tab's p.n entries, the gust factor and the two maps
+// (H x D doubles, y fastest; null = `speed` everywhere / 1 everywhere) -- cast into vx, vy, vz where out is null, else as three
+// planes of H x D doubles into out and the fields are not touched.  Single GPU (g.zh == 1).
+struct InflowParams;
+struct InflowEntry;
+void launch_inflow_table(hipStream_t st, const InflowParams& p, long t, InflowEntry* tab, double* eddies);
+template <class T>
+void launch_inflow_plane(hipStream_t st, const GridDesc& g, const InflowParams& p, const InflowEntry* tab, double gust, double speed,
+                         const double* mean, const double* scale, T* vx, T* vy, T* vz, double* out);
+
 }  // namespace fs

@@ -525,6 +525,44 @@ class Simulation:
         boundary handling of set_bounds.  The option vorticity_confinement=eps makes every step begin with such a pass."""
         check(self._L.fs_confine_vorticity(self._h, float(eps)))
 
+    def set_inflow(self, profile=None, rms=None, gust=None, eddies=0, sigma=4.0, u_rms=0.0, convect="auto", seed=1):
+        """Configures the inflow generator and turns it on (include/fluidsim.h, "turbulent inflow"; single-GPU handles): every
+        step then writes the x = 1 face as v_x = g(t) * U + r * u'_x, v_y = r * u'_y, v_z = r * u'_z.  `profile` (U) and
+        `rms` (r) are maps of shape (depth, height) or None (speed everywhere / 1 everywhere; fluid_simulation_amd.inflow
+        has power_law, log_law and intensity_profile); `gust` a sequence of (step, factor) knots or None; `eddies`, `sigma`,
+        `u_rms`, `convect` (cells per step or "auto") and `seed` the synthetic eddies.  The same options are constructor
+        keywords (inflow="on", inflow_eddies=N, inflow_sigma=S, inflow_rms=R, inflow_convect=C, inflow_seed=K).
+        set_option("inflow", "off") restores the uniform inlet."""
+        n = self.height * self.depth
+        maps = []
+        for m in (profile, rms):
+            maps.append(None if m is None else np.ascontiguousarray(m, dtype=np.float64).reshape(-1))
+            if maps[-1] is not None and maps[-1].size != n:
+                raise ValueError("an inflow map has height * depth = %d values, not %d" % (n, maps[-1].size))
+        check(self._L.fs_inflow_profile(self._h, *[None if m is None else m.ctypes.data for m in maps], n))
+        knots = np.zeros((0, 2)) if gust is None else np.ascontiguousarray(gust, dtype=np.float64).reshape(-1, 2)
+        ts, fs = np.ascontiguousarray(knots[:, 0]), np.ascontiguousarray(knots[:, 1])
+        check(self._L.fs_inflow_gust(self._h, ts.ctypes.data, fs.ctypes.data, len(ts)))
+        self.set_option("inflow_eddies", int(eddies))
+        self.set_option("inflow_sigma", repr(float(sigma)))
+        self.set_option("inflow_rms", repr(float(u_rms)))
+        self.set_option("inflow_convect", convect if isinstance(convect, str) else repr(float(convect)))
+        self.set_option("inflow_seed", int(seed))
+        self.set_option("inflow", "on")
+
+    def inflow_plane(self, step):
+        """The three fp64 components of the inlet plane at step number `step`, before the rounding to the field type, as an
+        array (3, depth, height) (fs_inflow_plane); works whether the inflow generator is on or off and changes no field."""
+        out = np.empty((3, self.depth, self.height), dtype=np.float64)
+        check(self._L.fs_inflow_plane(self._h, int(step), out.ctypes.data, out.size))
+        return out
+
+    def inflow_eddies(self, step):
+        """The synthetic eddies at step number `step` (fs_inflow_eddies): an array (N, 6) of ex, ey, ez and the three signs."""
+        out = np.empty((self._geti("inflow_eddies"), 6), dtype=np.float64)
+        check(self._L.fs_inflow_eddies(self._h, int(step), out.ctypes.data, out.size))
+        return out
+
     def isosurface(self, source, level):
         """The triangle mesh of {source > level} over the padded box (fs_isosurface; single-GPU handles): `source` is a
         field selector (DENS .. BUFFER) or ISO_VORTEX | VORTEX_*.  Returns (vertices (n, 3) float32 in the viewer's

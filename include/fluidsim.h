@@ -177,6 +177,17 @@ int fs_destroy(fs_sim* s);
  *                 forcing of simulation.cpp:103-105; the step then proceeds exactly as without it.  NOT the reference's
  *                 arithmetic.  May be changed at any time; single-GPU handles only (fs_step on a handle with a
  *                 communicator is FS_EINVAL while eps > 0).  fs_get_float "vorticity_confinement" answers it.
+ *   "inflow"      "off" (default) | "on": fs_step writes the x = 1 face from the inflow generator (see "turbulent inflow" below)
+ *                 instead of (speed, 0, 0); "on" with nothing else set writes the same numbers through the new path.  NOT the
+ *                 reference's arithmetic once a map, a gust or eddies are set.  Single-GPU handles only (fs_step on a handle
+ *                 with a communicator is FS_EINVAL while it is on);
+ *   "inflow_eddies" N, 0 (default: no fluctuations) .. 65536;  "inflow_sigma" the eddy radius in cells, >= 1 (default 4);
+ *   "inflow_rms"  the strength u_rms >= 0 (default 0);  "inflow_convect" cells an eddy moves per step, >= 0, or "auto" (default):
+ *                 ((double)dt * (double)width) * (double)speed as they are when a plane is made;  "inflow_seed" an unsigned
+ *                 64-bit number (default 1).  All may be changed at any time; a value that is not finite, negative, a sigma
+ *                 below 1 or more than 65536 eddies is FS_EINVAL and changes nothing.  fs_get_int answers "inflow" (0 / 1),
+ *                 "inflow_eddies" and "inflow_passes" (planes the steps wrote); fs_get_float "inflow_sigma" "inflow_rms"
+ *                 "inflow_convect" (what "auto" stands for now).
  * fs_get_int also answers "local_depth" "z_offset" "halo_depth" "last_advect_reach" "pair_shape" "triple_plan"
  * "two_sweep_fused" "mg_levels" "mg_first_replicated" (the first coarse level every slab rank holds whole) and, for
  * slab handles, "stream_syncs" (compute-stream synchronisations issued by slab steps; 0 on the step path) "reach_waits"
@@ -606,6 +617,60 @@ int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles);
  * for it.  fs_get_int "confinement_passes" counts the passes done, those inside steps included.
  */
 int fs_confine_vorticity(fs_sim* s, double epsilon);
+
+/* ---- turbulent inflow (beyond the reference: its only inflow is (speed, 0, 0) on the x = 1 face, simulation.cpp:103-105) ----
+ *
+ * An inflow generator for boundary layers, gusts and free-stream turbulence.  With option "inflow" = "on" fs_step writes, where
+ * the reference's step writes (speed, 0, 0) -- after the confinement pass, before the pre-diffusion snapshot -- to every cell
+ * (1, y, z), y in 1..h, z in 1..d, solid or not (the step's own setBounds calls deal with solids afterwards), at step number t =
+ * the steps this handle has completed:
+ *     v_x = (T)( g(t) * U(y,z) + r(y,z) * u'_x(y,z,t) )     v_y = (T)( r(y,z) * u'_y(y,z,t) )     v_z = (T)( r(y,z) * u'_z(y,z,t) )
+ * All arithmetic is fp64, one rounding per written operation, in exactly the order written here, without contraction; T, the
+ * handle's precision, enters in the last rounding only.  The stream is STATELESS: the plane is a pure function of the
+ * parameters and t, so a resumed run continues it and no launch shape can change a bit.
+ * MAPS: U and r are h x d doubles, index (z-1)*h + (y-1); a missing U is (double)speed everywhere, a missing r is 1.
+ * GUST: g(t) from up to FS_INFLOW_KNOTS_MAX knots (t_i, f_i), t_i strictly increasing; with x = (double)t: f_0 where x <= t_0,
+ * f_last where x >= t_last, else for t_i <= x < t_(i+1):  f_i + (f_(i+1) - f_i) * ((x - t_i) / (t_(i+1) - t_i)).  No knots: 1.
+ * Evaluated on the host.
+ * FLUCTUATIONS: the synthetic-eddy method of Jarrin, Benhamadouche, Laurence and Prosser (2006) with isotropic eddies of one
+ * radius.  Parameters: N eddies, radius sigma >= 1, strength u_rms >= 0, convection c >= 0 cells per step, a 64-bit seed.
+ * The eddies live in the box x in [1-sigma, 1+sigma), y in [1-sigma, h+sigma), z in [1-sigma, d+sigma); with two = 2.0*sigma,
+ * Ly = (double)(h-1) + two, Lz = (double)(d-1) + two its volume is V = (two * Ly) * Lz.
+ * HASH: on 64-bit unsigned integers modulo 2^64, MIX(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ * 0x94D049BB133111EB; z ^ (z >> 31) (splitmix64's finaliser).  With G = 0x9E3779B97F4A7C15,
+ *     HASH(k, gen, draw) = MIX( MIX( MIX(seed + G*(k+1)) + G*gen ) + G*(draw+1) ),     UNI(hash) = (double)(hash >> 11) * 2^-53.
+ * EDDY k (0 <= k < N) AT STEP t:  u0 = UNI(HASH(k, 0, 0));  start = u0 * two;  moved = (double)t * c;  s = start + moved;
+ * q = s / two;  gen = floor(q);  base = gen * two;  rem = s - base;  if rem < 0: rem = 0;  if not rem < two: rem = 0 and gen =
+ * gen + 1 (either can happen only by the rounding of q or base).  Then
+ *     ex = (1 - sigma) + rem,   ey = (1 - sigma) + UNI(HASH(k, gen, 1)) * Ly,   ez = (1 - sigma) + UNI(HASH(k, gen, 2)) * Lz,
+ * and the sign eps_j of component j = 0, 1, 2 (x, y, z) is -1 where bit 63 of HASH(k, gen, 3 + j) is set, else +1.  An eddy
+ * is so reborn at another (ey, ez) with other signs each time it leaves the box, however many times per step.  gen must stay
+ * below 2^53: a step number with ((double)t * c) / two + 2 >= 2^53, or a negative one, is FS_EINVAL.
+ * TENT: f(rho) = K * max(0, 1 - |rho|) with K = sqrt(3/2) correctly rounded (1.2247448713915890), so the integral of f^2 is 1.
+ * AMPLITUDE: A = u_rms * sqrt(V / ((double)N * ((sigma*sigma)*sigma))), correctly rounded square root; it must be finite.
+ * With inv = 1.0 / sigma:  ax_k = A * f((1 - ex_k) * inv),  and for the cell (y, z):
+ *     w_k = (ax_k * f(((double)y - ey_k) * inv)) * f(((double)z - ez_k) * inv),        u'_j = sum over k of eps_j,k * w_k,
+ * the sum in ascending k from +0.0, one addition per eddy (eps * w is exact).  An eddy with w_k == 0 adds +-0 and changes no bit,
+ * which is what lets an implementation skip it.  E[u'_j^2] = u_rms^2 at every inlet cell, those at the plane's edges included
+ * (the box is padded by sigma), and the three components are uncorrelated.
+ *
+ * fs_inflow_profile: sets both maps (n = h * d values each; a null pointer = that map is not given); a wrong n or an entry that
+ * is not finite is FS_EINVAL and changes nothing.  fs_inflow_gust: sets the schedule (n = 0 clears it); knots out of order or
+ * not finite, or more than FS_INFLOW_KNOTS_MAX, are FS_EINVAL and change nothing.  fs_inflow_plane: the three fp64 components
+ * before the last rounding for any step number, n = 3 * h * d values, component j of cell (y, z) at j*h*d + (z-1)*h + (y-1);
+ * works whether the option is on or off, changes no field and no counter but the timing family.  fs_inflow_eddies: n = 6 * N
+ * values, per eddy ex, ey, ez and the three signs as -1.0 / +1.0 (tests, plotting).  Two HIP kernels per plane (the eddy
+ * table, then the plane: a workgroup per 16 x 16 patch keeps the eddies that can reach it, in order; timing family "inflow",
+ * one launch counted per plane).  The maps and the table are allocated at the first use; with the option off a step launches
+ * and allocates nothing for it and is the step it was.  Every solver mode, both precisions.  Single GPU only: with a
+ * communicator fs_step (option on), fs_inflow_profile, fs_inflow_plane and fs_inflow_eddies are FS_EINVAL.
+ */
+#define FS_INFLOW_EDDIES_MAX 65536
+#define FS_INFLOW_KNOTS_MAX 4096
+int fs_inflow_profile(fs_sim* s, const double* u, const double* rms, size_t n);
+int fs_inflow_gust(fs_sim* s, const double* steps, const double* factor, int n);
+int fs_inflow_plane(fs_sim* s, long step, double* out, size_t n);
+int fs_inflow_eddies(fs_sim* s, long step, double* out, size_t n);
 
 /* ---- point probes and field sampling (beyond the reference: it evaluates a field off the grid only inside advect) ----
  *

@@ -73,6 +73,13 @@
 //                  as CSV: fs_monitor_log's columns, then cfl_x, cfl_y, cfl_z = ((double)dt * N) * max |.|, numbers as %.17g
 //                  (they read back exactly).  --monitor-every K takes every Kth step (steps 1, K+1, ...), --monitor-stations
 //                  LIST ("x1,x2,...", up to 8 indices in 1..w) adds the x-profile rows of those planes.  Single GPU.
+//   --inflow-profile FILE  the inflow generator (option "inflow" = "on"; include/fluidsim.h, "turbulent inflow"): FILE is text,
+//                  height * depth numbers of the mean map U (y fastest, then z), optionally followed by as many of the
+//                  fluctuation scale r; `#` starts a comment.  --inflow-gust FILE: lines `step factor`, the knots of the gust
+//                  schedule, steps strictly increasing.  --inflow-eddies N, --inflow-sigma S, --inflow-rms R, --inflow-convect C
+//                  (cells per step, or auto), --inflow-seed K: the synthetic eddies (options "inflow_eddies", "inflow_sigma",
+//                  "inflow_rms", "inflow_convect", "inflow_seed").  Any of these flags turns the generator on.  The step number
+//                  the eddies are taken at counts this run's steps: --resume restores the fields, not the count.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -339,6 +346,42 @@ int read_points(const char* path, std::vector<double>& pts)
     return ok ? 0 : 1;
 }
 
+// the numbers of --inflow-profile and --inflow-gust: separated by white space, `#` comments
+int read_numbers(const char* path, std::vector<double>& out)
+{
+    FILE* fp = fopen(path, "r");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot open %s\n", path); return 1; }
+    static char line[1 << 16];
+    int lineno = 0;
+    bool ok = true, whole = true;                        // whole: the previous piece ended its line
+    while (ok && fgets(line, sizeof line, fp)) {
+        if (whole) ++lineno;
+        const size_t len = strlen(line);
+        whole = len > 0 && line[len - 1] == '\n';
+        if (!whole && len + 1 == sizeof line) {
+            fprintf(stderr, "simulation.out: %s:%d: a line is longer than %zu characters\n", path, lineno, sizeof line - 2);
+            ok = false;
+            break;
+        }
+        if (char* hash = strchr(line, '#')) *hash = 0;
+        for (char* q = line; ok;) {
+            q += strspn(q, " \t\r\n");
+            if (!*q) break;
+            char* end = nullptr;
+            const double v = strtod(q, &end);
+            if (end == q || !strchr(" \t\r\n", *end)) {
+                fprintf(stderr, "simulation.out: %s:%d: not a number: %.20s\n", path, lineno, q);
+                ok = false;
+            } else {
+                out.push_back(v);
+                q = end;
+            }
+        }
+    }
+    fclose(fp);
+    return ok ? 0 : 1;
+}
+
 // the final tracer pool -> CSV (the arrays of fs_tracer_fetch)
 int write_tracers(fs_sim* sim, const char* path)
 {
@@ -461,7 +504,8 @@ int main(int argc, char** argv)
     double volume_view[3] = {45.0, 30.0, 200.0}, volume_range[2] = {0.0, 0.01}, volume_opacity = 0.05;
     int volume_cols = 512, volume_rows = 512;
     long volume_every = 1;
-    std::string monitor_path;
+    std::string monitor_path, inflow_profile_path, inflow_gust_path;
+    bool inflow = false;
     long monitor_every = 1;
     int dump_every = 1;
     std::vector<int> view_spec;
@@ -516,6 +560,13 @@ int main(int argc, char** argv)
         if (key == "mean-every") { options.push_back({ "flow_stats_every", val }); return true; }
         if (key == "confinement") { options.push_back({ "vorticity_confinement", val }); return true; }
         if (key == "monitor") { monitor_path = val; return true; }
+        if (key == "inflow-profile") { inflow_profile_path = val; inflow = true; return true; }
+        if (key == "inflow-gust") { inflow_gust_path = val; inflow = true; return true; }
+        if (key == "inflow-eddies") { options.push_back({ "inflow_eddies", val }); inflow = true; return true; }
+        if (key == "inflow-sigma") { options.push_back({ "inflow_sigma", val }); inflow = true; return true; }
+        if (key == "inflow-rms") { options.push_back({ "inflow_rms", val }); inflow = true; return true; }
+        if (key == "inflow-convect") { options.push_back({ "inflow_convect", val }); inflow = true; return true; }
+        if (key == "inflow-seed") { options.push_back({ "inflow_seed", val }); inflow = true; return true; }
         if (key == "monitor-every") { monitor_every = atol(val); return monitor_every >= 1; }
         if (key == "monitor-stations") { options.push_back({ "monitor_stations", val }); return true; }
         return false;
@@ -524,7 +575,8 @@ int main(int argc, char** argv)
                                         "precision", "solver", "omega", "mg-cycles", "seed", "resume", "forces", "residuals", "mean-flow", "mean-from",
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
                                         "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
-                                        "volume-range", "volume-opacity", "volume-every", "confinement", "monitor", "monitor-every", "monitor-stations" };
+                                        "volume-range", "volume-opacity", "volume-every", "confinement", "monitor", "monitor-every", "monitor-stations",
+                                        "inflow-profile", "inflow-gust", "inflow-eddies", "inflow-sigma", "inflow-rms", "inflow-convect", "inflow-seed" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -575,6 +627,25 @@ int main(int argc, char** argv)
     }
     if (!probe_log_path.empty()) options.push_back({ "probe_log", std::to_string(iter) });
     if (tracers > 0) options.push_back({ "tracers", std::to_string(tracers) });
+    if (inflow) options.push_back({ "inflow", "on" });
+    if (!inflow_profile_path.empty()) {
+        std::vector<double> maps;
+        const size_t cells = (size_t)height * (size_t)depth;
+        if (read_numbers(inflow_profile_path.c_str(), maps)) return 2;
+        if (maps.size() != cells && maps.size() != 2 * cells) {
+            fprintf(stderr, "simulation.out: %s holds %zu numbers, not height * depth = %zu or twice as many\n", inflow_profile_path.c_str(),
+                    maps.size(), cells);
+            return 2;
+        }
+        if (fs_inflow_profile(sim, maps.data(), maps.size() == cells ? nullptr : maps.data() + cells, cells)) return die("fs_inflow_profile");
+    }
+    if (!inflow_gust_path.empty()) {
+        std::vector<double> knots, steps, factors;
+        if (read_numbers(inflow_gust_path.c_str(), knots)) return 2;
+        if (knots.size() % 2) { fprintf(stderr, "simulation.out: %s: expected pairs `step factor`\n", inflow_gust_path.c_str()); return 2; }
+        for (size_t i = 0; i < knots.size(); i += 2) { steps.push_back(knots[i]); factors.push_back(knots[i + 1]); }
+        if (fs_inflow_gust(sim, steps.data(), factors.data(), (int)std::min<size_t>(steps.size(), 1u << 20))) return die("fs_inflow_gust");
+    }
     for (auto& kv : options)
         if (fs_set_option(sim, kv.first.c_str(), kv.second.c_str())) return die(kv.first.c_str());
     if (!tracer_emitters_path.empty()) {
