@@ -28,6 +28,7 @@
 #include "inflow.h"
 #include "sample.h"
 #include "step_ring.h"
+#include "options.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -387,6 +388,39 @@ struct LogRing {
             dst = (char*)dst + (size_t)run[r].count * bytes;
         }
         return e;
+    }
+
+    // The three steps every log's fetch shares; what lies between them (how slots become rows) is the log's own.
+    // 1. The sizes go out: `rows` (what the retained records amount to, in the entry's unit) into *n_out, the overwritten
+    //    records into *n_dropped.  Returns GO_ON, or the entry's answer: FS_OK for a caller that asked for the sizes alone
+    //    (`wants_data` false: nothing is drained), FS_EINVAL for one without the room.
+    struct FetchWords { const char *entry, *unit, *hint; };   // of the refusal: "fs_force_log", "rows", "rows = NULL"
+    enum { GO_ON = 1 };                                        // neither FS_OK nor an error code
+    int fetch_begin(const FetchWords& w, long rows, long room, bool wants_data, long* n_out, long* n_dropped) const
+    {
+        if (n_out) *n_out = rows;
+        if (n_dropped) *n_dropped = at.dropped();
+        if (!wants_data) return FS_OK;
+        if (room < rows) return fail(FS_EINVAL, "%s: %ld %s retained, room for %ld (pass %s to ask)", w.entry, rows, w.unit, room, w.hint);
+        return GO_ON;
+    }
+    // 2. The retained slots to the host, oldest first, and one synchronisation of `stream`: the whole slots into `dst`, or one
+    //    or two sections of the ring into `dst` and `dst2` (a null one is left out).  An empty log costs nothing: its fetch
+    //    is no synchronisation point.
+    hipError_t fetch_copy(hipStream_t stream, void* dst, const void* section = nullptr, size_t bytes = 0, void* dst2 = nullptr,
+                          const void* section2 = nullptr, size_t bytes2 = 0) const
+    {
+        if (at.retained() == 0) return hipSuccess;
+        hipError_t e = dst ? copy_out(stream, dst, section, bytes) : hipSuccess;
+        if (e == hipSuccess && dst2) e = copy_out(stream, dst2, section2, bytes2);
+        return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+    }
+    // 3. The records have been handed out: their step numbers into `steps` (if any), and the ring is empty again.
+    void fetch_end(long* steps = nullptr)
+    {
+        if (steps)
+            for (long i = 0, n = at.retained(); i < n; ++i) steps[i] = at.step_of(i);
+        at.drain();
     }
 };
 
@@ -2780,19 +2814,12 @@ struct Engine : EngineBase {
         if (S->comm.active()) return fail(FS_EINVAL, "fs_tracer_log: tracers need a single-GPU handle");
         int rc = ensure_tracers();
         if (rc) return rc;
-        const long n = tr_ring.at.retained();
-        if (n_frames) *n_frames = n;
-        if (n_dropped) *n_dropped = tr_ring.at.dropped();
-        if (!xyz && !status) return FS_OK;
-        if (max_frames < n) return fail(FS_EINVAL, "fs_tracer_log: %ld frames retained, room for %ld (pass both arrays NULL to ask)", n, max_frames);
-        if (n > 0) {
-            if (xyz) HIP_TRY(tr_ring.copy_out(S->stream, xyz, tracer_frame_xyz(0), (size_t)tr_cap * 3 * sizeof(double)));
-            if (status) HIP_TRY(tr_ring.copy_out(S->stream, status, tracer_frame_status(0), (size_t)tr_cap * sizeof(int32_t)));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-        }
-        if (steps)
-            for (long i = 0; i < n; ++i) steps[i] = tr_ring.at.step_of(i);
-        tr_ring.at.drain();
+        rc = tr_ring.fetch_begin({"fs_tracer_log", "frames", "both arrays NULL"}, tr_ring.at.retained(), max_frames,
+                                 xyz || status, n_frames, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
+        HIP_TRY(tr_ring.fetch_copy(S->stream, xyz, tracer_frame_xyz(0), (size_t)tr_cap * 3 * sizeof(double),
+                                   status, tracer_frame_status(0), (size_t)tr_cap * sizeof(int32_t)));
+        tr_ring.fetch_end(steps);
         return FS_OK;
     }
 
@@ -2852,17 +2879,12 @@ struct Engine : EngineBase {
         int rc = ensure_probe_ring();
         if (rc) return rc;
         const long n = probe_ring.at.retained();
-        if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = probe_ring.at.dropped();
-        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
-        if (max_rows < n) return fail(FS_EINVAL, "fs_probe_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        rc = probe_ring.fetch_begin({"fs_probe_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "probe records need the other slabs' planes; the FSNULL transport carries none");
         const size_t per = (size_t)probe_n * fs::PROBE_VALUES;   // one record
         std::vector<double> mine((size_t)n * per), all;
-        if (n > 0) {
-            HIP_TRY(probe_ring.copy_out(S->stream, mine.data()));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-        }
+        HIP_TRY(probe_ring.fetch_copy(S->stream, mine.data()));
         if ((rc = gather_plane_records(mine, all, "probe records"))) return rc;
         const size_t blob = mine.size();
         const int nr = S->comm.active() ? S->comm.nranks : 1, ld = S->D / nr;
@@ -2880,7 +2902,7 @@ struct Engine : EngineBase {
                 for (int j = 0; j < fs::PROBE_VALUES; ++j)
                     o[1 + (size_t)k * fs::PROBE_VALUES + j] = all[owner_off[(size_t)k] + (size_t)i * per + j];
         }
-        probe_ring.at.drain();
+        probe_ring.fetch_end();
         return FS_OK;
     }
 
@@ -3060,18 +3082,11 @@ struct Engine : EngineBase {
     {
         int rc = ensure_image_ring();
         if (rc) return rc;
-        const long n = img_ring.at.retained();
-        if (n_frames) *n_frames = n;
-        if (n_dropped) *n_dropped = img_ring.at.dropped();
-        if (!frames) return FS_OK;                       // sizes only: nothing drained
-        if (max_frames < n) return fail(FS_EINVAL, "fs_image_log: %ld frames retained, room for %ld (pass frames = NULL to ask)", n, max_frames);
-        if (n > 0) {
-            HIP_TRY(img_ring.copy_out(S->stream, frames));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-        }
-        if (steps)
-            for (long i = 0; i < n; ++i) steps[i] = img_ring.at.step_of(i);
-        img_ring.at.drain();
+        rc = img_ring.fetch_begin({"fs_image_log", "frames", "frames = NULL"}, img_ring.at.retained(), max_frames,
+                                  frames != nullptr, n_frames, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
+        HIP_TRY(img_ring.fetch_copy(S->stream, frames));
+        img_ring.fetch_end(steps);
         return FS_OK;
     }
 
@@ -3197,18 +3212,11 @@ struct Engine : EngineBase {
     {
         int rc = ensure_volume_ring();
         if (rc) return rc;
-        const long n = vol_ring.at.retained();
-        if (n_frames) *n_frames = n;
-        if (n_dropped) *n_dropped = vol_ring.at.dropped();
-        if (!frames) return FS_OK;                       // sizes only: nothing drained
-        if (max_frames < n) return fail(FS_EINVAL, "fs_volume_log: %ld frames retained, room for %ld (pass frames = NULL to ask)", n, max_frames);
-        if (n > 0) {
-            HIP_TRY(vol_ring.copy_out(S->stream, frames));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-        }
-        if (steps)
-            for (long i = 0; i < n; ++i) steps[i] = vol_ring.at.step_of(i);
-        vol_ring.at.drain();
+        rc = vol_ring.fetch_begin({"fs_volume_log", "frames", "frames = NULL"}, vol_ring.at.retained(), max_frames,
+                                  frames != nullptr, n_frames, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
+        HIP_TRY(vol_ring.fetch_copy(S->stream, frames));
+        vol_ring.fetch_end(steps);
         return FS_OK;
     }
 
@@ -3278,15 +3286,12 @@ struct Engine : EngineBase {
         int rc = ensure_force_ring();
         if (rc) return rc;
         const long n = force_ring.at.retained();
-        if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = force_ring.at.dropped();
-        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
-        if (max_rows < n) return fail(FS_EINVAL, "fs_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        rc = force_ring.fetch_begin({"fs_force_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
         const size_t per = 2 * plane_doubles();   // one step: both projections
         std::vector<double> mine((size_t)n * per), all;
-        HIP_TRY(force_ring.copy_out(S->stream, mine.data()));
-        HIP_TRY(hipStreamSynchronize(S->stream));
+        HIP_TRY(force_ring.fetch_copy(S->stream, mine.data()));
         if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
         const size_t blob = mine.size();
         for (long i = 0; i < n; ++i) {
@@ -3303,7 +3308,7 @@ struct Engine : EngineBase {
             o[7] = s[1][3];
             o[8] = s[1][4];
         }
-        force_ring.at.drain();
+        force_ring.fetch_end();
         return FS_OK;
     }
 
@@ -3483,16 +3488,13 @@ struct Engine : EngineBase {
         if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
         int rc = ensure_body_ring();
         if (rc) return rc;
-        const long steps = body_ring.at.retained();
-        const long nrec = body_B + 1, n = steps * nrec;
-        if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = body_ring.at.dropped();
-        if (!rows) return FS_OK;                         // sizes only: nothing drained
-        if (max_rows < n) return fail(FS_EINVAL, "fs_body_force_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        const long nrec = body_B + 1;                    // rows of one step
+        const long steps = body_ring.at.retained(), n = steps * nrec;
+        rc = body_ring.fetch_begin({"fs_body_force_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
         const size_t per = 2 * body_slot_doubles();      // one step: both projections
         std::vector<double> mine((size_t)steps * per);
-        HIP_TRY(body_ring.copy_out(S->stream, mine.data()));
-        HIP_TRY(hipStreamSynchronize(S->stream));
+        HIP_TRY(body_ring.fetch_copy(S->stream, mine.data()));
         for (long i = 0; i < steps; ++i)
             for (long k = 0; k < nrec; ++k) {
                 const double* a = &mine[(size_t)i * per + (size_t)k * fs::BODY_REC];
@@ -3507,7 +3509,7 @@ struct Engine : EngineBase {
                 o[14] = b[6];
                 o[15] = b[7];
             }
-        body_ring.at.drain();
+        body_ring.fetch_end();
         return FS_OK;
     }
 
@@ -3579,21 +3581,16 @@ struct Engine : EngineBase {
         int rc = ensure_monitor_ring();
         if (rc) return rc;
         const long n = mon_ring.at.retained();
-        if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = mon_ring.at.dropped();
-        if (!rows) return FS_OK;                         // sizes only: nothing drained
-        if (max_rows < n) return fail(FS_EINVAL, "fs_monitor_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        rc = mon_ring.fetch_begin({"fs_monitor_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
         std::vector<double> mine((size_t)n * fs::MON_RESULT);
-        if (n > 0) {
-            HIP_TRY(mon_ring.copy_out(S->stream, mine.data()));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-        }
+        HIP_TRY(mon_ring.fetch_copy(S->stream, mine.data()));
         for (long i = 0; i < n; ++i) {
             double* o = rows + (size_t)i * FS_MONITOR_LOG_COLS;
             o[0] = (double)mon_ring.at.step_of(i);
             memcpy(o + 1, &mine[(size_t)i * fs::MON_RESULT], fs::MON_RESULT * sizeof(double));
         }
-        mon_ring.at.drain();
+        mon_ring.fetch_end();
         return FS_OK;
     }
 
@@ -3671,15 +3668,12 @@ struct Engine : EngineBase {
         int rc = ensure_residual_ring();
         if (rc) return rc;
         const long n = res_ring.at.retained();
-        if (n_rows) *n_rows = n;
-        if (n_dropped) *n_dropped = res_ring.at.dropped();
-        if (!rows) return FS_OK;                         // sizes only: nothing drained, nothing exchanged
-        if (max_rows < n) return fail(FS_EINVAL, "fs_residual_log: %ld rows retained, room for %ld (pass rows = NULL to ask)", n, max_rows);
+        rc = res_ring.fetch_begin({"fs_residual_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
         if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
         const size_t rec = res_plane_doubles(), per = (size_t)RES_SOLVES * 2 * rec;   // one step: six solves, before and after
         std::vector<double> mine((size_t)n * per), all;
-        HIP_TRY(res_ring.copy_out(S->stream, mine.data()));
-        HIP_TRY(hipStreamSynchronize(S->stream));
+        HIP_TRY(res_ring.fetch_copy(S->stream, mine.data()));
         if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
         const size_t blob = mine.size();
         const double nan = std::nan("");
@@ -3701,7 +3695,7 @@ struct Engine : EngineBase {
                 q[4] = s[1][3];
             }
         }
-        res_ring.at.drain();
+        res_ring.fetch_end();
         return FS_OK;
     }
 };
@@ -3794,21 +3788,24 @@ int fs_destroy(fs_sim* s)
     return FS_OK;
 }
 
+// Values are read by the parsers of options.h: nothing may follow a number.  The tuning options that read theirs with a bare
+// atoi keep doing so, trailing characters and all ("12abc" is 12), because scripts in the field may rely on it: dump_every,
+// sweep_zc, sweep_abl, pair_zc, pair_shape, mg_cycles, mg_pre, mg_post, mg_coarse_iters, mg_min_planes, advect_window,
+// sweep_ry, sweep_fuse, vortex_ry, sweep_blocks, overlap, comm_cus.
 int fs_set_option(fs_sim* s, const char* key, const char* value)
 {
     if (!s || !key || !value) return fail(FS_EINVAL, "fs_set_option: null argument");
     std::string k = key, v = value;
+    long num = 0;   // the value of an option that is a number
+    int word = -1;  // ... that is a keyword: its place in the list
     if (k == "precision") {
         if (s->eng) return fail(FS_EINVAL, "precision must be set before first use");
-        if (v == "fp32") s->fp64 = false;
-        else if (v == "fp64") s->fp64 = true;
-        else return fail(FS_EINVAL, "precision: fp32 | fp64");
+        if ((word = fs::keyword(value, {"fp32", "fp64"})) < 0) return fail(FS_EINVAL, "precision: fp32 | fp64");
+        s->fp64 = (word == 1);
     } else if (k == "solver") {
-        if (v == "jacobi") s->solver = FS_SOLVER_JACOBI;
-        else if (v == "gs_lex") s->solver = FS_SOLVER_GS_LEX;
-        else if (v == "rbsor") s->solver = FS_SOLVER_RBSOR;
-        else if (v == "mg") s->solver = FS_SOLVER_MG;
-        else return fail(FS_EINVAL, "solver: jacobi | gs_lex | rbsor | mg");
+        const int solvers[] = {FS_SOLVER_JACOBI, FS_SOLVER_GS_LEX, FS_SOLVER_RBSOR, FS_SOLVER_MG};
+        if ((word = fs::keyword(value, {"jacobi", "gs_lex", "rbsor", "mg"})) < 0) return fail(FS_EINVAL, "solver: jacobi | gs_lex | rbsor | mg");
+        s->solver = solvers[word];
     } else if (k == "mg_cycles" || k == "mg_pre" || k == "mg_post" || k == "mg_coarse_iters") {
         const int n = atoi(value);
         if (n < (k == "mg_cycles" ? 0 : 1) || n > 1000) return fail(FS_EINVAL, "%s out of range", key);
@@ -3840,17 +3837,13 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
     } else if (k == "elide_dead_density_solve") {
         s->elide_dead = (v != "0");
     } else if (k == "force_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "force_log: steps kept, 0 (off) .. 1048576");
-        s->force_log = (int)n;
+        if (!fs::parse_int(value, 0, 1L << 20, &num)) return fail(FS_EINVAL, "force_log: steps kept, 0 (off) .. 1048576");
+        s->force_log = (int)num;
         s->force_log_gen++;
     } else if (k == "body_force_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "body_force_log: steps kept, 0 (off) .. 1048576");
-        if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "body_force_log: bodies are labelled on a single-GPU handle");
-        s->body_log = (int)n;
+        if (!fs::parse_int(value, 0, 1L << 20, &num)) return fail(FS_EINVAL, "body_force_log: steps kept, 0 (off) .. 1048576");
+        if (num > 0 && s->comm.active()) return fail(FS_EINVAL, "body_force_log: bodies are labelled on a single-GPU handle");
+        s->body_log = (int)num;
         s->body_log_gen++;
     } else if (k == "moment_origin") {
         double r[3];
@@ -3865,26 +3858,20 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         for (int a = 0; a < 3; ++a) s->moment_origin[a] = r[a];
         s->body_log_gen++;
     } else if (k == "residual_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "residual_log: steps kept, 0 (off) .. 1048576");
-        s->residual_log = (int)n;
+        if (!fs::parse_int(value, 0, 1L << 20, &num)) return fail(FS_EINVAL, "residual_log: steps kept, 0 (off) .. 1048576");
+        s->residual_log = (int)num;
         s->residual_log_gen++;
     } else if (k == "probe_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "probe_log: records kept, 0 (off) .. 1048576");
-        if ((size_t)n * (s->probes.size() / 3) * FS_PROBE_VALUES * sizeof(double) > ((size_t)1 << 30))
-            return fail(FS_EINVAL, "probe_log: %ld records of %zu probes exceed 1 GiB", n, s->probes.size() / 3);
-        s->probe_log = (int)n;
+        if (!fs::parse_int(value, 0, 1L << 20, &num)) return fail(FS_EINVAL, "probe_log: records kept, 0 (off) .. 1048576");
+        if ((size_t)num * (s->probes.size() / 3) * FS_PROBE_VALUES * sizeof(double) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "probe_log: %ld records of %zu probes exceed 1 GiB", num, s->probes.size() / 3);
+        s->probe_log = (int)num;
         s->probe_gen++;
     } else if (k == "image_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > 65536) return fail(FS_EINVAL, "image_log: frames kept, 0 (off) .. 65536");
-        if ((size_t)n * image_frame_bytes(s, s->image_views) > ((size_t)1 << 30))
-            return fail(FS_EINVAL, "image_log: %ld frames of %zu bytes exceed 1 GiB", n, image_frame_bytes(s, s->image_views));
-        s->image_log = (int)n;
+        if (!fs::parse_int(value, 0, 65536, &num)) return fail(FS_EINVAL, "image_log: frames kept, 0 (off) .. 65536");
+        if ((size_t)num * image_frame_bytes(s, s->image_views) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "image_log: %ld frames of %zu bytes exceed 1 GiB", num, image_frame_bytes(s, s->image_views));
+        s->image_log = (int)num;
         s->image_gen++;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
@@ -3892,113 +3879,78 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         }
     } else if (k == "tracers" || k == "tracer_log") {
         const bool pool = (k == "tracers");
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
         if (s->comm.active()) return fail(FS_EINVAL, "%s: tracers need a single-GPU handle", key);
-        if (end == value || *end || n < 0 || n > (pool ? 4194304L : 65536L))
+        if (!fs::parse_int(value, 0, pool ? 4194304L : 65536L, &num))
             return fail(FS_EINVAL, pool ? "tracers: slots of the pool, 0 (off) .. 4194304" : "tracer_log: frames kept, 0 (off) .. 65536");
-        const size_t C = (size_t)(pool ? n : s->tracers), N = (size_t)(pool ? s->tracer_log : n);
+        const size_t C = (size_t)(pool ? num : s->tracers), N = (size_t)(pool ? s->tracer_log : num);
         if (N * C * FS_TRACER_FRAME_BYTES > ((size_t)1 << 30))
             return fail(FS_EINVAL, "%s: %zu frames of %zu slots exceed 1 GiB", key, N, C);
-        if (pool) { s->tracers = (int)n; s->tracer_gen++; }
-        else { s->tracer_log = (int)n; s->tracer_log_gen++; }
+        if (pool) { s->tracers = (int)num; s->tracer_gen++; }
+        else { s->tracer_log = (int)num; s->tracer_log_gen++; }
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
             return s->eng->tracer_config();
         }
         if (pool) s->tracer_seeded = 0;
     } else if (k == "tracer_every") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
         if (s->comm.active()) return fail(FS_EINVAL, "tracer_every: tracers need a single-GPU handle");
-        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "tracer_every: K >= 1");
-        s->tracer_every = n;
+        if (!fs::parse_int(value, 1, 1L << 30, &num)) return fail(FS_EINVAL, "tracer_every: K >= 1");
+        s->tracer_every = num;
     } else if (k == "volume_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > 65536) return fail(FS_EINVAL, "volume_log: frames kept, 0 (off) .. 65536");
-        if ((size_t)n * volume_frame_bytes(s, s->volume_views) > ((size_t)1 << 30))
-            return fail(FS_EINVAL, "volume_log: %ld frames of %zu bytes exceed 1 GiB", n, volume_frame_bytes(s, s->volume_views));
-        if (n > 0 && s->comm.active()) return fail(FS_EINVAL, "volume_log: volumes are rendered on a single-GPU handle");
-        s->volume_log = (int)n;
+        if (!fs::parse_int(value, 0, 65536, &num)) return fail(FS_EINVAL, "volume_log: frames kept, 0 (off) .. 65536");
+        if ((size_t)num * volume_frame_bytes(s, s->volume_views) > ((size_t)1 << 30))
+            return fail(FS_EINVAL, "volume_log: %ld frames of %zu bytes exceed 1 GiB", num, volume_frame_bytes(s, s->volume_views));
+        if (num > 0 && s->comm.active()) return fail(FS_EINVAL, "volume_log: volumes are rendered on a single-GPU handle");
+        s->volume_log = (int)num;
         s->volume_gen++;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
             return s->eng->volume_config();
         }
     } else if (k == "monitor_log") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
         if (s->comm.active()) return fail(FS_EINVAL, "monitor_log: the flow monitor needs a single-GPU handle");
-        if (end == value || *end || n < 0 || n > (1L << 20)) return fail(FS_EINVAL, "monitor_log: records kept, 0 (off) .. 1048576");
-        s->monitor_log = (int)n;
+        if (!fs::parse_int(value, 0, 1L << 20, &num)) return fail(FS_EINVAL, "monitor_log: records kept, 0 (off) .. 1048576");
+        s->monitor_log = (int)num;
         s->monitor_gen++;
     } else if (k == "monitor_every") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
         if (s->comm.active()) return fail(FS_EINVAL, "monitor_every: the flow monitor needs a single-GPU handle");
-        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "monitor_every: K >= 1");
-        s->monitor_every = n;
+        if (!fs::parse_int(value, 1, 1L << 30, &num)) return fail(FS_EINVAL, "monitor_every: K >= 1");
+        s->monitor_every = num;
     } else if (k == "monitor_stations") {
         if (s->comm.active()) return fail(FS_EINVAL, "monitor_stations: the flow monitor needs a single-GPU handle");
         fs::MonitorStations st = {{0, 0, 0, 0, 0, 0, 0, 0}};
-        int n = 0;
-        for (const char* q = value; *q;) {
-            char* end = nullptr;
-            const long x = strtol(q, &end, 10);
-            if (end == q || (*end != ',' && *end != '\0') || (*end == ',' && end[1] == '\0') || x < 1 || x > s->W || n == fs::MON_STATIONS)
-                return fail(FS_EINVAL, "monitor_stations: \"x1,x2,...\", up to %d indices in 1 .. %d (\"\" = none)", fs::MON_STATIONS, s->W);
-            st.x[n++] = (int)x;
-            q = *end ? end + 1 : end;
-        }
+        if (!fs::parse_int_list(value, 1, s->W, fs::MON_STATIONS, st.x, &s->monitor_nstations))
+            return fail(FS_EINVAL, "monitor_stations: \"x1,x2,...\", up to %d indices in 1 .. %d (\"\" = none)", fs::MON_STATIONS, s->W);
         s->monitor_stations = st;
-        s->monitor_nstations = n;
         s->monitor_gen++;
     } else if (k == "vorticity_confinement") {
-        char* end = nullptr;
-        const double e = strtod(value, &end);
-        if (end == value || *end || !std::isfinite(e) || !(e >= 0.0)) return fail(FS_EINVAL, "vorticity_confinement: a finite strength >= 0 (0 = off)");
-        s->confinement = e;
+        if (!fs::parse_real(value, 0.0, &s->confinement)) return fail(FS_EINVAL, "vorticity_confinement: a finite strength >= 0 (0 = off)");
     } else if (k == "inflow") {
-        if (v != "on" && v != "off") return fail(FS_EINVAL, "inflow: on | off");
-        s->inflow = (v == "on");
+        if ((word = fs::keyword(value, {"off", "on"})) < 0) return fail(FS_EINVAL, "inflow: on | off");
+        s->inflow = (word == 1);
     } else if (k == "inflow_eddies") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 0 || n > fs::INFLOW_EDDIES_MAX) return fail(FS_EINVAL, "inflow_eddies: 0 .. %d", fs::INFLOW_EDDIES_MAX);
-        s->inflow_n = (int)n;
+        if (!fs::parse_int(value, 0, fs::INFLOW_EDDIES_MAX, &num)) return fail(FS_EINVAL, "inflow_eddies: 0 .. %d", fs::INFLOW_EDDIES_MAX);
+        s->inflow_n = (int)num;
     } else if (k == "inflow_sigma" || k == "inflow_rms" || k == "inflow_convect") {
         if (k == "inflow_convect" && v == "auto") {
             s->inflow_convect = -1.0;
         } else {
-            char* end = nullptr;
-            const double x = strtod(value, &end);
             const double least = (k == "inflow_sigma") ? 1.0 : 0.0;
-            if (end == value || *end || !std::isfinite(x) || !(x >= least))
+            if (!fs::parse_real(value, least, k == "inflow_sigma" ? &s->inflow_sigma : k == "inflow_rms" ? &s->inflow_rms : &s->inflow_convect))
                 return fail(FS_EINVAL, "%s: a finite number >= %g%s", key, least, k == "inflow_convect" ? ", or auto" : "");
-            (k == "inflow_sigma" ? s->inflow_sigma : k == "inflow_rms" ? s->inflow_rms : s->inflow_convect) = x;
         }
     } else if (k == "inflow_seed") {
-        char* end = nullptr;
-        errno = 0;
-        const unsigned long long x = strtoull(value, &end, 0);
-        if (end == value || *end || errno || value[0] == '-') return fail(FS_EINVAL, "inflow_seed: an unsigned 64-bit number");
-        s->inflow_seed = (uint64_t)x;
+        if (!fs::parse_u64(value, &s->inflow_seed)) return fail(FS_EINVAL, "inflow_seed: an unsigned 64-bit number");
     } else if (k == "volume_every") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "volume_every: K >= 1");
-        s->volume_every = n;
+        if (!fs::parse_int(value, 1, 1L << 30, &num)) return fail(FS_EINVAL, "volume_every: K >= 1");
+        s->volume_every = num;
     } else if (k == "image_every") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
-        if (end == value || *end || n < 1 || n > (1L << 30)) return fail(FS_EINVAL, "image_every: K >= 1");
-        s->image_every = n;
+        if (!fs::parse_int(value, 1, 1L << 30, &num)) return fail(FS_EINVAL, "image_every: K >= 1");
+        s->image_every = num;
     } else if (k == "flow_stats") {
-        if (v == "off") s->flow_stats = 0;
-        else if (v == "mean") s->flow_stats = fs::ST_NMEAN;
-        else if (v == "moments") s->flow_stats = fs::ST_NMOMENTS;
-        else return fail(FS_EINVAL, "flow_stats: off | mean | moments");
+        const int kinds[] = {0, fs::ST_NMEAN, fs::ST_NMOMENTS};
+        if ((word = fs::keyword(value, {"off", "mean", "moments"})) < 0) return fail(FS_EINVAL, "flow_stats: off | mean | moments");
+        s->flow_stats = kinds[word];
         s->flow_stats_gen++;
         s->flow_stats_n = 0;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
@@ -4006,23 +3958,21 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
             return s->eng->flow_stats_config();
         }
     } else if (k == "flow_stats_every" || k == "flow_stats_start") {
-        char* end = nullptr;
-        const long n = strtol(value, &end, 10);
         const bool every = (k == "flow_stats_every");
-        if (end == value || *end || n < (every ? 1 : 0) || n > (1L << 30))
+        if (!fs::parse_int(value, every ? 1 : 0, 1L << 30, &num))
             return fail(FS_EINVAL, every ? "flow_stats_every: N >= 1" : "flow_stats_start: S >= 0");
-        (every ? s->flow_stats_every : s->flow_stats_start) = n;
+        (every ? s->flow_stats_every : s->flow_stats_start) = num;
     } else if (k == "dump_async") {
         s->dump_async = (v != "0");
     } else if (k == "fuse_advect") {
         s->fuse_advect = (v != "0");
     } else if (k == "zero_start" || k == "fuse_project_advect") {
-        if (v != "auto" && v != "0" && v != "1") return fail(FS_EINVAL, "%s: auto | 0 | 1", key);
-        (k == "zero_start" ? s->zero_start : s->fuse_project_advect) = (v == "auto") ? -1 : atoi(value);
+        if ((word = fs::keyword(value, {"auto", "0", "1"})) < 0) return fail(FS_EINVAL, "%s: auto | 0 | 1", key);
+        (k == "zero_start" ? s->zero_start : s->fuse_project_advect) = word - 1;
     } else if (k == "overlap") {
         if (s->eng && s->overlap_plan >= 0) return fail(FS_EINVAL, "overlap must be set before the first solve");
-        s->overlap = (v == "auto") ? -1 : atoi(value);
-        if (s->overlap < -1 || s->overlap > 3 || (v != "auto" && v != "0" && v != "1" && v != "2" && v != "3"))
+        s->overlap = (v == "auto") ? -1 : atoi(value);   // a refused value stays behind, as it always did
+        if (s->overlap < -1 || s->overlap > 3 || fs::keyword(value, {"auto", "0", "1", "2", "3"}) < 0)
             return fail(FS_EINVAL, "overlap: auto | 0 | 1 | 2 | 3");
     } else if (k == "comm_cus") {
         if (s->eng) return fail(FS_EINVAL, "comm_cus must be set before first use");
@@ -4051,29 +4001,18 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (r != 1 && r != 2) return fail(FS_EINVAL, "vortex_ry: 1 | 2");
         s->tune.vortex_ry = r;
     } else if (k == "project_kernels") {
-        if (v == "cell") s->tune.project_cell = 1;
-        else if (v == "march") s->tune.project_cell = 0;
-        else return fail(FS_EINVAL, "project_kernels: march | cell");
+        if ((word = fs::keyword(value, {"march", "cell"})) < 0) return fail(FS_EINVAL, "project_kernels: march | cell");
+        s->tune.project_cell = word;
     } else if (k == "advect_kernels") {
-        if (v == "cell") s->tune.advect_cell = 1;
-        else if (v == "celltab") s->tune.advect_cell = 2;
-        else if (v == "row") s->tune.advect_cell = 0;
-        else if (v == "tile") s->tune.advect_cell = 3;
-        else return fail(FS_EINVAL, "advect_kernels: cell | celltab | tile | row");
+        if ((word = fs::keyword(value, {"row", "cell", "celltab", "tile"})) < 0) return fail(FS_EINVAL, "advect_kernels: cell | celltab | tile | row");
+        s->tune.advect_cell = word;
     } else if (k == "advect_window") {
         const int n = atoi(value);
         if (n < 1 || n > 128) return fail(FS_EINVAL, "advect_window: 1 .. 128");
         s->tune.advect_window = n;
-    } else if (k == "wall_free") {
-        if (v == "0") s->tune.wall_free = 0;
-        else if (v == "auto") s->tune.wall_free = 1;
-        else if (v == "1") s->tune.wall_free = 2;
-        else return fail(FS_EINVAL, "wall_free: 0 | auto | 1");
-    } else if (k == "mask_free") {
-        if (v == "0") s->tune.mask_free = 0;
-        else if (v == "auto") s->tune.mask_free = 1;
-        else if (v == "1") s->tune.mask_free = 2;
-        else return fail(FS_EINVAL, "mask_free: 0 | auto | 1");
+    } else if (k == "wall_free" || k == "mask_free") {
+        if ((word = fs::keyword(value, {"0", "auto", "1"})) < 0) return fail(FS_EINVAL, "%s: 0 | auto | 1", key);
+        (k == "wall_free" ? s->tune.wall_free : s->tune.mask_free) = word;
     } else if (k == "chunk_cost") {
         // per-iteration costs of the general, wall-free and mask-free bodies the z chunks are balanced by; "0" = equal chunks
         fs::ChunkCost c;
@@ -4086,10 +4025,8 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
     } else if (k == "pair_shape") {
         s->tune.pair_shape = atoi(value);
     } else if (k == "two_sweep_kernel") {
-        if (v == "auto") s->tune.two_kind = 0;
-        else if (v == "pair") s->tune.two_kind = 1;
-        else if (v == "fused") s->tune.two_kind = 2;
-        else return fail(FS_EINVAL, "two_sweep_kernel: auto | pair | fused");
+        if ((word = fs::keyword(value, {"auto", "pair", "fused"})) < 0) return fail(FS_EINVAL, "two_sweep_kernel: auto | pair | fused");
+        s->tune.two_kind = word;
     } else {
         return fail(FS_EINVAL, "unknown option '%s'", key);
     }
