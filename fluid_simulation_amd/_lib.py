@@ -65,6 +65,14 @@ VOLUME_VIEWS_MAX = 4
 VOLUME_PARAMS = 11      # vmin, vmax, opacity, step, t_min, obstacle r g b, background r g b
 VOLUME_CAMERA = 11      # eye[3], target[3], up[3], half_height, ortho
 VOLUME_SAMPLES_MAX = 16384
+# heat and buoyancy: entries of fs_heat_params, columns of the heat budget and of a row of fs_heat_log, the temperature as a
+# source of fs_sample, the image and volume entries and fs_isosurface, the codes of `up`
+HEAT_PARAMS = 15        # FS_HEAT_PARAMS
+HEAT_COLS = 9           # FS_HEAT_COLS
+HEAT_LOG_COLS = 10      # FS_HEAT_LOG_COLS: step, then the budget
+SOURCE_HEAT = 8192      # FS_SOURCE_HEAT
+HEAT_NAMES = ["cells", "sum", "sum_sq", "max", "min", "held", "loss", "outflow", "inflow"]
+HEAT_UP = {"+x": 0, "-x": 1, "+y": 2, "-y": 3, "+z": 4, "-z": 5}
 
 
 class FluidsimError(RuntimeError):
@@ -129,6 +137,14 @@ _SIGNATURES = {
     "fs_vortex_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_vortex_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "fs_confine_vorticity": (C.c_int, [C.c_void_p, C.c_double]),
+    "fs_heat_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_heat_params_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "fs_heat_apply": (C.c_int, [C.c_void_p]),
+    "fs_heat_transport": (C.c_int, [C.c_void_p]),
+    "fs_heat_budget": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fs_heat_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_heat_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    "fs_heat_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_inflow_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "fs_inflow_gust": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fs_inflow_plane": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_size_t]),

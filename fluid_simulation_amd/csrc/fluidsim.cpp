@@ -26,6 +26,7 @@
 #include "vortex.h"
 #include "confine.h"
 #include "inflow.h"
+#include "heat.h"
 #include "sample.h"
 #include "step_ring.h"
 #include "options.h"
@@ -76,10 +77,18 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_COUNT };
-const char* const kFamilyNames[FAM_COUNT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_HEAT, FAM_COUNT };
+const char* const kFamilyNames[FAM_HEAT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
+// the families added since (tests/test_inflow_cpu.py pins the text of the table above): FAM_HEAT onwards
+const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT] = { "heat" };
+inline const char* family_name(int f) { return f < FAM_HEAT ? kFamilyNames[f] : kLaterFamilyNames[f - FAM_HEAT]; }
 
 constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
+// heat (heat.h): two more slots of the engine's slot table behind the public fields -- the temperature and its pre-solve
+// snapshot -- and two more arrays in the pool while heat is on
+constexpr int NHEAT = 2, NSLOT = FS_NFIELDS + NHEAT, NPOOL_MAX = NPOOL + NHEAT;
+constexpr int F_THETA = FS_NFIELDS, F_THETA_PREV = FS_NFIELDS + 1;
+static_assert(fs::HEAT_PARAMS == FS_HEAT_PARAMS && fs::HEAT_COLS == FS_HEAT_COLS && FS_HEAT_LOG_COLS == 1 + FS_HEAT_COLS, "heat.h restates the header");
 
 struct Span {
     hipEvent_t a, b;
@@ -127,6 +136,13 @@ struct EngineBase {
     virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
     virtual int vortex_dump(const char* dir) = 0;
     virtual int confine_vorticity(double eps) = 0;
+    virtual int heat_config(const double* par) = 0;          // apply fs_heat_params (validated): allocate or free, set up the log
+    virtual int heat_apply() = 0;
+    virtual int heat_transport() = 0;
+    virtual int heat_budget(double* out, double* per_plane) = 0;
+    virtual int heat_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
+    virtual int heat_get(void* dst, size_t n, int elem) = 0;
+    virtual int heat_set(const void* src, size_t n, int elem) = 0;
     virtual int inflow_plane(long step, double* out) = 0;
     virtual int inflow_eddies(long step, double* out) = 0;
     virtual int flow_monitor(double* out16, double* per_plane, double* x_profile) = 0;
@@ -199,6 +215,10 @@ struct fs_sim {
     int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
     double confinement = 0.0;    // "vorticity_confinement": strength of the confinement pass at the start of a step, 0 = off
     long n_confine = 0;          // confinement passes done, inside steps and by fs_confine_vorticity (fs_get_int)
+    // heat and buoyancy (heat.h): the parameters as fs_heat_params last set them; mode 0 = off, 1 = manual, 2 = in fs_step
+    double heat[fs::HEAT_PARAMS] = {0, 0, 0, 0, 2, 0, 0, 0, 1, 1, 1, 1, 1, 1, 0};
+    int heat_mode() const { return (int)heat[fs::HP_MODE]; }
+    long n_heat_apply = 0, n_heat_transport = 0;   // passes done, inside steps and by fs_heat_apply / fs_heat_transport (fs_get_int)
     // turbulent inflow (inflow.h): with "inflow" on, fs_step writes the x = 1 face from these instead of (speed, 0, 0)
     bool inflow = false;
     int inflow_n = 0;            // "inflow_eddies"
@@ -427,7 +447,7 @@ struct LogRing {
 // what the image entries accept without looking at the state: a source of fs_sample by its bits, and a colour range
 bool image_source_ok(int source)
 {
-    if (source >= 0 && source < FS_NFIELDS) return true;
+    if ((source >= 0 && source < FS_NFIELDS) || source == FS_SOURCE_HEAT) return true;
     if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX) return (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS;
     if (source >= 0 && (source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
         const int sel = source & (FS_SAMPLE_STAT - 1), which = sel & ~FS_STAT_RAW;
@@ -476,9 +496,13 @@ struct Engine : EngineBase {
     size_t pool_stride = 0;
     int pool_per = 1;
     std::vector<T*> gather_chunks;      // the same behind gathered / gathered3 (z-slabs, allocated at the first gather)
-    T* arr[NPOOL] = {nullptr};          // LEAD-shifted pointers
-    int slot[FS_NFIELDS];               // field -> array id (aliases allowed inside a step)
-    bool held[NPOOL] = {false};         // temporaries owned by a running solve
+    T* arr[NPOOL_MAX] = {nullptr};      // LEAD-shifted pointers; the last NHEAT exist while heat is on
+    int slot[NSLOT];                    // field -> array id (aliases allowed inside a step); F_THETA / F_THETA_PREV: -1 while heat is off
+    bool held[NPOOL_MAX] = {false};     // temporaries owned by a running solve
+    int npool = NPOOL;                  // arrays of the pool: NPOOL_MAX while heat is on
+    T* heat_chunk = nullptr;            // the allocation behind arr[NPOOL ..]
+    double* heat_ws = nullptr;          // workspace of the heat budget's three launches (stream-ordered reuse)
+    LogRing heat_ring;                  // the per-step heat log: records of HEAT_COLS doubles
     uint8_t* flags = nullptr;           // shifted like the fields
     uint8_t* kill = nullptr;            // one byte per four cells for the sweeps; byte (cell+3)/4
     fs::MaskPlan maskplan;              // single GPU, fp32: which rows are free of kill bytes (the three-sweep kernel's mask-free body)
@@ -642,6 +666,7 @@ struct Engine : EngineBase {
         }
         for (int i = 0; i < NPOOL; ++i) arr[i] = pool_chunks[(size_t)(i / pool_per)] + (size_t)(i % pool_per) * pool_stride + g.lead;
         for (int f = 0; f < FS_NFIELDS; ++f) slot[f] = f;
+        slot[F_THETA] = slot[F_THETA_PREV] = -1;
         uint8_t* fb = nullptr;
         HIP_TRY(hipMalloc((void**)&fb, g.n));
         HIP_TRY(hipMemsetAsync(fb, 0, g.n, S->stream));
@@ -725,11 +750,13 @@ struct Engine : EngineBase {
         if (vol_rgb) hipFree(vol_rgb);
         if (vol_acc) hipFree(vol_acc);
         if (mon_ws) hipFree(mon_ws);
+        if (heat_chunk) hipFree(heat_chunk);
+        if (heat_ws) hipFree(heat_ws);
         for (void* q : { (void*)inflow_dmean, (void*)inflow_dscale, (void*)inflow_out, (void*)inflow_dbg, (void*)inflow_tab })
             if (q) hipFree(q);
         for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
             if (q) hipFree(q);
-        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring, &mon_ring }) r->release();
+        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring, &mon_ring, &heat_ring }) r->release();
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -740,13 +767,13 @@ struct Engine : EngineBase {
     // ---- array pool ------------------------------------------------------------------
     bool referenced(int id) const
     {
-        for (int f = 0; f < FS_NFIELDS; ++f)
+        for (int f = 0; f < NSLOT; ++f)
             if (slot[f] == id) return true;
         return held[id];
     }
     int acquire(int not_a = -1, int not_b = -1)
     {
-        for (int i = 0; i < NPOOL; ++i)
+        for (int i = 0; i < npool; ++i)
             if (i != not_a && i != not_b && !referenced(i)) { held[i] = true; return i; }
         return -1;   // cannot happen: NPOOL covers the worst case of a step
     }
@@ -762,7 +789,7 @@ struct Engine : EngineBase {
     static bool beats(M ms, M best) { return ms < best * (M)0.985; }
     bool shared_slot(int f) const
     {
-        for (int k = 0; k < FS_NFIELDS; ++k)
+        for (int k = 0; k < NSLOT; ++k)
             if (k != f && slot[k] == slot[f]) return true;
         return false;
     }
@@ -784,7 +811,7 @@ struct Engine : EngineBase {
     {
         if (!halos_dirty || !S->comm.active()) { halos_dirty = false; return FS_OK; }
         halos_dirty = false;
-        bool done[NPOOL] = {false};
+        bool done[NPOOL_MAX] = {false};
         for (int f = 0; f < FS_NFIELDS; ++f) {
             if (f == FS_OBS || done[slot[f]]) continue;
             done[slot[f]] = true;
@@ -1711,6 +1738,186 @@ struct Engine : EngineBase {
         return confine_pass("fs_confine_vorticity", eps);
     }
 
+    // ---- heat and buoyancy (heat.h; beyond the reference) ------------------------------------------------
+    // The temperature and its pre-solve snapshot are slots F_THETA / F_THETA_PREV of the slot table, behind the public
+    // fields, and two more arrays of the pool: allocated when heat is switched on, freed when it is switched off.
+    bool heat_on() const { return heat_chunk != nullptr; }
+    int heat_alloc()
+    {
+        if (heat_chunk) return FS_OK;
+        T* chunk = nullptr;
+        hipError_t e = hipMalloc((void**)&chunk, (size_t)NHEAT * pool_stride * sizeof(T));
+        if (e != hipSuccess) return fail(FS_ENOMEM, "fs_heat_params: the temperature arrays: %s", hipGetErrorString(e));
+        if ((e = hipMemsetAsync(chunk, 0, (size_t)NHEAT * pool_stride * sizeof(T), S->stream)) != hipSuccess) {
+            hipFree(chunk);
+            return fail(FS_EHIP, "fs_heat_params: clearing the temperature arrays: %s", hipGetErrorString(e));
+        }
+        heat_chunk = chunk;
+        for (int k = 0; k < NHEAT; ++k) {
+            arr[NPOOL + k] = chunk + (size_t)k * pool_stride + g.lead;
+            held[NPOOL + k] = false;
+        }
+        npool = NPOOL_MAX;
+        slot[F_THETA] = NPOOL;
+        slot[F_THETA_PREV] = NPOOL + 1;
+        return FS_OK;
+    }
+    // The pool's arrays are interchangeable, so a field may live in one of the two that go: it moves to a free one that stays.
+    int heat_free()
+    {
+        if (!heat_chunk) return FS_OK;
+        slot[F_THETA] = slot[F_THETA_PREV] = -1;
+        for (int id = NPOOL; id < NPOOL_MAX; ++id) {
+            if (!referenced(id)) continue;
+            int to = -1;
+            for (int i = 0; i < NPOOL && to < 0; ++i)
+                if (!referenced(i)) to = i;
+            if (to < 0) return fail(FS_ENOMEM, "array pool exhausted");   // cannot happen: NPOOL covers the fields
+            fs::launch_copy<T>(S->stream, g, arr[id], arr[to]);
+            for (int f = 0; f < FS_NFIELDS; ++f)
+                if (slot[f] == id) slot[f] = to;
+        }
+        HIP_TRY(hipStreamSynchronize(S->stream));        // queued work may still use what is freed here
+        HIP_TRY(hipFree(heat_chunk));
+        heat_chunk = nullptr;
+        for (int k = 0; k < NHEAT; ++k) arr[NPOOL + k] = nullptr;
+        npool = NPOOL;
+        if (heat_ws) HIP_TRY(hipFree(heat_ws));
+        heat_ws = nullptr;
+        return FS_OK;
+    }
+    // fs_heat_params with values the entry has checked: the arrays and the log first, then the values
+    int heat_config(const double* par) override
+    {
+        const int mode = (int)par[fs::HP_MODE], log = mode ? (int)par[fs::HP_LOG] : 0;
+        if (mode != 0 && S->comm.active()) return fail(FS_EINVAL, "fs_heat_params: heat needs a single GPU handle (it is not exchanged between slabs)");
+        int rc = mode ? heat_alloc() : heat_free();
+        if (rc) return rc;
+        if (log != heat_ring.at.cap) {
+            if (log > 0 && !heat_ws) HIP_TRY(hipMalloc((void**)&heat_ws, fs::heat_workspace_doubles(g) * sizeof(double)));
+            HIP_TRY(heat_ring.setup(S->stream, 0, log, (size_t)fs::HEAT_COLS * sizeof(double)));
+        }
+        for (int k = 0; k < fs::HEAT_PARAMS; ++k) S->heat[k] = par[k];
+        return FS_OK;
+    }
+    fs::HeatPass heat_pass_params() const
+    {
+        fs::HeatPass p;
+        p.beta = S->heat[fs::HP_BETA];
+        p.alpha = S->heat[fs::HP_ALPHA];
+        p.dt = (double)S->dt;
+        p.inlet = S->heat[fs::HP_INLET];
+        p.wall_t = S->heat[fs::HP_WALL_T];
+        p.up = (int)S->heat[fs::HP_UP];
+        p.wall = (int)S->heat[fs::HP_WALL];
+        for (int k = 0; k < 6; ++k) p.box[k] = (int)S->heat[fs::HP_X0 + k];
+        return p;
+    }
+    int heat_need(const char* who)
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "%s: heat needs a single GPU handle (it is not exchanged between slabs)", who);
+        if (!heat_on()) return fail(FS_EINVAL, "%s: heat is off (fs_heat_params, mode 1 or 2)", who);
+        return FS_OK;
+    }
+    // Pass A: inlet and wall temperatures, buoyancy on the component along `up`, in place.  One launch.
+    int heat_apply_pass(const char* who)
+    {
+        int rc = heat_need(who);
+        if (rc) return rc;
+        if ((rc = ensure_flags())) return rc;
+        const fs::HeatPass p = heat_pass_params();
+        const bool force = p.beta != 0.0 || p.alpha != 0.0;
+        const int up = FS_VX + (p.up >> 1);
+        if ((rc = unalias(F_THETA))) return rc;
+        if (force && (rc = unalias(up))) return rc;
+        {
+            ScopedSpan sp(S, FAM_HEAT);
+            fs::launch_heat_apply<T>(S->stream, g, p, arr[slot[F_THETA]], force ? arr[slot[up]] : nullptr,
+                                     force ? arr[slot[FS_DENS]] : nullptr, flags);
+        }
+        ++S->n_heat_apply;
+        return FS_OK;
+    }
+    // Pass B: the reference's diffusion and advection of a scalar, on the temperature (no new kernel)
+    int heat_transport_pass(const char* who)
+    {
+        int rc = heat_need(who);
+        if (rc) return rc;
+        if ((rc = ensure_flags())) return rc;
+        // dt * kappa * width * height * depth, left to right like diffusion_a()
+        const T a = (T)S->dt * (T)S->heat[fs::HP_KAPPA] * (T)S->W * (T)S->H * (T)S->D;
+        const T c = (T)1 + (T)6 * a;
+        if (S->solver == FS_SOLVER_GS_LEX || S->acc <= 0) {
+            if ((rc = unalias(F_THETA)) || (rc = unalias(F_THETA_PREV))) return rc;
+            ScopedSpan sp(S, FAM_MISC);
+            fs::launch_copy<T>(S->stream, g, arr[slot[F_THETA]], arr[slot[F_THETA_PREV]]);
+        } else {
+            slot[F_THETA_PREV] = slot[F_THETA];          // Jacobi never writes its input: the snapshot is an alias
+        }
+        int res;
+        if ((rc = solve(0, slot[F_THETA], slot[F_THETA_PREV], a, c, S->acc, &res))) return rc;
+        adopt(F_THETA_PREV, res);                        // the solved array: what the advection carries
+        if ((rc = advect(0, F_THETA, F_THETA_PREV))) return rc;
+        ++S->n_heat_transport;
+        return FS_OK;
+    }
+    int heat_apply() override
+    {
+        if (!in_step) vzmax_prev = -1.0;
+        return heat_apply_pass("fs_heat_apply");
+    }
+    int heat_transport() override { return heat_transport_pass("fs_heat_transport"); }
+
+    // Pass C: the heat budget of the state as it is now into `result` (a ring slot or the workspace's result slot)
+    void heat_budget_launch(double* result)
+    {
+        ScopedSpan sp(S, FAM_HEAT, 3);
+        fs::launch_heat_budget<T>(S->stream, g, heat_pass_params(), arr[slot[F_THETA]], arr[slot[FS_VX]], flags, heat_ws, result);
+    }
+    int heat_budget(double* out, double* per_plane) override
+    {
+        int rc = heat_need("fs_heat_budget");
+        if (rc) return rc;
+        if ((rc = ensure_flags())) return rc;
+        const size_t total = fs::heat_workspace_doubles(g), planes = fs::heat_planes_offset(g);
+        if (!heat_ws) HIP_TRY(hipMalloc((void**)&heat_ws, total * sizeof(double)));
+        heat_budget_launch(heat_ws + (total - fs::HEAT_COLS));
+        std::vector<double> host(total - planes);        // the plane records, then the result
+        HIP_TRY(hipMemcpyAsync(host.data(), heat_ws + planes, host.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipStreamSynchronize(S->stream));
+        memcpy(out, host.data() + (size_t)g.D * fs::HEAT_COLS, fs::HEAT_COLS * sizeof(double));
+        if (per_plane) memcpy(per_plane, host.data(), (size_t)g.D * fs::HEAT_COLS * sizeof(double));
+        return FS_OK;
+    }
+    int heat_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
+    {
+        if (S->comm.active()) return fail(FS_EINVAL, "fs_heat_log: heat needs a single GPU handle");
+        const long n = heat_ring.at.retained();
+        int rc = heat_ring.fetch_begin({"fs_heat_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
+        if (rc != LogRing::GO_ON) return rc;
+        std::vector<double> mine((size_t)n * fs::HEAT_COLS);
+        HIP_TRY(heat_ring.fetch_copy(S->stream, mine.data()));
+        for (long i = 0; i < n; ++i) {
+            double* o = rows + (size_t)i * FS_HEAT_LOG_COLS;
+            o[0] = (double)heat_ring.at.step_of(i);
+            memcpy(o + 1, &mine[(size_t)i * fs::HEAT_COLS], fs::HEAT_COLS * sizeof(double));
+        }
+        heat_ring.fetch_end();
+        return FS_OK;
+    }
+    int heat_get(void* dst, size_t n, int elem) override
+    {
+        int rc = heat_need("fs_heat_get");
+        if (rc) return rc;
+        return get_field(F_THETA, dst, n, elem);
+    }
+    int heat_set(const void* src, size_t n, int elem) override
+    {
+        int rc = heat_need("fs_heat_set");
+        if (rc) return rc;
+        return set_field(F_THETA, src, n, elem);
+    }
+
     // ---- turbulent inflow (inflow.h; beyond the reference) -----------------------------------------------
     // the parameters as they stand; FS_EINVAL where they do not make a finite amplitude or step t is out of range
     int inflow_params(const char* who, long t, fs::InflowParams* p) const
@@ -1825,6 +2032,9 @@ struct Engine : EngineBase {
         res_ran_now = 0;
         // "vorticity_confinement": the pass comes before everything the reference's step does
         if (S->confinement > 0.0 && (rc = confine_pass("fs_step", S->confinement))) return rc;
+        // heat, mode 2: inlet and wall temperatures and the buoyancy force come next, still before the reference's step
+        const bool heat_step = S->heat_mode() == 2;
+        if (heat_step && (rc = heat_apply_pass("fs_step"))) return rc;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
@@ -1901,11 +2111,17 @@ struct Engine : EngineBase {
         }
         if ((rc = advect(0, FS_DENS, FS_BUFFER))) return rc;   // :136
         slack_check();
+        if (heat_step && (rc = heat_transport_pass("fs_step"))) return rc;   // the temperature is diffused and carried last
         S->step_no++;
         S->steps_total++;
         if (force_ring.on()) force_ring.at.commit(S->steps_total);
         if (body_ring.on()) body_ring.at.commit(S->steps_total);
         if (res_ring.on()) res_ring.at.commit(S->steps_total, res_ran_now);
+        // the heat log: the budget of the state the transport left (three launches, no host synchronisation, the step's own stream)
+        if (heat_step && heat_ring.on()) {
+            heat_budget_launch((double*)heat_ring.slot(heat_ring.at.next()));
+            heat_ring.at.commit(S->steps_total);
+        }
         // "flow_stats": the state as :136 left it is a sample (no host synchronisation, the step's own stream)
         if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
             (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
@@ -2282,8 +2498,11 @@ struct Engine : EngineBase {
             int rc = vortex_compute("fs_isosurface", source & (FS_ISO_VORTEX - 1));
             if (rc) return rc;
             field = vort;
+        } else if (source == FS_SOURCE_HEAT) {
+            if (!heat_on()) return fail(FS_EINVAL, "fs_isosurface: FS_SOURCE_HEAT while heat is off (fs_heat_params, mode 1 or 2)");
+            field = arr[slot[F_THETA]];
         } else {
-            return fail(FS_EINVAL, "fs_isosurface: unknown source %d (a field selector, or FS_ISO_VORTEX | FS_VORTEX_*)", source);
+            return fail(FS_EINVAL, "fs_isosurface: unknown source %d (a field selector, FS_SOURCE_HEAT, or FS_ISO_VORTEX | FS_VORTEX_*)", source);
         }
         return surface_into(field, (T)level, S->iso_verts, S->iso_tris, S->iso_valid);
     }
@@ -2602,8 +2821,11 @@ struct Engine : EngineBase {
                 fs::launch_flow_stats_finalize(S->stream, g, stat_acc, sel & ~FS_STAT_RAW, (sel & FS_STAT_RAW) != 0, S->flow_stats_n,
                                                false, false, (double*)dense);
             stat = (const double*)dense + fs::LEAD;
+        } else if (source == FS_SOURCE_HEAT) {
+            if (!heat_on()) return fail(FS_EINVAL, "%s: FS_SOURCE_HEAT while heat is off (fs_heat_params, mode 1 or 2)", who);
+            field = arr[slot[F_THETA]];
         } else {
-            return fail(FS_EINVAL, "%s: unknown source %d (a field selector, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", who, source);
+            return fail(FS_EINVAL, "%s: unknown source %d (a field selector, FS_SOURCE_HEAT, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", who, source);
         }
         return FS_OK;
     }
@@ -3750,6 +3972,7 @@ fs_sim* fs_create(int w, int h, int d, int iter, int speed, float dt, float diff
     fs_sim* s = new fs_sim;
     s->W = w; s->H = h; s->D = d; s->iter = iter; s->speed = speed; s->acc = acc;
     s->dt = dt; s->diff = diff; s->visc = visc;
+    s->heat[fs::HP_X1] = w; s->heat[fs::HP_Y1] = h; s->heat[fs::HP_Z1] = d;   // the wall box: the whole domain
     if (hipGetDevice(&s->device) != hipSuccess) s->device = 0;
     e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -4080,6 +4303,9 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "inflow") *out = s->inflow ? 1 : 0;
     else if (n == "inflow_eddies") *out = s->inflow_n;
     else if (n == "inflow_passes") *out = (int)std::min<long>(s->n_inflow, 2147483647L);   // inlet planes the steps wrote through the inflow generator
+    else if (n == "heat_mode") *out = s->heat_mode();                     // 0 off, 1 manual, 2 in fs_step (fs_heat_params)
+    else if (n == "heat_applies") *out = (int)std::min<long>(s->n_heat_apply, 2147483647L);       // passes A done, in steps and by fs_heat_apply
+    else if (n == "heat_transports") *out = (int)std::min<long>(s->n_heat_transport, 2147483647L);   // passes B done, in steps and by fs_heat_transport
     else if (n == "confinement_passes") *out = (int)std::min<long>(s->n_confine, 2147483647L);   // confinement passes done, in steps and by fs_confine_vorticity
     else if (n == "monitor_log") *out = s->monitor_log;
     else if (n == "monitor_every") *out = (int)s->monitor_every;
@@ -4308,7 +4534,7 @@ int fs_get_timing(fs_sim* s, const char* family, double* total_ms, long* launche
     hipSetDevice(s->device);
     s->resolve_spans();
     for (int f = 0; f < FAM_COUNT; ++f)
-        if (strcmp(family, kFamilyNames[f]) == 0) {
+        if (strcmp(family, family_name(f)) == 0) {
             if (total_ms) *total_ms = s->fam_ms[f];
             if (launches) *launches = s->fam_launches[f];
             return FS_OK;
@@ -4500,6 +4726,63 @@ int fs_confine_vorticity(fs_sim* s, double epsilon)
 {
     ENGINE_OR_RETURN(s);
     return s->eng->confine_vorticity(epsilon);
+}
+int fs_heat_params(fs_sim* s, const double* par, int n)
+{
+    ENGINE_OR_RETURN(s);
+    if (!par) return fail(FS_EINVAL, "fs_heat_params: null argument");
+    if (n != FS_HEAT_PARAMS) return fail(FS_EINVAL, "fs_heat_params: n = %d, the call takes FS_HEAT_PARAMS = %d numbers", n, FS_HEAT_PARAMS);
+    static const char* const name[FS_HEAT_PARAMS] = { "mode", "kappa", "beta", "alpha", "up", "inlet temperature", "wall mode",
+                                                      "wall temperature", "box x0", "box x1", "box y0", "box y1", "box z0", "box z1", "log" };
+    for (int k = 0; k < FS_HEAT_PARAMS; ++k)
+        if (!std::isfinite(par[k])) return fail(FS_EINVAL, "fs_heat_params: par[%d] (%s) is not finite", k, name[k]);
+    auto whole = [&](int k, double lo, double hi) { return par[k] >= lo && par[k] <= hi && par[k] == std::floor(par[k]); };
+    if (!whole(fs::HP_MODE, 0, 2)) return fail(FS_EINVAL, "fs_heat_params: par[0] (mode) is 0 (off), 1 (manual) or 2 (in fs_step)");
+    for (int k : { fs::HP_KAPPA, fs::HP_BETA, fs::HP_ALPHA })
+        if (!(par[k] >= 0.0)) return fail(FS_EINVAL, "fs_heat_params: par[%d] (%s) must be >= 0", k, name[k]);
+    if (!whole(fs::HP_UP, 0, 5)) return fail(FS_EINVAL, "fs_heat_params: par[4] (up) is 0..5 = +x, -x, +y, -y, +z, -z");
+    if (!whole(fs::HP_WALL, 0, 1)) return fail(FS_EINVAL, "fs_heat_params: par[6] (wall mode) is 0 or 1");
+    const int ext[3] = { s->W, s->H, s->D };
+    for (int a = 0; a < 3; ++a) {
+        const int lo = fs::HP_X0 + 2 * a, hi = lo + 1;
+        if (!whole(lo, 1, ext[a]) || !whole(hi, 1, ext[a]) || par[lo] > par[hi])
+            return fail(FS_EINVAL, "fs_heat_params: par[%d], par[%d] (%s, %s) must be whole cells with 1 <= lo <= hi <= %d", lo, hi,
+                        name[lo], name[hi], ext[a]);
+    }
+    if (!whole(fs::HP_LOG, 0, 1048576)) return fail(FS_EINVAL, "fs_heat_params: par[14] (log) is a record count 0 .. 2^20");
+    return s->eng->heat_config(par);
+}
+int fs_heat_params_get(fs_sim* s, double* par, int n)
+{
+    if (!s || !par) return fail(FS_EINVAL, "fs_heat_params_get: null argument");
+    if (n != FS_HEAT_PARAMS) return fail(FS_EINVAL, "fs_heat_params_get: n = %d, the call fills FS_HEAT_PARAMS = %d numbers", n, FS_HEAT_PARAMS);
+    for (int k = 0; k < FS_HEAT_PARAMS; ++k) par[k] = s->heat[k];
+    return FS_OK;
+}
+int fs_heat_apply(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->heat_apply(); }
+int fs_heat_transport(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->heat_transport(); }
+int fs_heat_budget(fs_sim* s, double out[FS_HEAT_COLS], double* per_plane)
+{
+    ENGINE_OR_RETURN(s);
+    if (!out) return fail(FS_EINVAL, "fs_heat_budget: null argument");
+    return s->eng->heat_budget(out, per_plane);
+}
+int fs_heat_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return s->eng->heat_log_fetch(rows, max_rows, n_rows, n_dropped);
+}
+int fs_heat_get(fs_sim* s, void* dst, size_t n_elems, int elem_size)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dst) return fail(FS_EINVAL, "fs_heat_get: null buffer");
+    return s->eng->heat_get(dst, n_elems, elem_size);
+}
+int fs_heat_set(fs_sim* s, const void* src, size_t n_elems, int elem_size)
+{
+    ENGINE_OR_RETURN(s);
+    if (!src) return fail(FS_EINVAL, "fs_heat_set: null buffer");
+    return s->eng->heat_set(src, n_elems, elem_size);
 }
 int fs_inflow_profile(fs_sim* s, const double* u, const double* rms, size_t n)
 {

@@ -239,4 +239,22 @@ template <class T>
 void launch_inflow_plane(hipStream_t st, const GridDesc& g, const InflowParams& p, const InflowEntry* tab, double gust, double speed,
                          const double* mean, const double* scale, T* vx, T* vy, T* vz, double* out);
 
+// Heat and buoyancy (heat.h has the arithmetic, heat.hip the kernels).  launch_heat_apply: one streaming pass, in place, over
+// the temperature `theta` and -- only where p.beta != 0 or p.alpha != 0 -- the velocity component `vup` along p.up, which
+// reads the density `dens`; otherwise vup and dens are not touched and may be null.  Both arrays come out as set_bounds(0, .)
+// and set_bounds(1 + p.up / 2, .) would leave them: ghost faces from the un-zeroed new values, solid cells (for the velocity
+// also their fluid neighbours) zeroed; the twelve box edges are not written or take +0.0.
+// launch_heat_budget: the heat budget of `theta` and the x velocity `u` in three launches -- the COLUMN records, the PLANE
+// records, the WHOLE record into `result` (HEAT_COLS doubles on the device) -- through the workspace `ws`
+// (heat_workspace_doubles, whose PLANE records start at heat_planes_offset); no atomics, every sum in its written order.
+// Single GPU (g.zh == 1, both z walls physical).
+struct HeatPass;
+template <class T>
+void launch_heat_apply(hipStream_t st, const GridDesc& g, const HeatPass& p, T* theta, T* vup, const T* dens, const uint8_t* flags);
+size_t heat_workspace_doubles(const GridDesc& g);
+size_t heat_planes_offset(const GridDesc& g);
+template <class T>
+void launch_heat_budget(hipStream_t st, const GridDesc& g, const HeatPass& p, const T* theta, const T* u, const uint8_t* flags,
+                        double* ws, double* result);
+
 }  // namespace fs

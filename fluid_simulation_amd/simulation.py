@@ -525,6 +525,88 @@ class Simulation:
         boundary handling of set_bounds.  The option vorticity_confinement=eps makes every step begin with such a pass."""
         check(self._L.fs_confine_vorticity(self._h, float(eps)))
 
+    # -- heat and buoyancy (include/fluidsim.h, "heat and buoyancy"; single-GPU handles) --------------------------------------
+    def set_heat(self, kappa=0.0, beta=0.0, alpha=0.0, up="+y", inlet=0.0, wall=None, box=None, log=0, in_step=True):
+        """Switches heat on (fs_heat_params): a temperature theta, the excess over ambient, with thermal diffusivity `kappa`,
+        buoyancy `beta` per unit theta and weight `alpha` per unit smoke density along `up` ("+x" .. "-z" or 0..5), `inlet`
+        forced on the plane x = 1, and -- with `wall` a temperature -- the fluid cells beside a solid inside `box` =
+        (x0, x1, y0, y1, z0, z1) in cells (default: the whole domain) held at it.  in_step=True makes every step apply and
+        transport it (mode 2), False leaves that to heat_apply() / heat_transport() (mode 1).  log=N keeps the heat budget of
+        the last N steps (heat_log()).  theta starts at 0 and survives a change of the parameters."""
+        par = np.zeros(_lib.HEAT_PARAMS, dtype=np.float64)
+        par[0] = 2 if in_step else 1
+        par[1:4] = float(kappa), float(beta), float(alpha)
+        par[4] = _lib.HEAT_UP[up] if isinstance(up, str) else int(up)
+        par[5] = float(inlet)
+        par[6] = 0 if wall is None else 1
+        par[7] = 0.0 if wall is None else float(wall)
+        par[8:14] = (1, self.width, 1, self.height, 1, self.depth) if box is None else tuple(box)
+        par[14] = int(log)
+        check(self._L.fs_heat_params(self._h, par.ctypes.data, par.size))
+
+    def set_heat_params(self, par):
+        """fs_heat_params with the HEAT_PARAMS numbers as they are (heat_params() returns them in this form)."""
+        par = np.ascontiguousarray(par, dtype=np.float64).reshape(-1)
+        check(self._L.fs_heat_params(self._h, par.ctypes.data, par.size))
+
+    def heat_off(self):
+        """Switches heat off and frees theta; the other parameters stay as they were."""
+        par = self.heat_params()
+        par[0] = 0
+        check(self._L.fs_heat_params(self._h, par.ctypes.data, par.size))
+
+    def heat_params(self):
+        """The HEAT_PARAMS numbers in force (fs_heat_params_get)."""
+        par = np.zeros(_lib.HEAT_PARAMS, dtype=np.float64)
+        check(self._L.fs_heat_params_get(self._h, par.ctypes.data, par.size))
+        return par
+
+    def temperature(self, dtype=None):
+        """theta, shaped like get() (fs_heat_get)."""
+        dtype = np.dtype(dtype or self.dtype)
+        n = self._L.fs_padded_size(self._h)
+        out = np.empty(n, dtype=dtype)
+        check(self._L.fs_heat_get(self._h, out.ctypes.data_as(C.c_void_p), n, dtype.itemsize))
+        return out.reshape(self.shape)
+
+    def set_temperature(self, arr):
+        """Overwrites theta with a padded array, ghosts included; no bounds are applied (fs_heat_set)."""
+        a = np.ascontiguousarray(arr)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(self.dtype)
+        a = a.reshape(-1)
+        check(self._L.fs_heat_set(self._h, a.ctypes.data_as(C.c_void_p), a.size, a.dtype.itemsize))
+
+    def heat_apply(self):
+        """Pass A now: inlet and wall temperatures, then the buoyancy force on the velocity component along `up`."""
+        check(self._L.fs_heat_apply(self._h))
+
+    def heat_transport(self):
+        """Pass B now: theta is diffused with `kappa` and carried by the velocities as they are."""
+        check(self._L.fs_heat_transport(self._h))
+
+    def heat_budget(self, per_plane=False):
+        """The heat budget of the state as it is now (fs_heat_budget; changes nothing): a dict of HEAT_NAMES -> float over the
+        cells that are not solid, "values" the same HEAT_COLS numbers as an array; per_plane=True adds "per_plane"
+        (depth, HEAT_COLS).  Every sum has one written order (include/fluidsim.h)."""
+        out = np.zeros(_lib.HEAT_COLS, dtype=np.float64)
+        pp = np.zeros((self.depth, _lib.HEAT_COLS), dtype=np.float64) if per_plane else None
+        check(self._L.fs_heat_budget(self._h, out.ctypes.data, None if pp is None else pp.ctypes.data))
+        r = {name: float(out[k]) for k, name in enumerate(_lib.HEAT_NAMES)}
+        r["values"] = out
+        if pp is not None:
+            r["per_plane"] = pp
+        return r
+
+    def heat_log(self, with_dropped=False):
+        """Drains the heat log (set_heat(log=N); fs_heat_log): one row per retained record, oldest first, (n, HEAT_LOG_COLS)
+        float64 -- step, then the budget.  with_dropped=True returns (rows, records the ring overwrote since the last drain)."""
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_heat_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        rows = np.zeros((n.value, _lib.HEAT_LOG_COLS), dtype=np.float64)
+        check(self._L.fs_heat_log(self._h, rows.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        return (rows, dropped.value) if with_dropped else rows
+
     def set_inflow(self, profile=None, rms=None, gust=None, eddies=0, sigma=4.0, u_rms=0.0, convect="auto", seed=1):
         """Configures the inflow generator and turns it on (include/fluidsim.h, "turbulent inflow"; single-GPU handles): every
         step then writes the x = 1 face as v_x = g(t) * U + r * u'_x, v_y = r * u'_y, v_z = r * u'_z.  `profile` (U) and

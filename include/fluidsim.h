@@ -618,6 +618,75 @@ int fs_isosurface_fetch(fs_sim* s, float* vertices, int* triangles);
  */
 int fs_confine_vorticity(fs_sim* s, double epsilon);
 
+/* ---- heat and buoyancy (beyond the reference: it transports one passive scalar and has no body force) ----
+ *
+ * A temperature theta, carried and diffused like the reference's density, heated at the inlet and at the walls of bodies, and
+ * the second force of Fedkiw, Stam and Jensen (2001): f = (-alpha * q + beta * theta) * up, q the smoke density.  theta is
+ * the EXCESS over ambient: 0 means ambient, so the boundary rule b = 0 (solid cells zero, ghost faces copied) reads "bodies at
+ * ambient, adiabatic box walls".  Default off: a handle that never switches heat on allocates and launches nothing for it.
+ * Single GPU only: with a communicator (the FSNULL one included) every entry below, and fs_step with heat on, is FS_EINVAL.
+ * Both precisions, every solver mode (solver=mg relaxes the temperature system as it relaxes the other diffusion systems).
+ *
+ * fs_heat_params: all parameters in one atomic call, n == FS_HEAT_PARAMS; a bad n or entry is FS_EINVAL with a message naming
+ * the first bad entry, and nothing changes.  Every entry must be finite.
+ *    par[0]  mode: 0 = off (theta is freed), 1 = manual (theta exists, the passes run only when called), 2 = in fs_step.
+ *            Switching between 1 and 2 keeps theta; switching on allocates theta = 0.
+ *    par[1]  kappa >= 0, the thermal diffusivity;  par[2] beta >= 0, buoyancy per unit theta;  par[3] alpha >= 0, weight per
+ *            unit smoke density;  par[4] up: 0..5 = +x, -x, +y, -y, +z, -z.
+ *    par[5]  theta_in, forced on the inlet plane x = 1;  par[6] wall mode: 0 = bodies are not heated, 1 = HELD cells take
+ *            par[7] theta_w;  par[8..13] a box x0, x1, y0, y1, z0, z1 in cells, 1 <= lo <= hi <= extent: only cells inside it
+ *            are held (how one body of several is heated).
+ *    par[14] records the per-step heat log keeps, 0 (off) .. 2^20.  A changed count clears the log.
+ * fs_heat_params_get returns the values in force (before the first call: mode 0, up = +y, the box = the whole domain).
+ *
+ * A HELD cell: wall mode on, the cell is interior with obs != 1, has an interior 6-neighbour with obs == 1 (its flag byte
+ * says so) and lies inside the box.
+ *
+ * PASS A, fs_heat_apply: one streaming HIP kernel, in place, per interior cell (x, y, z), solid or not; every intermediate is
+ * fp64, every operation rounded once, in this order, without contraction; T is the handle's precision:
+ *    1. t = theta;  if x == 1, t = (T)theta_in;  if the cell is HELD, t = (T)theta_w  (the wall wins over the inlet).
+ *    2. only if beta != 0 or alpha != 0 (otherwise no velocity and no density is read or written, so -0.0 stays -0.0):
+ *         b = beta * (double)t;  w = alpha * (double)q;  d = b - w;  f = (double)dt * d;
+ *         v_up' = (T)((double)v_up + f) for up = +axis, (T)((double)v_up - f) for up = -axis;  the other two components stay.
+ *    3. theta is left exactly as fs_set_bounds(0, .) would leave the array of t, v_up exactly as fs_set_bounds(1 + up / 2, .)
+ *       would leave the array of v_up': ghost faces from the un-zeroed values, then cells with obs == 1 zeroed (for the
+ *       velocity also their fluid neighbours).  The twelve box edges are not written or take +0.0.
+ * PASS B, fs_heat_transport: no new arithmetic.  a = (T)dt * (T)kappa * (T)w * (T)h * (T)d left to right, c = 1 + 6a; the
+ * reference's linear solver (0, theta, snapshot of theta, a, c) with the handle's acc and solver, then its advection (b = 0)
+ * of the solved array by the velocities as they are.  The same bits as fs_linear_solver + fs_advect on a field.  It is not
+ * one of the FS_RESIDUAL_LOG_SOLVES logged solves.
+ * PASS C, fs_heat_budget: PLANE records of FS_HEAT_COLS = 9 doubles for z = 1..d into per_plane (may be NULL) and their
+ * combination over increasing z into out.  Over the cells of plane z with obs != 1, theta widened to fp64:
+ *    0 cells   1 sum theta   2 sum theta * theta   3 max theta (from -Inf, "if (a > m) m = a")   4 min theta (from +Inf)
+ *    5 HELD cells   6 the conductive loss: over the HELD cells, s = 0, then s = s + (theta_c - theta_n) for each neighbour n in
+ *    the order x-, x+, y-, y+, z-, z+ that is interior, has obs == 0 and is not HELD; the cell adds s
+ *    7 outflow: sum of (double)v_x * theta over the column x = w   8 inflow: the same over x = 1.
+ * ORDER: a COLUMN (z, x) adds its cells in increasing y from 0; a PLANE combines the columns' values in increasing x, the
+ * WHOLE record the planes' in increasing z (the flow monitor's order).  Times kappa and the cell size, column 6 is the heat
+ * flux off the heated walls: the numerator of a Nusselt number.
+ * fs_heat_log: with par[14] > 0 every fs_step in mode 2 ends with a record { step, the 9 numbers of out } on a device ring,
+ * written without a host synchronisation; the fetch has the shape of fs_monitor_log and drains the log.
+ *
+ * fs_step in mode 2: confinement (if on), pass A, the reference's step exactly as without heat, pass B, the log record, the
+ * samplers.  It is bit-identical to fs_heat_apply, fs_step, fs_heat_transport on a mode-1 handle.
+ * fs_heat_get / fs_heat_set: theta as a dense padded array under fs_get_field's rules for n_elems and elem_size; no bounds
+ * are applied on set.  FS_SOURCE_HEAT is theta as a source of fs_sample, fs_tracer_sample, the image and volume entries and
+ * fs_isosurface (FS_EINVAL while heat is off).  Timing family "heat"; fs_get_int "heat_mode", "heat_applies",
+ * "heat_transports".
+ */
+#define FS_HEAT_PARAMS 15
+#define FS_HEAT_COLS 9
+#define FS_HEAT_LOG_COLS 10
+#define FS_SOURCE_HEAT 8192   /* the temperature as a source of fs_sample, the image and volume entries and fs_isosurface */
+int fs_heat_params(fs_sim* s, const double* par, int n);
+int fs_heat_params_get(fs_sim* s, double* par, int n);
+int fs_heat_apply(fs_sim* s);
+int fs_heat_transport(fs_sim* s);
+int fs_heat_budget(fs_sim* s, double out[FS_HEAT_COLS], double* per_plane);
+int fs_heat_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+int fs_heat_get(fs_sim* s, void* dst, size_t n_elems, int elem_size);
+int fs_heat_set(fs_sim* s, const void* src, size_t n_elems, int elem_size);
+
 /* ---- turbulent inflow (beyond the reference: its only inflow is (speed, 0, 0) on the x = 1 face, simulation.cpp:103-105) ----
  *
  * An inflow generator for boundary layers, gusts and free-stream turbulence.  With option "inflow" = "on" fs_step writes, where

@@ -80,6 +80,15 @@
 //                  (cells per step, or auto), --inflow-seed K: the synthetic eddies (options "inflow_eddies", "inflow_sigma",
 //                  "inflow_rms", "inflow_convect", "inflow_seed").  Any of these flags turns the generator on.  The step number
 //                  the eddies are taken at counts this run's steps: --resume restores the fields, not the count.  Single GPU.
+//   --heat KAPPA,BETA,ALPHA  heat and buoyancy (fs_heat_params, mode 2; include/fluidsim.h, "heat and buoyancy"): a temperature
+//                  with thermal diffusivity KAPPA, buoyancy BETA per unit temperature and weight ALPHA per unit smoke density,
+//                  applied and transported by every step.  --heat-up AXIS: +x, -x, +y (default), -y, +z or -z.  --heat-inlet T:
+//                  the temperature forced on the inlet plane.  --heat-wall T[,x0,x1,y0,y1,z0,z1]: the fluid cells beside a body
+//                  are held at T, with a box in cells only those inside it.  --heat-log FILE.csv: the heat budget after every
+//                  step (fs_heat_log's columns, numbers as %.17g).  --heat-dump FILE: the temperature is appended to FILE as
+//                  float32 in the frames' layout whenever a frame is dumped (the run then goes step by step, as for
+//                  --images).  The other --heat-* flags need --heat.  A --resume run starts the temperature from zero: the
+//                  dumped frames do not hold it.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -269,6 +278,39 @@ int write_monitor(fs_sim* sim, const char* path, int width, int height, int dept
     const bool ok = fclose(fp) == 0;
     if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
     return ok ? 0 : 1;
+}
+
+// the heat log of the run -> CSV (the columns of Simulation.heat_log() in the Python package)
+int write_heat_log(fs_sim* sim, const char* path)
+{
+    long n = 0, dropped = 0;
+    if (fs_heat_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * FS_HEAT_LOG_COLS);
+    if (fs_heat_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    if (dropped) fprintf(stderr, "simulation.out: %ld heat records were overwritten before they were written\n", dropped);
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step,cells,sum,sum_sq,max,min,held,loss,outflow,inflow\n");
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * FS_HEAT_LOG_COLS];
+        fprintf(fp, "%ld", (long)r[0]);
+        for (int k = 1; k < FS_HEAT_LOG_COLS; ++k) fprintf(fp, ",%.17g", r[k]);
+        fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
+// the temperature as one more float32 frame at the end of `path`
+int append_heat_frame(fs_sim* sim, const char* path)
+{
+    std::vector<float> frame(fs_padded_size(sim));
+    if (fs_heat_get(sim, frame.data(), frame.size(), 4)) return 1;
+    FILE* fp = fopen(path, "ab");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    const bool ok = fwrite(frame.data(), sizeof(float), frame.size(), fp) == frame.size();
+    return (fclose(fp) == 0 && ok) ? 0 : 1;
 }
 
 // the probe cells of --probes: `x y z` per line, `#` comments
@@ -507,6 +549,9 @@ int main(int argc, char** argv)
     std::string monitor_path, inflow_profile_path, inflow_gust_path;
     bool inflow = false;
     long monitor_every = 1;
+    bool heat = false, heat_other = false;
+    double heat_par[FS_HEAT_PARAMS] = { 2, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };   // mode 2, up = +y; a box of zeros = the whole domain
+    std::string heat_log_path, heat_dump_path;
     int dump_every = 1;
     std::vector<int> view_spec;
     std::vector<double> view_range;
@@ -567,6 +612,25 @@ int main(int argc, char** argv)
         if (key == "inflow-rms") { options.push_back({ "inflow_rms", val }); inflow = true; return true; }
         if (key == "inflow-convect") { options.push_back({ "inflow_convect", val }); inflow = true; return true; }
         if (key == "inflow-seed") { options.push_back({ "inflow_seed", val }); inflow = true; return true; }
+        if (key == "heat") { heat = true; return sscanf(val, "%lf,%lf,%lf", &heat_par[1], &heat_par[2], &heat_par[3]) == 3; }
+        if (key == "heat-up") {
+            static const char* const axes[6] = { "+x", "-x", "+y", "-y", "+z", "-z" };
+            heat_other = true;
+            for (int k = 0; k < 6; ++k)
+                if (strcmp(val, axes[k]) == 0) { heat_par[4] = k; return true; }
+            return false;
+        }
+        if (key == "heat-inlet") { heat_other = true; return sscanf(val, "%lf", &heat_par[5]) == 1; }
+        if (key == "heat-wall") {
+            heat_other = true;
+            heat_par[6] = 1;
+            const int got = sscanf(val, "%lf,%lf,%lf,%lf,%lf,%lf,%lf", &heat_par[7], &heat_par[8], &heat_par[9], &heat_par[10],
+                                   &heat_par[11], &heat_par[12], &heat_par[13]);
+            if (got == 1) heat_par[8] = 0;
+            return got == 1 || got == 7;
+        }
+        if (key == "heat-log") { heat_other = true; heat_log_path = val; return true; }
+        if (key == "heat-dump") { heat_other = true; heat_dump_path = val; return true; }
         if (key == "monitor-every") { monitor_every = atol(val); return monitor_every >= 1; }
         if (key == "monitor-stations") { options.push_back({ "monitor_stations", val }); return true; }
         return false;
@@ -576,7 +640,8 @@ int main(int argc, char** argv)
                                         "mean-every", "vortex", "probes", "probe-log", "body-forces", "moment-origin", "images", "image-every",
                                         "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
                                         "volume-range", "volume-opacity", "volume-every", "confinement", "monitor", "monitor-every", "monitor-stations",
-                                        "inflow-profile", "inflow-gust", "inflow-eddies", "inflow-sigma", "inflow-rms", "inflow-convect", "inflow-seed" };
+                                        "inflow-profile", "inflow-gust", "inflow-eddies", "inflow-sigma", "inflow-rms", "inflow-convect", "inflow-seed",
+                                        "heat", "heat-up", "heat-inlet", "heat-wall", "heat-log", "heat-dump" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -602,6 +667,10 @@ int main(int argc, char** argv)
     }
     if (tracer_every_given && tracer_emitters_path.empty()) {
         fprintf(stderr, "simulation.out: --tracer-every is the emitters' release period and needs --tracer-emitters\n");
+        return 2;
+    }
+    if (heat_other && !heat) {
+        fprintf(stderr, "simulation.out: --heat-up, --heat-inlet, --heat-wall, --heat-log and --heat-dump need --heat KAPPA,BETA,ALPHA\n");
         return 2;
     }
     if (!stl_given) {
@@ -653,7 +722,16 @@ int main(int argc, char** argv)
         if (read_points(tracer_emitters_path.c_str(), pts)) return 2;
         if (fs_tracer_emitters(sim, pts.data(), (long)(pts.size() / 3), tracer_every)) return die("fs_tracer_emitters");
     }
-    bool stepwise = false;                               // --images, --volume: the run's frames do not fit the ring
+    if (heat) {
+        if (heat_par[8] == 0) {                          // no box given: the whole domain
+            const double whole[6] = { 1, (double)width, 1, (double)height, 1, (double)depth };
+            for (int k = 0; k < 6; ++k) heat_par[8 + k] = whole[k];
+        }
+        if (!heat_log_path.empty()) heat_par[14] = (double)std::min(1048576L, (long)std::max(iter, 0));
+        if (fs_heat_params(sim, heat_par, FS_HEAT_PARAMS)) return die("fs_heat_params");
+        if (!heat_dump_path.empty()) remove(heat_dump_path.c_str());   // the run appends to it
+    }
+    bool stepwise = !heat_dump_path.empty();             // --images, --volume: the run's frames do not fit the ring; --heat-dump
     long image_ring = 0;
     if (!images_dir.empty()) {
         if (view_spec.empty()) {                         // the 2-D viewer's density and v_x frames (gui.py:271-279)
@@ -710,7 +788,10 @@ int main(int argc, char** argv)
     } else {
         for (int i = 0; i < iter; ++i) {
             if (fs_run_one(sim)) return die("fs_run_one");
-            if (dump_every > 0 && (i + 1) % dump_every == 0 && fs_dump_frame(sim)) return die("fs_dump_frame");
+            if (dump_every > 0 && (i + 1) % dump_every == 0) {
+                if (fs_dump_frame(sim)) return die("fs_dump_frame");
+                if (!heat_dump_path.empty() && append_heat_frame(sim, heat_dump_path.c_str())) return die("--heat-dump");
+            }
             long kept = 0;
             if (!images_dir.empty()) {
                 if (fs_image_log(sim, nullptr, nullptr, 0, &kept, nullptr)) return die("fs_image_log");
@@ -721,7 +802,10 @@ int main(int argc, char** argv)
                 if (kept == volume_ring && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
             }
         }
-        if (dump_every == -1 && fs_dump_frame(sim)) return die("fs_dump_frame");
+        if (dump_every == -1) {
+            if (fs_dump_frame(sim)) return die("fs_dump_frame");
+            if (!heat_dump_path.empty() && append_heat_frame(sim, heat_dump_path.c_str())) return die("--heat-dump");
+        }
     }
     if (fs_sync(sim)) return die("fs_sync");
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -729,6 +813,7 @@ int main(int argc, char** argv)
     if (!body_forces_path.empty() && write_body_forces(sim, body_forces_path.c_str(), width, height, depth, dt, speed)) return die("fs_body_force_log");
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!monitor_path.empty() && write_monitor(sim, monitor_path.c_str(), width, height, depth, dt)) return die("fs_monitor_log");
+    if (!heat_log_path.empty() && write_heat_log(sim, heat_log_path.c_str())) return die("fs_heat_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
     if (!volume_dir.empty() && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
