@@ -7,6 +7,9 @@
 //
 // Orchestration follows Simulation::step()/run() of the reference (simulation.cpp:49-150);
 // every numeric expression lives in kernels.hip.
+//
+// One translation unit: this file holds the core of Engine<T> (the reference's step) and the C entries; each feature
+// beyond the reference is a part of the engine in driver/<feature>.h, over driver/common.h.
 #include "../../include/fluidsim.h"
 #include "kernels.h"
 #include "voxelize.h"
@@ -31,42 +34,23 @@
 #include "step_ring.h"
 #include "options.h"
 
-#include <hip/hip_runtime_api.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cerrno>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <exception>
-#include <limits>
-#include <string>
-#include <type_traits>
-#include <vector>
+#include "driver/common.h"
+#include "driver/forces.h"
+#include "driver/bodies.h"
+#include "driver/residual.h"
+#include "driver/flow_stats.h"
+#include "driver/vortex.h"
+#include "driver/sampling.h"
+#include "driver/images.h"
+#include "driver/volume.h"
+#include "driver/tracers.h"
+#include "driver/monitor.h"
+#include "driver/inflow.h"
+#include "driver/heat.h"
+#include "driver/confine.h"
+#include "driver/viewer.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 // what "auto" means for the options "zero_start" and "fuse_project_advect": decided by measurement.
 // (-DFS_ZERO_START_AUTO=0|1, -DFS_PROJECT_ADVECT_AUTO=0|1: development builds for same-box A/B runs of an unchanged bench.py)
@@ -77,412 +61,9 @@ int fail(int code, const char* fmt, ...)
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_HEAT, FAM_COUNT };
 const char* const kFamilyNames[FAM_HEAT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
 // the families added since (tests/test_inflow_cpu.py pins the text of the table above): FAM_HEAT onwards
 const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT] = { "heat" };
-inline const char* family_name(int f) { return f < FAM_HEAT ? kFamilyNames[f] : kLaterFamilyNames[f - FAM_HEAT]; }
-
-constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
-// heat (heat.h): two more slots of the engine's slot table behind the public fields -- the temperature and its pre-solve
-// snapshot -- and two more arrays in the pool while heat is on
-constexpr int NHEAT = 2, NSLOT = FS_NFIELDS + NHEAT, NPOOL_MAX = NPOOL + NHEAT;
-constexpr int F_THETA = FS_NFIELDS, F_THETA_PREV = FS_NFIELDS + 1;
-static_assert(fs::HEAT_PARAMS == FS_HEAT_PARAMS && fs::HEAT_COLS == FS_HEAT_COLS && FS_HEAT_LOG_COLS == 1 + FS_HEAT_COLS, "heat.h restates the header");
-
-struct Span {
-    hipEvent_t a, b;
-    int fam;
-    long launches;
-};
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------------
-struct EngineBase {
-    virtual ~EngineBase() {}
-    virtual int step() = 0;
-    virtual int run_one() = 0;
-    virtual int set_bounds(int b, int field) = 0;
-    virtual int linear_solver(int b, int field, int prev, float a, float c) = 0;
-    virtual int diffuse(int b, int field, int prev) = 0;
-    virtual int project() = 0;
-    virtual int advect(int b, int field, int prev) = 0;
-    virtual int get_field(int which, void* dst, size_t n, int elem) = 0;
-    virtual int set_field(int which, const void* src, size_t n, int elem) = 0;
-    virtual int set_mask(const uint8_t* mask, size_t n) = 0;
-    virtual int point(int which, int x, int y, int z, float v, int set_instead) = 0;
-    virtual int stats(int which, double* out3) = 0;
-    virtual int dump_frame() = 0;
-    virtual int time_sweeps(int b, int field, int prev, float a, float c, int reps, double* ms) = 0;
-    virtual int apply_solid_cells(const int* cells, long n) = 0;
-    virtual int tuned_two() const = 0;      // launch plan ids in use (launch_plan.h), -1 = none
-    virtual int tuned_three() const = 0;
-    virtual int halo_depth() const = 0;
-    virtual int streamlines(int density, double proximity, int max_length, double step_size, double threshold) = 0;
-    virtual int obstacle_surface() = 0;
-    virtual int reference_order_sum(int which, double* out) = 0;
-    virtual int multigrid_levels() const = 0;
-    virtual int multigrid_first_replicated() const = 0;
-    virtual int obstacle_force(double* out5, double* per_plane) = 0;
-    virtual int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int solve_residual(int b, int field, int prev, double a, double c, double* out4, double* per_plane) = 0;
-    virtual int diffuse_residual(int b, int field, int prev, double* out4, double* per_plane) = 0;
-    virtual int residual_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int flow_stats_config() = 0;       // apply fs_set_option("flow_stats"): allocate or free, clear
-    virtual int flow_stats_sample() = 0;
-    virtual int flow_stats_field(int which, void* dst, size_t n, int elem) = 0;
-    virtual int flow_stats_dump(const char* dir) = 0;
-    virtual int vortex_field(int which, void* dst, size_t n, int elem) = 0;
-    virtual int vortex_dump(const char* dir) = 0;
-    virtual int confine_vorticity(double eps) = 0;
-    virtual int heat_config(const double* par) = 0;          // apply fs_heat_params (validated): allocate or free, set up the log
-    virtual int heat_apply() = 0;
-    virtual int heat_transport() = 0;
-    virtual int heat_budget(double* out, double* per_plane) = 0;
-    virtual int heat_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int heat_get(void* dst, size_t n, int elem) = 0;
-    virtual int heat_set(const void* src, size_t n, int elem) = 0;
-    virtual int inflow_plane(long step, double* out) = 0;
-    virtual int inflow_eddies(long step, double* out) = 0;
-    virtual int flow_monitor(double* out16, double* per_plane, double* x_profile) = 0;
-    virtual int monitor_sample() = 0;
-    virtual int monitor_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int isosurface(int source, double level) = 0;
-    virtual int sample_points(const double* xyz, long n) = 0;
-    virtual int sample(int source, int mode, double* out, long n) = 0;
-    virtual int probe_sample() = 0;
-    virtual int probe_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int label_bodies(long* n_components, long* n_bodies) = 0;
-    virtual int body_labels(int32_t* dst, size_t n) = 0;
-    virtual int body_info(double* rows, long max_rows, long* n_rows) = 0;
-    virtual int body_force(double* out, long max_rows, long* n_rows, double* per_plane) = 0;
-    virtual int body_force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) = 0;
-    virtual int body_counts(int* bodies, int* components) = 0;
-    virtual int image_values(int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows) = 0;
-    virtual int image_rgb(int source, int kind, int axis, int index, double vmin, double vmax, double alpha, uint8_t* out, size_t n_bytes,
-                          int* cols, int* rows) = 0;
-    virtual int image_config() = 0;            // apply fs_image_views / fs_set_option("image_log"): allocate or free, clear
-    virtual int image_sample() = 0;
-    virtual int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
-    virtual int volume_rays(int slot, const double* rays, int cols, int rows) = 0;
-    virtual int volume_render(int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc) = 0;
-    virtual int volume_config() = 0;           // apply fs_volume_views / fs_volume_rays / fs_set_option("volume_log"): allocate or free, clear
-    virtual int volume_sample() = 0;
-    virtual int volume_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
-    virtual int tracer_config() = 0;           // apply fs_set_option("tracers") / ("tracer_log"): allocate or free, clear
-    virtual int tracer_seed(const double* xyz, long n) = 0;
-    virtual int tracer_clear() = 0;
-    virtual int tracer_advance() = 0;
-    virtual int tracer_fetch(double* xyz, int32_t* meta, long max, long* n) = 0;
-    virtual int tracer_sample(int source, int mode, double* out, long n) = 0;
-    virtual int tracer_log_fetch(double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped) = 0;
-};
-
-// one view of the image log (fs_image_views)
-struct ImageView {
-    int source, kind, axis, index;
-    double vmin, vmax, alpha;
-};
-
-// one view of the volume log (fs_volume_views)
-struct VolumeLogView {
-    int source, slot;
-    double par[fs::VOLUME_PARAMS];
-};
-
-struct fs_sim {
-    // Simulation's public members (simulation.h:44-54); W/H/D are the GLOBAL extents
-    int W = 0, H = 0, D = 0, iter = 0, speed = 0, acc = 0;
-    float dt = 0, diff = 0, visc = 0;
-    // options
-    bool fp64 = false;
-    int solver = FS_SOLVER_JACOBI;
-    float omega = 1.0f;          // relaxation factor of solver=rbsor
-    int replay_two = -2, replay_three = -2;   // "launch_plans": replay these plan ids instead of timing (-2: not set)
-    int mg_cycles = 4, mg_pre = 1, mg_post = 1, mg_coarse = 30;   // solver=mg: V-cycles per pressure solve, smoothing steps, coarsest-level iterations
-    int mg_min_planes = 32;      // z-slabs: a coarse level stays distributed while every rank keeps at least this many of its planes
-                                 // (measured, 512^3 as four slabs: 4 -> 203, 16 -> 186, 32 -> 175, 64 -> 152 ms per step; below 32 the
-                                 // exchanges of a level cost more than computing it whole on every rank, above it the whole-held level
-                                 // of an 8-way split is as large as a rank's own slab)
-    std::string dump_dir = "data";
-    int dump_every = 1;
-    unsigned voxel_seed = 1;
-    bool quiet = false, profile = false, elide_dead = false;
-    bool fuse_advect = true;     // one kernel for the three velocity advections of a step (single GPU)
-    // "zero_start" / "fuse_project_advect": -1 = auto, 0, 1.  What auto means is decided by measurement.
-    int zero_start = -1;         // project(): the divergence pass does not zero p in memory, the first pass of the solve takes zeros
-    int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
-    double confinement = 0.0;    // "vorticity_confinement": strength of the confinement pass at the start of a step, 0 = off
-    long n_confine = 0;          // confinement passes done, inside steps and by fs_confine_vorticity (fs_get_int)
-    // heat and buoyancy (heat.h): the parameters as fs_heat_params last set them; mode 0 = off, 1 = manual, 2 = in fs_step
-    double heat[fs::HEAT_PARAMS] = {0, 0, 0, 0, 2, 0, 0, 0, 1, 1, 1, 1, 1, 1, 0};
-    int heat_mode() const { return (int)heat[fs::HP_MODE]; }
-    long n_heat_apply = 0, n_heat_transport = 0;   // passes done, inside steps and by fs_heat_apply / fs_heat_transport (fs_get_int)
-    // turbulent inflow (inflow.h): with "inflow" on, fs_step writes the x = 1 face from these instead of (speed, 0, 0)
-    bool inflow = false;
-    int inflow_n = 0;            // "inflow_eddies"
-    double inflow_sigma = 4.0, inflow_rms = 0.0;   // "inflow_sigma", "inflow_rms"
-    double inflow_convect = -1.0;   // "inflow_convect": cells per step, < 0 = "auto" (dt * width * speed)
-    uint64_t inflow_seed = 1;
-    std::vector<double> inflow_mean, inflow_scale;   // fs_inflow_profile: h x d each, empty = speed everywhere / 1 everywhere
-    std::vector<double> gust_t, gust_f;              // fs_inflow_gust: the knots
-    long inflow_gen = 0;         // bumped by fs_inflow_profile: the maps are uploaded anew
-    long n_inflow = 0;           // planes written by steps ("inflow_passes")
-    double inflow_convect_now() const { return inflow_convect < 0.0 ? ((double)dt * (double)W) * (double)speed : inflow_convect; }
-    long n_zero_start = 0, n_project_advect = 0;   // projections / steps that took those paths (fs_get_int)
-    int overlap = -1;            // z-slabs, how a pass and its halo exchange are scheduled: 0 the pass, then the exchange; 1 boundary
-                                 // planes first, their exchange on the communication stream while the interior is computed; 2 boundary
-                                 // launch + exchange on the communication stream beside the interior launch; -1 (default) = "auto":
-                                 // the three are timed once over the real transport, the slowest rank's time decides (all ranks agree)
-    int comm_cus = 0;            // z-slabs: CUs kept free of solver workgroups (the compute stream gets a CU mask) so that the
-                                 // transport's kernels find room beside a launch that fills the chip; -1 = "auto": 0 and 8 are timed
-    bool split_dens = true;      // z-slabs: run half of the (dead) density solve between the first projection and the velocity
-                                 // advection, so that the reach of the back-trace arrives on the host without stalling the device
-    // slab-step bookkeeping readable through fs_get_int
-    long n_stream_syncs = 0;     // host synchronisations of the compute stream issued by the slab step (reach fallback path)
-    long n_alloc_syncs = 0;      // ... by one-off allocations inside a step (the gathered sources at the first gather)
-    long n_reach_waits = 0, n_reach_blocked = 0;   // waits for an asynchronously delivered reach; those that found it not yet there
-    long n_reach_hidden = 0, n_reach_exposed = 0;  // gathers + advections queued while the device was still busy with the half density
-                                                   // solve placed before them (hidden) / after it had run dry (exposed: a bubble)
-    double reach_wait_ms = 0.0;  // host time spent in them
-    int overlap_plan = -1, cus_plan = -1;          // what "auto" chose (or the forced values), -1 before the first slab solve
-    double overlap_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // slowest rank's ms per pass of each timed candidate (overlap 0..3 x cu mask off/on)
-    bool debug_poison = false;   // fill the gathered advection source with NaN bit patterns before each gather
-    int last_reach = 0;          // planes of reach used by the most recent slab advection
-    // device
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream_full = nullptr, stream_masked = nullptr;   // z-slabs with comm_cus: `stream` is one of these two
-    EngineBase* eng = nullptr;
-    // z-slab partition (comm.h)
-    fs::Comm comm;
-    // timing
-    std::vector<Span> spans;
-    std::vector<hipEvent_t> event_pool;
-    double fam_ms[FAM_COUNT] = {0};
-    long fam_launches[FAM_COUNT] = {0};
-    // dumps
-    FILE* dump_fp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool dump_open = false, dump_warned = false, in_run = false;
-    long step_no = 0;
-    long steps_total = 0;        // steps this handle has completed (the "step" column of fs_force_log)
-    int force_log = 0;           // "force_log": steps the per-step force log keeps, 0 = off
-    long force_log_gen = 0;      // bumped by every fs_set_option("force_log"): the ring is reallocated and cleared
-    int residual_log = 0;        // "residual_log": steps the per-step residual log keeps, 0 = off
-    long residual_log_gen = 0;   // bumped by every fs_set_option("residual_log")
-    int flow_stats = 0;          // "flow_stats": accumulators per cell, 0 = off, 5 = "mean", 12 = "moments" (flow_stats.h)
-    long flow_stats_gen = 0;     // bumped by every fs_set_option("flow_stats"): the accumulators are (re)allocated and cleared
-    long flow_stats_every = 1, flow_stats_start = 0;   // fs_step samples when steps_total > start and (steps_total - start - 1) % every == 0
-    long flow_stats_n = 0;       // samples taken since the last reset
-    std::vector<int> probes;     // fs_set_probes: x, y, z per probe, padded global coordinates
-    int probe_log = 0;           // "probe_log": records the probe log keeps, 0 = off
-    long probe_gen = 0;          // bumped by fs_set_probes and fs_set_option("probe_log"): list and ring are set up anew, the log is cleared
-    int body_log = 0;            // "body_force_log": steps the per-body force log keeps, 0 = off
-    long body_log_gen = 0;       // bumped by fs_set_option("body_force_log") and ("moment_origin"): the ring is reallocated and cleared
-    double moment_origin[3] = {0.0, 0.0, 0.0};   // "moment_origin": r0 of the per-body moments, padded index coordinates
-    std::vector<ImageView> image_views;   // fs_image_views
-    int image_log = 0;           // "image_log": frames the image log keeps, 0 = off
-    long image_every = 1;        // "image_every": fs_step takes a frame when (steps_total - 1) % image_every == 0
-    long image_gen = 0;          // bumped by fs_image_views and fs_set_option("image_log"): the ring is set up anew, the log is cleared
-    std::vector<uint8_t> image_table;   // fs_image_colormap: n RGB triples; empty = the built-in table
-    long image_table_gen = 0;    // bumped by fs_image_colormap
-    int vol_cols[fs::VOLUME_CAMERAS_MAX] = {0, 0, 0, 0}, vol_rows[fs::VOLUME_CAMERAS_MAX] = {0, 0, 0, 0};   // the ray set of each camera slot, 0 = free
-    std::vector<VolumeLogView> volume_views;   // fs_volume_views
-    int volume_log = 0;          // "volume_log": frames the volume log keeps, 0 = off
-    long volume_every = 1;       // "volume_every": fs_step takes a frame when (steps_total - 1) % volume_every == 0
-    long volume_gen = 0;         // bumped by fs_volume_views, fs_set_option("volume_log") and a new ray set of a slot a view uses
-    int monitor_log = 0;         // "monitor_log": records the flow-monitor log keeps, 0 = off
-    long monitor_every = 1;      // "monitor_every": fs_step takes a record when (steps_total - 1) % monitor_every == 0
-    long monitor_gen = 0;        // bumped by fs_set_option("monitor_log") and ("monitor_stations"): the ring is reallocated and cleared
-    int monitor_nstations = 0;   // "monitor_stations": how many are set
-    fs::MonitorStations monitor_stations = {{0, 0, 0, 0, 0, 0, 0, 0}};   // their x indices, 0 = unused
-    int tracers = 0;             // "tracers": slots of the tracer pool, 0 = off
-    long tracer_gen = 0;         // bumped by fs_set_option("tracers"): pool and log are set up anew and cleared
-    int tracer_log = 0;          // "tracer_log": snapshot frames the tracer log keeps, 0 = off
-    long tracer_log_gen = 0;     // bumped by fs_set_option("tracer_log"): the ring is set up anew, the log is cleared
-    long tracer_every = 1;       // "tracer_every": fs_step takes a snapshot when (steps_total - 1) % tracer_every == 0
-    long tracer_seeded = 0;      // particles ever seeded or released since the pool was cleared: the next goes into slot seeded % C
-    std::vector<double> tracer_emit;   // fs_tracer_emitters: x, y, z per emitter
-    long tracer_emit_every = 1;  // fs_step releases one particle per emitter when (steps_total - 1) % tracer_emit_every == 0
-    long tracer_emit_gen = 0;    // bumped by fs_tracer_emitters
-    long dump_frames = 0;
-    fs::FrameWriter writer;      // pinned double-buffered D2H + writer thread
-    // result of the last fs_streamlines call
-    std::vector<long> sl_offsets;
-    std::vector<double> sl_points, sl_norm;
-    // result of the last fs_obstacle_surface call
-    std::vector<float> surf_verts;
-    std::vector<int> surf_tris;
-    bool surf_valid = false;
-    // result of the last fs_isosurface call (a slot of its own)
-    std::vector<float> iso_verts;
-    std::vector<int> iso_tris;
-    bool iso_valid = false;
-    bool dump_async = true;
-    fs::SweepTune tune;          // launch tunables of this handle (fs_set_option sweep_* / pair_* / project_kernels)
-
-    int span_begin(int fam)
-    {
-        if (!profile) return -1;
-        Span sp;
-        sp.fam = fam;
-        sp.launches = 0;
-        for (hipEvent_t* ev : { &sp.a, &sp.b }) {
-            if (!event_pool.empty()) { *ev = event_pool.back(); event_pool.pop_back(); }
-            else if (hipEventCreate(ev) != hipSuccess) return -1;
-        }
-        hipEventRecord(sp.a, stream);
-        spans.push_back(sp);
-        return (int)spans.size() - 1;
-    }
-    void span_end(int id, long launches)
-    {
-        if (id < 0) return;
-        spans[id].launches = launches;
-        hipEventRecord(spans[id].b, stream);
-    }
-    void resolve_spans()
-    {
-        if (spans.empty()) return;
-        hipStreamSynchronize(stream);
-        for (Span& sp : spans) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
-                fam_ms[sp.fam] += ms;
-                fam_launches[sp.fam] += sp.launches;
-            }
-            event_pool.push_back(sp.a);
-            event_pool.push_back(sp.b);
-        }
-        spans.clear();
-    }
-};
-
-namespace {
-
-struct ScopedSpan {
-    fs_sim* s; int id; long n;
-    ScopedSpan(fs_sim* s_, int fam, long launches = 1) : s(s_), id(s_->span_begin(fam)), n(launches) {}
-    ~ScopedSpan() { s->span_end(id, n); }
-};
-
-// The device ring of a per-step log: `at` keeps the books (step_ring.h), `base` holds at.cap slots of slot_bytes, set up for
-// generation `gen` of the options that size it.  What a slot holds, when a record is committed and how the fetched slots
-// become rows is the log's own business.
-struct LogRing {
-    fs::StepRing at;
-    char* base = nullptr;
-    size_t slot_bytes = 0;
-    long gen = -1;
-
-    bool on() const { return at.cap > 0; }
-    char* slot(long k) const { return base + (size_t)k * slot_bytes; }
-    void release() { if (base) hipFree(base); base = nullptr; }   // the engine's end
-    // For generation `gen_`: the old ring goes (a queued record may still write to it: the stream is synchronised first) and
-    // `cap` zero-filled slots of `bytes` come; cap <= 0 = the log is off.  Where the allocation fails, `base` is null.
-    hipError_t setup(hipStream_t stream, long gen_, int cap = 0, size_t bytes = 0)
-    {
-        hipError_t e = base ? hipStreamSynchronize(stream) : hipSuccess;
-        if (e == hipSuccess && base) e = hipFree(base);
-        if (e != hipSuccess) return e;
-        base = nullptr;
-        slot_bytes = bytes;
-        at.reset(0);
-        gen = gen_;
-        if (cap <= 0) return hipSuccess;
-        if ((e = hipMalloc((void**)&base, (size_t)cap * bytes)) != hipSuccess) { base = nullptr; return e; }
-        if ((e = hipMemsetAsync(base, 0, (size_t)cap * bytes, stream)) == hipSuccess) at.reset(cap);
-        return e;
-    }
-    // The retained slots, oldest first, to the host buffer `dst`, in at most two copies on `stream`.  A ring laid out in
-    // sections (the tracer log) names the section's first slot and its bytes per slot.
-    hipError_t copy_out(hipStream_t stream, void* dst, const void* section = nullptr, size_t bytes = 0) const
-    {
-        const char* from = section ? (const char*)section : base;
-        if (!section) bytes = slot_bytes;
-        fs::StepRing::Run run[2];
-        hipError_t e = hipSuccess;
-        for (int r = 0, n = at.runs(run); r < n && e == hipSuccess; ++r) {
-            e = hipMemcpyAsync(dst, from + (size_t)run[r].first_slot * bytes, (size_t)run[r].count * bytes, hipMemcpyDeviceToHost, stream);
-            dst = (char*)dst + (size_t)run[r].count * bytes;
-        }
-        return e;
-    }
-
-    // The three steps every log's fetch shares; what lies between them (how slots become rows) is the log's own.
-    // 1. The sizes go out: `rows` (what the retained records amount to, in the entry's unit) into *n_out, the overwritten
-    //    records into *n_dropped.  Returns GO_ON, or the entry's answer: FS_OK for a caller that asked for the sizes alone
-    //    (`wants_data` false: nothing is drained), FS_EINVAL for one without the room.
-    struct FetchWords { const char *entry, *unit, *hint; };   // of the refusal: "fs_force_log", "rows", "rows = NULL"
-    enum { GO_ON = 1 };                                        // neither FS_OK nor an error code
-    int fetch_begin(const FetchWords& w, long rows, long room, bool wants_data, long* n_out, long* n_dropped) const
-    {
-        if (n_out) *n_out = rows;
-        if (n_dropped) *n_dropped = at.dropped();
-        if (!wants_data) return FS_OK;
-        if (room < rows) return fail(FS_EINVAL, "%s: %ld %s retained, room for %ld (pass %s to ask)", w.entry, rows, w.unit, room, w.hint);
-        return GO_ON;
-    }
-    // 2. The retained slots to the host, oldest first, and one synchronisation of `stream`: the whole slots into `dst`, or one
-    //    or two sections of the ring into `dst` and `dst2` (a null one is left out).  An empty log costs nothing: its fetch
-    //    is no synchronisation point.
-    hipError_t fetch_copy(hipStream_t stream, void* dst, const void* section = nullptr, size_t bytes = 0, void* dst2 = nullptr,
-                          const void* section2 = nullptr, size_t bytes2 = 0) const
-    {
-        if (at.retained() == 0) return hipSuccess;
-        hipError_t e = dst ? copy_out(stream, dst, section, bytes) : hipSuccess;
-        if (e == hipSuccess && dst2) e = copy_out(stream, dst2, section2, bytes2);
-        return e == hipSuccess ? hipStreamSynchronize(stream) : e;
-    }
-    // 3. The records have been handed out: their step numbers into `steps` (if any), and the ring is empty again.
-    void fetch_end(long* steps = nullptr)
-    {
-        if (steps)
-            for (long i = 0, n = at.retained(); i < n; ++i) steps[i] = at.step_of(i);
-        at.drain();
-    }
-};
-
-// what the image entries accept without looking at the state: a source of fs_sample by its bits, and a colour range
-bool image_source_ok(int source)
-{
-    if ((source >= 0 && source < FS_NFIELDS) || source == FS_SOURCE_HEAT) return true;
-    if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX) return (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS;
-    if (source >= 0 && (source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
-        const int sel = source & (FS_SAMPLE_STAT - 1), which = sel & ~FS_STAT_RAW;
-        return which >= 0 && which <= FS_STAT_TKE && !((sel & FS_STAT_RAW) && which == FS_STAT_TKE);
-    }
-    return false;
-}
-bool image_range_ok(double vmin, double vmax, double alpha)
-{
-    return std::isfinite(vmin) && std::isfinite(vmax) && vmin < vmax && alpha >= 0.0 && alpha <= 1.0;
-}
-// bytes of one frame of the image log: the views' RGB images one after the other
-size_t image_frame_bytes(const fs_sim* s, const std::vector<ImageView>& views)
-{
-    size_t bytes = 0;
-    for (const ImageView& v : views) {
-        int c, r;
-        fs::image_dims(v.axis, s->W, s->H, s->D, &c, &r);
-        bytes += 3 * (size_t)c * (size_t)r;
-    }
-    return bytes;
-}
-
-// bytes of one frame of the volume log: the views' RGB images one after the other; `slot`, cols, rows: a slot about to change
-size_t volume_frame_bytes(const fs_sim* s, const std::vector<VolumeLogView>& views, int slot = -1, int cols = 0, int rows = 0)
-{
-    size_t bytes = 0;
-    for (const VolumeLogView& v : views)
-        bytes += v.slot == slot ? 3 * (size_t)cols * (size_t)rows : 3 * (size_t)s->vol_cols[v.slot] * (size_t)s->vol_rows[v.slot];
-    return bytes;
-}
-
-template <class T> T host_cbrt(T v);
-template <> float host_cbrt<float>(float v) { return std::cbrt(v); }     // std::cbrt(float), simulation.cpp:295
-template <> double host_cbrt<double>(double v) { return std::cbrt(v); }
 
 // ---------------------------------------------------------------------------------------
 template <class T>
@@ -500,24 +81,21 @@ struct Engine : EngineBase {
     int slot[NSLOT];                    // field -> array id (aliases allowed inside a step); F_THETA / F_THETA_PREV: -1 while heat is off
     bool held[NPOOL_MAX] = {false};     // temporaries owned by a running solve
     int npool = NPOOL;                  // arrays of the pool: NPOOL_MAX while heat is on
-    T* heat_chunk = nullptr;            // the allocation behind arr[NPOOL ..]
-    double* heat_ws = nullptr;          // workspace of the heat budget's three launches (stream-ordered reuse)
-    LogRing heat_ring;                  // the per-step heat log: records of HEAT_COLS doubles
+    DevBuf<uint8_t> flags_buf, kill_buf;   // what the two views below look into
     uint8_t* flags = nullptr;           // shifted like the fields
     uint8_t* kill = nullptr;            // one byte per four cells for the sweeps; byte (cell+3)/4
     fs::MaskPlan maskplan;              // single GPU, fp32: which rows are free of kill bytes (the three-sweep kernel's mask-free body)
     bool flags_dirty = true;
     bool halos_dirty = false;           // a host-side mutation may have changed a slab boundary plane
-    void* dense = nullptr;              // device staging of fs_get_field / fs_set_field (dense local slab), on demand
-    size_t dense_bytes = 0;
+    DevBuf<char> dense;                 // device staging of fs_get_field / fs_set_field (dense local slab), grown on demand
     T* gathered = nullptr;              // gathered advection source (z-slabs only), LEAD-shifted global array
     T* gathered3[3] = {nullptr, nullptr, nullptr};   // the same for the three sources of the fused velocity advection
-    double* red = nullptr;              // stats scratch
+    DevBuf<double> red;                 // stats scratch
     T rb_omega = (T)1;                  // relaxation factor of the red-black / damped passes of the running solve
     bool rb_damped = false;             // those passes are two damped Jacobi sweeps (solver=mg level 0) instead of one red-black iteration
     fs::Multigrid<T> mg;                // coarse levels of solver=mg; rebuilt when the flag bytes change
     bool mg_current = false;
-    T* coltab = nullptr;                // clamp tables of the advection row kernels: 6 x (H+2)(D+2) (single GPU only)
+    DevBuf<T> coltab;                   // clamp tables of the advection row kernels: 6 x (H+2)(D+2) (single GPU only)
     // launch plan ids (launch_plan.h), chosen once per grid by choose_launch_plans
     int plan_two = -1;                  // fastest two-sweep plan, of the pair or the fused kernel (-1: not chosen yet)
     int plan_two_pair = 0;              // fastest plan of jacobi_pair_kernel itself: its red-black / damped passes (rbsor, mg level 0)
@@ -540,80 +118,22 @@ struct Engine : EngineBase {
     double vzmax_prev = -1.0;           // max |v_z| at the end of the previous step (= v_z_prev of this one), -1 = unknown
     double vzmax_end = -1.0;            // the same for the step that is running
     bool in_step = false;               // inside step(): the data flow between the solver's calls is known
-    // pressure force (forces.h): the per-step log is a device ring of steps x 2 projections x g.D plane records
-    LogRing force_ring;                 // for S->force_log_gen
-    double* force_scratch = nullptr;    // fs_obstacle_force: one record per local plane
-    // solve residuals (residual.h): the per-step log is a device ring of steps x 6 solves x {before, after} x g.D plane records
-    LogRing res_ring;                   // for S->residual_log_gen; a slot's tag, bit k: solve k of that step ran (an elided solve leaves no record)
-    double* res_scratch = nullptr;      // fs_solve_residual: one record per local plane
-    double* res_partial = nullptr;      // the row-chunk records between the two kernels of a launch (stream-ordered reuse)
-    unsigned res_ran_now = 0;           // the tag of the step that is running
-    // time-averaged flow statistics (flow_stats.h): private allocations, one per accumulator, never exported to slab neighbours
-    fs::FlowStatsAcc stat_acc = {};
-    int stat_nacc = 0;                  // accumulators allocated: 0, 5 or 12
-    long stat_gen = -1;                 // S->flow_stats_gen they were set up for
-    // vortex identification (vortex.h): the one field a call computes, in the fields' layout (LEAD-shifted like them); private,
-    // allocated at the first call.  Only the kernel writes it, and only cells of interior rows: its ghosts stay +0.0.
-    T* vort = nullptr;
-    // field sampling (sample.h): the point set of fs_sample_points and the values of the last fs_sample, on the device
-    double* samp_pts = nullptr;
-    double* samp_out = nullptr;
-    long samp_n = 0, samp_room = 0;     // points kept / points the two arrays have room for
-    // point probes (sample.h): the per-step log is a device ring of records x probe_n probes x {q, u, v, w, p}
-    long* probe_idx = nullptr;          // each probe's cell index in this slab's arrays, -1 = a plane another rank owns
-    LogRing probe_ring;                 // for S->probe_gen, as is the list; on only with probe_n > 0
-    int probe_n = 0;
-    // slice and projection images (image.h): one allocation holds the value image, the flag image of a slice, the obstacle
-    // silhouette of each axis (valid until obs changes), an RGB staging image and the colour table; the per-step log is a
-    // device ring of frames (the views' RGB images one after the other)
-    double* img_val = nullptr;          // the allocation's base
-    uint8_t* img_flag = nullptr;
-    uint8_t* img_sil[3] = {nullptr, nullptr, nullptr};
-    bool img_sil_ok[3] = {false, false, false};
-    uint8_t* img_rgb = nullptr;
-    uint8_t* img_table = nullptr;
-    int img_table_n = 0;
-    long img_table_gen = -1;            // S->image_table_gen the device table holds
-    LogRing img_ring;                   // for S->image_gen
-    // volume rendering (volume.h): the ray set of each camera slot, the staging images of fs_volume_render (grown on demand),
-    // and the per-step log, a device ring of frames (the views' RGB images one after the other).  The colour table is the
-    // image entries' (img_table).
-    double* vol_rays[fs::VOLUME_CAMERAS_MAX] = {nullptr, nullptr, nullptr, nullptr};
-    uint8_t* vol_rgb = nullptr;
-    double* vol_acc = nullptr;
-    size_t vol_room = 0;                // pixels the two staging images have room for
-    LogRing vol_ring;                   // for S->volume_gen
-    // tracer particles (tracers.h): the pool (positions as the sampler's point list, four meta words per slot), the emitters'
-    // points, and the snapshot log, a device ring of frames (all position frames, then all status frames)
-    double* tr_xyz = nullptr;
-    int* tr_meta = nullptr;
-    int tr_cap = 0;                     // slots allocated: S->tracers once set up
-    long tr_gen = -1;                   // S->tracer_gen the pool was set up for
-    double* tr_emit = nullptr;          // FS_TRACER_EMITTERS_MAX points, allocated with the pool
-    long tr_emit_gen = -1;              // S->tracer_emit_gen the device list holds
-    double* tr_out = nullptr;           // fs_tracer_sample: one value per slot, allocated at the first call
-    LogRing tr_ring;                    // for S->tracer_log_gen, -1 after a new pool
-    // per-body forces and moments (bodies.h): the labels (dense padded int32), what the host keeps of the last labelling, and
-    // the per-step log, a device ring of steps x 2 projections x (body_B + 1) whole-grid records
-    int* body_L = nullptr;
-    bool bodies_dirty = true;           // obs changed since the last labelling (set where the flag bytes are rebuilt)
-    int body_B = 0;                     // bodies 1 .. body_B; record 0 is the REST
-    long body_ncomp = 0;                // components, the REST's included
-    std::vector<double> body_info_host; // (body_B + 1) x BODY_INFO
-    int* body_bbox = nullptr;           // per record, the cells its workgroups scan
-    double* body_planes = nullptr;      // plane records of the last launch: g.D x (BODY_MAX + 1) x BODY_REC (stream-ordered reuse)
-    double* body_total = nullptr;       // fs_body_force: the whole-grid records
-    LogRing body_ring;                  // for S->body_log_gen, -1 after a relabelling: the ring is set up anew, the log is cleared
-    // flow monitor (monitor.h): the workspace of its three launches (allocated at the first record, stream-ordered reuse) and
-    // the per-step log, a device ring of records of MON_RESULT doubles (the whole record, then the stations' profile rows)
-    double* mon_ws = nullptr;
-    LogRing mon_ring;                   // for S->monitor_gen
-    // turbulent inflow (inflow.h): the two maps as uploaded for S->inflow_gen (null = not given), the eddy table of the step
-    // being written (room for inflow_cap entries), the result of fs_inflow_plane / fs_inflow_eddies; all stream-ordered reuse
-    double *inflow_dmean = nullptr, *inflow_dscale = nullptr, *inflow_out = nullptr, *inflow_dbg = nullptr;
-    fs::InflowEntry* inflow_tab = nullptr;
-    int inflow_cap = 0;
-    long inflow_up_gen = -1;
+    // the features beyond the reference's step, one part each (driver/*.h): a part's state is private to it, and it reaches the
+    // core through its reference to the engine
+    Forces<T> forces{*this};
+    Bodies<T> bodies{*this};
+    Residual<T> residual{*this};
+    FlowStats<T> flow_stats{*this};
+    Vortex<T> vortex{*this};
+    Sampling<T> sampling{*this};
+    Images<T> images{*this};
+    Volume<T> volume{*this};
+    Tracers<T> tracers{*this};
+    Monitor<T> monitor{*this};
+    Inflow<T> inflow{*this};
+    Heat<T> heat{*this};
+    Confine<T> confine{*this};
+    Viewer<T> viewer{*this};
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
     static constexpr int NRED = 3 * 1024 + 18;   // reduction scratch + up to six {sum, min, max} results (0, 1: stats / trace_reach; 2..4: post_vzmax)
 
@@ -623,12 +143,7 @@ struct Engine : EngineBase {
 
     int need_dense(size_t bytes)
     {
-        if (bytes <= dense_bytes) return FS_OK;
-        if (dense) HIP_TRY(hipFree(dense));
-        dense = nullptr;
-        dense_bytes = 0;
-        HIP_TRY(hipMalloc(&dense, bytes));
-        dense_bytes = bytes;
+        HIP_TRY(dense.grow(bytes));
         return FS_OK;
     }
 
@@ -667,16 +182,14 @@ struct Engine : EngineBase {
         for (int i = 0; i < NPOOL; ++i) arr[i] = pool_chunks[(size_t)(i / pool_per)] + (size_t)(i % pool_per) * pool_stride + g.lead;
         for (int f = 0; f < FS_NFIELDS; ++f) slot[f] = f;
         slot[F_THETA] = slot[F_THETA_PREV] = -1;
-        uint8_t* fb = nullptr;
-        HIP_TRY(hipMalloc((void**)&fb, g.n));
-        HIP_TRY(hipMemsetAsync(fb, 0, g.n, S->stream));
-        flags = fb + g.lead;
-        uint8_t* kb = nullptr;
-        HIP_TRY(hipMalloc((void**)&kb, g.n / 4 + 16));
-        HIP_TRY(hipMemsetAsync(kb, 0, g.n / 4 + 16, S->stream));
-        kill = kb + (g.lead - fs::LEAD) / 4;
-        HIP_TRY(hipMalloc((void**)&red, NRED * sizeof(double)));
-        if (!cm.active()) HIP_TRY(hipMalloc((void**)&coltab, sizeof(T) * 6 * (size_t)(g.H + 2) * (size_t)(g.D + 2)));
+        HIP_TRY(flags_buf.alloc((size_t)g.n));
+        HIP_TRY(hipMemsetAsync(flags_buf.get(), 0, g.n, S->stream));
+        flags = flags_buf.get() + g.lead;
+        HIP_TRY(kill_buf.alloc((size_t)g.n / 4 + 16));
+        HIP_TRY(hipMemsetAsync(kill_buf.get(), 0, g.n / 4 + 16, S->stream));
+        kill = kill_buf.get() + (g.lead - fs::LEAD) / 4;
+        HIP_TRY(red.alloc(NRED));
+        if (!cm.active()) HIP_TRY(coltab.alloc((size_t)6 * (size_t)(g.H + 2) * (size_t)(g.D + 2)));
         if (cm.active()) {
             int lo_pri = 0, hi_pri = 0;
             HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
@@ -723,40 +236,12 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    ~Engine() override
+    // Device memory frees itself (DevBuf), here and in the parts; what is left is the exported arena chunks, whose peers
+    // fs_destroy has unmapped by now (release_buffers), and what is not device memory.
+    ~Engine()
     {
         for (T* c : pool_chunks) hipFree(c);
-        if (flags) hipFree(flags - g.lead);
-        if (kill) hipFree(kill - (g.lead - fs::LEAD) / 4);
         for (T* c : gather_chunks) hipFree(c);        // the four gathered advection sources
-        if (dense) hipFree(dense);
-        if (red) hipFree(red);
-        if (coltab) hipFree(coltab);
-        if (force_scratch) hipFree(force_scratch);
-        if (res_scratch) hipFree(res_scratch);
-        if (res_partial) hipFree(res_partial);
-        for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
-        if (vort) hipFree(vort - g.lead);
-        if (samp_pts) hipFree(samp_pts);
-        if (samp_out) hipFree(samp_out);
-        if (probe_idx) hipFree(probe_idx);
-        if (img_val) hipFree(img_val);
-        if (tr_xyz) hipFree(tr_xyz);
-        if (tr_meta) hipFree(tr_meta);
-        if (tr_emit) hipFree(tr_emit);
-        if (tr_out) hipFree(tr_out);
-        for (double* q : vol_rays)
-            if (q) hipFree(q);
-        if (vol_rgb) hipFree(vol_rgb);
-        if (vol_acc) hipFree(vol_acc);
-        if (mon_ws) hipFree(mon_ws);
-        if (heat_chunk) hipFree(heat_chunk);
-        if (heat_ws) hipFree(heat_ws);
-        for (void* q : { (void*)inflow_dmean, (void*)inflow_dscale, (void*)inflow_out, (void*)inflow_dbg, (void*)inflow_tab })
-            if (q) hipFree(q);
-        for (void* q : { (void*)body_L, (void*)body_bbox, (void*)body_planes, (void*)body_total })
-            if (q) hipFree(q);
-        for (LogRing* r : { &force_ring, &body_ring, &res_ring, &probe_ring, &img_ring, &tr_ring, &vol_ring, &mon_ring, &heat_ring }) r->release();
         mg.release();
         for (hipEvent_t ev : { ev_edges, ev_halo, ev_int, ev_c2x, ev_reach[0], ev_reach[1], ev_reach[2], ev_slack })
             if (ev) hipEventDestroy(ev);
@@ -836,8 +321,8 @@ struct Engine : EngineBase {
         fs::launch_build_kill(S->stream, g, sc, flags, kill);
         if ((rc = build_clean())) return rc;
         flags_dirty = false;
-        bodies_dirty = true;
-        img_sil_ok[0] = img_sil_ok[1] = img_sil_ok[2] = false;
+        bodies.obs_changed();
+        images.obs_changed();
         mg_current = false;
         return FS_OK;
     }
@@ -932,14 +417,14 @@ struct Engine : EngineBase {
     int slab_barrier()
     {
         HIP_TRY(hipStreamSynchronize(S->stream));
-        if (S->comm.barrier(comm_on_compute_stream() ? S->stream : comm_stream, red)) return fail(FS_ECOMM, "barrier: %s", S->comm.last_error());
+        if (S->comm.barrier(comm_on_compute_stream() ? S->stream : comm_stream, red.get())) return fail(FS_ECOMM, "barrier: %s", S->comm.last_error());
         return FS_OK;
     }
     // the largest `v` of any rank, the same bits on every rank (host-blocking; tuning only)
     int rank_max(double v, double* out)
     {
         double h[3] = { v, v, v };
-        double* d3 = red + 3 * 1024;
+        double* d3 = red.get() + 3 * 1024;
         HIP_TRY(hipMemcpyAsync(d3, h, sizeof h, hipMemcpyHostToDevice, S->stream));
         int rc = comm_op([&](hipStream_t st) { return S->comm.reduce_stats(st, d3, g, S->D); }, "all-reduce");
         if (rc) return rc;
@@ -1304,7 +789,7 @@ struct Engine : EngineBase {
         return (T)S->dt * (T)S->diff * (T)S->W * (T)S->H * (T)S->D;
     }
 
-    int linear_solver(int b, int field, int prev, float a, float c) override
+    int linear_solver(int b, int field, int prev, float a, float c)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         int rc = ensure_flags();
@@ -1331,16 +816,16 @@ struct Engine : EngineBase {
         if (rc) return rc;
         if (S->solver == FS_SOLVER_GS_LEX && (rc = unalias(field))) return rc;
         const T c = (T)1 + (T)6 * a;
-        if ((rc = log_residual(log_k, 0, b, slot[field], slot[prev], (double)a, (double)c))) return rc;
+        if ((rc = residual.log(log_k, 0, b, slot[field], slot[prev], (double)a, (double)c))) return rc;
         int res;
         rc = solve(b, slot[field], slot[prev], a, c, S->acc, &res);   // :283
         if (rc) return rc;
         adopt(field, res);
-        return log_residual(log_k, 1, b, slot[field], slot[prev], (double)a, (double)c);
+        return residual.log(log_k, 1, b, slot[field], slot[prev], (double)a, (double)c);
     }
-    int diffuse(int b, int field, int prev) override { if (!in_step) vzmax_prev = -1.0; return diffuse_T(b, field, prev); }
+    int diffuse(int b, int field, int prev) { if (!in_step) vzmax_prev = -1.0; return diffuse_T(b, field, prev); }
 
-    int set_bounds(int b, int field) override
+    int set_bounds(int b, int field)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         int rc = ensure_flags();
@@ -1355,8 +840,8 @@ struct Engine : EngineBase {
     // equation of :320.  Level 0 is smoothed by the reference's update as damped Jacobi sweeps, two per pass of the pair
     // kernel (its red-black instantiation is 1.6x slower and smooths no better here), the coarse levels live in
     // multigrid.hip.  Single GPU.
-    int multigrid_levels() const override { return mg.levels(); }
-    int multigrid_first_replicated() const override { return mg.first_repl; }
+    int multigrid_levels() const { return mg.levels(); }
+    int multigrid_first_replicated() const { return mg.first_repl; }
     // the transport's part in the coarse levels of a slab run (multigrid.h): one-plane halo refreshes of distributed levels,
     // all-gathers at the seam to the levels every rank holds whole
     fs::MgHooks<T> mg_hooks()
@@ -1441,13 +926,13 @@ struct Engine : EngineBase {
     bool zero_start_ok(int log_k) const
     {
         if (!(S->zero_start < 0 ? ZERO_START_AUTO : S->zero_start != 0) || S->solver != FS_SOLVER_JACOBI || S->acc < 3 || S->comm.active()) return false;
-        if (log_k >= 0 && res_ring.on()) return false;
+        if (log_k >= 0 && residual.on()) return false;
         const TunedFor now{S->tune.fuse, S->tune.pair_shape, S->tune.two_kind, S->replay_two, S->replay_three};
         if (!(plan_two >= 0 && tuned_for == now) || plan_three < 0) return false;
         return fs::jacobi_fused_zero_start(S->tune, g, sc, (int)sizeof(T), plan_three);
     }
 
-    int project() override { return project_T(false); }
+    int project() { return project_T(false); }
     // defer_gradient (step(), "fuse_project_advect"): everything but the gradient pass -- v stays as it was before the
     // projection and FS_PRESSURE holds the solved pressure; the caller's next launch applies the gradient itself
     int project_T(bool defer_gradient)
@@ -1471,28 +956,21 @@ struct Engine : EngineBase {
         // rhs at the cell itself); the pressure halo planes still hold the previous projection and
         // must become the neighbours' freshly zeroed planes before the first sweep reads them.
         if ((rc = halo(arr[slot[FS_PRESSURE]]))) return rc;
-        if ((rc = log_residual(log_k, 0, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
+        if ((rc = residual.log(log_k, 0, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
         int res;
         if (S->solver == FS_SOLVER_MG) rc = multigrid_solve(FS_PRESSURE, FS_DIVERGENCE, &res);
         else rc = solve(0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], (T)1, (T)6, S->acc, &res, false, zero_start);   // :320
         if (rc) return rc;
         adopt(FS_PRESSURE, res);
-        if ((rc = log_residual(log_k, 1, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
+        if ((rc = residual.log(log_k, 1, 0, slot[FS_PRESSURE], slot[FS_DIVERGENCE], 1.0, 6.0))) return rc;
         if (!defer_gradient) {
             ScopedSpan sp(S, FAM_GRAD);
             fs::launch_gradient<T>(S->stream, S->tune, g, sc, arr[slot[FS_PRESSURE]], arr[slot[FS_VX]], arr[slot[FS_VY]],
                                    arr[slot[FS_VZ]], flags, h, (T)2 * h);
         }
-        if (proj >= 0 && proj < 2 && force_ring.on()) {
-            // "force_log": this projection's plane records go straight into the step's ring slot (no host sync)
-            ScopedSpan sp(S, FAM_FORCES);
-            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_slot(force_ring.at.next(), proj));
-        }
-        if (proj >= 0 && proj < 2 && body_ring.on()) {
-            // "body_force_log": this projection's whole-grid records of every body go into the step's ring slot (no host sync)
-            ScopedSpan sp(S, FAM_BODYFORCES);
-            fs::launch_body_forces<T>(S->stream, g, arr[slot[FS_PRESSURE]], flags, body_L, body_bbox, body_B + 1, S->moment_origin,
-                                      body_planes, body_slot(body_ring.at.next(), proj));
+        if (proj >= 0 && proj < 2) {                  // "force_log", "body_force_log": this projection's records
+            forces.record(proj);
+            bodies.record(proj);
         }
         // the next consumer of v's z-halo planes is the divergence of the second projection
         // (v_z[z+-1]) and the advection back-trace; refresh them now.
@@ -1512,9 +990,9 @@ struct Engine : EngineBase {
     {
         if (which < 0 || which > 2) return FS_OK;
         ScopedSpan sp(S, FAM_COMM);
-        double* out3 = red + 3 * 1024 + 3 * (2 + which);
+        double* out3 = red.get() + 3 * 1024 + 3 * (2 + which);
         const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
-        fs::launch_stats<T>(S->stream, g, arr[slot[FS_VZ]], out3, red, 3 * 1024, zlo, zhi);
+        fs::launch_stats<T>(S->stream, g, arr[slot[FS_VZ]], out3, red.get(), 3 * 1024, zlo, zhi);
         int rc = comm_op([&](hipStream_t st) { return S->comm.reduce_stats(st, out3, g, S->D); }, "all-reduce of max |v_z|");
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(reach_pinned + 3 * which, out3, 3 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
@@ -1551,7 +1029,7 @@ struct Engine : EngineBase {
     }
 
     // ---- advect (simulation.cpp:367-424) ------------------------------------------------
-    int advect(int b, int field, int prev) override
+    int advect(int b, int field, int prev)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         int rc = ensure_flags();
@@ -1588,7 +1066,7 @@ struct Engine : EngineBase {
         {
             ScopedSpan sp(S, FAM_ADVECT);
             fs::launch_advect<T>(S->stream, S->tune, g, sc, b, arr[slot[field]], src, arr[slot[FS_VX]], arr[slot[FS_VY]],
-                                 arr[slot[FS_VZ]], flags, kill, coltab, kx, ky, kz, zshift);
+                                 arr[slot[FS_VZ]], flags, kill, coltab.get(), kx, ky, kz, zshift);
         }
         return halo(arr[slot[field]]);
     }
@@ -1603,16 +1081,16 @@ struct Engine : EngineBase {
         int k = 0;
         for (int f : fields) {
             if (k >= 4) break;
-            double* out3 = red + 3 * 1024 + 3 * k;
+            double* out3 = red.get() + 3 * 1024 + 3 * k;
             const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
-            fs::launch_stats<T>(S->stream, g, arr[slot[f]], out3, red, 3 * 1024, zlo, zhi);
+            fs::launch_stats<T>(S->stream, g, arr[slot[f]], out3, red.get(), 3 * 1024, zlo, zhi);
             if (S->comm.active()) {
                 int rc = comm_op([&](hipStream_t cs) { return S->comm.reduce_stats(cs, out3, g, S->D); }, "stats all-reduce");
                 if (rc) return rc;
             }
             ++k;
         }
-        HIP_TRY(hipMemcpyAsync(&st[0][0], red + 3 * 1024, 3 * k * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipMemcpyAsync(&st[0][0], red.get() + 3 * 1024, 3 * k * sizeof(double), hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
         ++S->n_stream_syncs;
         double umax = 0.0;
@@ -1682,7 +1160,7 @@ struct Engine : EngineBase {
         {
             ScopedSpan sp(S, FAM_ADVECT);
             fs::launch_advect_velocity<T>(S->stream, S->tune, g, sc, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], p[0], p[1],
-                                          p[2], flags, kill, coltab, kx, ky, kz, zshift);
+                                          p[2], flags, kill, coltab.get(), kx, ky, kz, zshift);
         }
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = halo(arr[slot[f]]))) return rc;
@@ -1702,57 +1180,10 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    // ---- vorticity confinement (confine.h; beyond the reference) -----------------------------------------
-    // One pass of strength eps > 0 over the velocities as they are: out of place into three pool arrays, which become the
-    // velocities (the kernel also does what set_bounds(1 / 2 / 3) would do afterwards).  One launch.
-    int confine_pass(const char* who, double eps)
+    // heat (driver/heat.h) lends the pool NHEAT more arrays, pool_stride elements apart in `chunk`, which stays heat's: the
+    // temperature and its pre-solve snapshot take them
+    void pool_extend(T* chunk)
     {
-        if (S->comm.active()) return fail(FS_EINVAL, "%s: vorticity confinement needs a single GPU handle (its stencil reaches two planes into the other slabs)", who);
-        int rc = ensure_flags();
-        if (rc) return rc;
-        const int V[3] = { FS_VX, FS_VY, FS_VZ };
-        for (int f : V)
-            if ((rc = unalias(f))) return rc;
-        int res[3] = { -1, -1, -1 };
-        for (int k = 0; k < 3; ++k)
-            if ((res[k] = acquire()) < 0) {
-                for (int j = 0; j < k; ++j) held[res[j]] = false;
-                return fail(FS_ENOMEM, "array pool exhausted");
-            }
-        const double k = (double)S->dt * eps;
-        {
-            ScopedSpan sp(S, FAM_CONFINE);
-            fs::launch_confine<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], flags, arr[res[0]], arr[res[1]],
-                                  arr[res[2]], k);
-        }
-        for (int a = 0; a < 3; ++a) adopt(V[a], res[a]);
-        ++S->n_confine;
-        return FS_OK;
-    }
-    int confine_vorticity(double eps) override
-    {
-        if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(FS_EINVAL, "fs_confine_vorticity: epsilon must be finite and >= 0");
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_confine_vorticity: vorticity confinement needs a single GPU handle");
-        if (eps == 0.0) return FS_OK;
-        if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
-        return confine_pass("fs_confine_vorticity", eps);
-    }
-
-    // ---- heat and buoyancy (heat.h; beyond the reference) ------------------------------------------------
-    // The temperature and its pre-solve snapshot are slots F_THETA / F_THETA_PREV of the slot table, behind the public
-    // fields, and two more arrays of the pool: allocated when heat is switched on, freed when it is switched off.
-    bool heat_on() const { return heat_chunk != nullptr; }
-    int heat_alloc()
-    {
-        if (heat_chunk) return FS_OK;
-        T* chunk = nullptr;
-        hipError_t e = hipMalloc((void**)&chunk, (size_t)NHEAT * pool_stride * sizeof(T));
-        if (e != hipSuccess) return fail(FS_ENOMEM, "fs_heat_params: the temperature arrays: %s", hipGetErrorString(e));
-        if ((e = hipMemsetAsync(chunk, 0, (size_t)NHEAT * pool_stride * sizeof(T), S->stream)) != hipSuccess) {
-            hipFree(chunk);
-            return fail(FS_EHIP, "fs_heat_params: clearing the temperature arrays: %s", hipGetErrorString(e));
-        }
-        heat_chunk = chunk;
         for (int k = 0; k < NHEAT; ++k) {
             arr[NPOOL + k] = chunk + (size_t)k * pool_stride + g.lead;
             held[NPOOL + k] = false;
@@ -1760,12 +1191,11 @@ struct Engine : EngineBase {
         npool = NPOOL_MAX;
         slot[F_THETA] = NPOOL;
         slot[F_THETA_PREV] = NPOOL + 1;
-        return FS_OK;
     }
-    // The pool's arrays are interchangeable, so a field may live in one of the two that go: it moves to a free one that stays.
-    int heat_free()
+    // ... and takes them back.  The pool's arrays are interchangeable, so a field may live in one of the two that go: it moves
+    // to a free one that stays.  Synchronises: queued work may still use what the caller frees next.
+    int pool_shrink()
     {
-        if (!heat_chunk) return FS_OK;
         slot[F_THETA] = slot[F_THETA_PREV] = -1;
         for (int id = NPOOL; id < NPOOL_MAX; ++id) {
             if (!referenced(id)) continue;
@@ -1777,235 +1207,14 @@ struct Engine : EngineBase {
             for (int f = 0; f < FS_NFIELDS; ++f)
                 if (slot[f] == id) slot[f] = to;
         }
-        HIP_TRY(hipStreamSynchronize(S->stream));        // queued work may still use what is freed here
-        HIP_TRY(hipFree(heat_chunk));
-        heat_chunk = nullptr;
+        HIP_TRY(hipStreamSynchronize(S->stream));
         for (int k = 0; k < NHEAT; ++k) arr[NPOOL + k] = nullptr;
         npool = NPOOL;
-        if (heat_ws) HIP_TRY(hipFree(heat_ws));
-        heat_ws = nullptr;
-        return FS_OK;
-    }
-    // fs_heat_params with values the entry has checked: the arrays and the log first, then the values
-    int heat_config(const double* par) override
-    {
-        const int mode = (int)par[fs::HP_MODE], log = mode ? (int)par[fs::HP_LOG] : 0;
-        if (mode != 0 && S->comm.active()) return fail(FS_EINVAL, "fs_heat_params: heat needs a single GPU handle (it is not exchanged between slabs)");
-        int rc = mode ? heat_alloc() : heat_free();
-        if (rc) return rc;
-        if (log != heat_ring.at.cap) {
-            if (log > 0 && !heat_ws) HIP_TRY(hipMalloc((void**)&heat_ws, fs::heat_workspace_doubles(g) * sizeof(double)));
-            HIP_TRY(heat_ring.setup(S->stream, 0, log, (size_t)fs::HEAT_COLS * sizeof(double)));
-        }
-        for (int k = 0; k < fs::HEAT_PARAMS; ++k) S->heat[k] = par[k];
-        return FS_OK;
-    }
-    fs::HeatPass heat_pass_params() const
-    {
-        fs::HeatPass p;
-        p.beta = S->heat[fs::HP_BETA];
-        p.alpha = S->heat[fs::HP_ALPHA];
-        p.dt = (double)S->dt;
-        p.inlet = S->heat[fs::HP_INLET];
-        p.wall_t = S->heat[fs::HP_WALL_T];
-        p.up = (int)S->heat[fs::HP_UP];
-        p.wall = (int)S->heat[fs::HP_WALL];
-        for (int k = 0; k < 6; ++k) p.box[k] = (int)S->heat[fs::HP_X0 + k];
-        return p;
-    }
-    int heat_need(const char* who)
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "%s: heat needs a single GPU handle (it is not exchanged between slabs)", who);
-        if (!heat_on()) return fail(FS_EINVAL, "%s: heat is off (fs_heat_params, mode 1 or 2)", who);
-        return FS_OK;
-    }
-    // Pass A: inlet and wall temperatures, buoyancy on the component along `up`, in place.  One launch.
-    int heat_apply_pass(const char* who)
-    {
-        int rc = heat_need(who);
-        if (rc) return rc;
-        if ((rc = ensure_flags())) return rc;
-        const fs::HeatPass p = heat_pass_params();
-        const bool force = p.beta != 0.0 || p.alpha != 0.0;
-        const int up = FS_VX + (p.up >> 1);
-        if ((rc = unalias(F_THETA))) return rc;
-        if (force && (rc = unalias(up))) return rc;
-        {
-            ScopedSpan sp(S, FAM_HEAT);
-            fs::launch_heat_apply<T>(S->stream, g, p, arr[slot[F_THETA]], force ? arr[slot[up]] : nullptr,
-                                     force ? arr[slot[FS_DENS]] : nullptr, flags);
-        }
-        ++S->n_heat_apply;
-        return FS_OK;
-    }
-    // Pass B: the reference's diffusion and advection of a scalar, on the temperature (no new kernel)
-    int heat_transport_pass(const char* who)
-    {
-        int rc = heat_need(who);
-        if (rc) return rc;
-        if ((rc = ensure_flags())) return rc;
-        // dt * kappa * width * height * depth, left to right like diffusion_a()
-        const T a = (T)S->dt * (T)S->heat[fs::HP_KAPPA] * (T)S->W * (T)S->H * (T)S->D;
-        const T c = (T)1 + (T)6 * a;
-        if (S->solver == FS_SOLVER_GS_LEX || S->acc <= 0) {
-            if ((rc = unalias(F_THETA)) || (rc = unalias(F_THETA_PREV))) return rc;
-            ScopedSpan sp(S, FAM_MISC);
-            fs::launch_copy<T>(S->stream, g, arr[slot[F_THETA]], arr[slot[F_THETA_PREV]]);
-        } else {
-            slot[F_THETA_PREV] = slot[F_THETA];          // Jacobi never writes its input: the snapshot is an alias
-        }
-        int res;
-        if ((rc = solve(0, slot[F_THETA], slot[F_THETA_PREV], a, c, S->acc, &res))) return rc;
-        adopt(F_THETA_PREV, res);                        // the solved array: what the advection carries
-        if ((rc = advect(0, F_THETA, F_THETA_PREV))) return rc;
-        ++S->n_heat_transport;
-        return FS_OK;
-    }
-    int heat_apply() override
-    {
-        if (!in_step) vzmax_prev = -1.0;
-        return heat_apply_pass("fs_heat_apply");
-    }
-    int heat_transport() override { return heat_transport_pass("fs_heat_transport"); }
-
-    // Pass C: the heat budget of the state as it is now into `result` (a ring slot or the workspace's result slot)
-    void heat_budget_launch(double* result)
-    {
-        ScopedSpan sp(S, FAM_HEAT, 3);
-        fs::launch_heat_budget<T>(S->stream, g, heat_pass_params(), arr[slot[F_THETA]], arr[slot[FS_VX]], flags, heat_ws, result);
-    }
-    int heat_budget(double* out, double* per_plane) override
-    {
-        int rc = heat_need("fs_heat_budget");
-        if (rc) return rc;
-        if ((rc = ensure_flags())) return rc;
-        const size_t total = fs::heat_workspace_doubles(g), planes = fs::heat_planes_offset(g);
-        if (!heat_ws) HIP_TRY(hipMalloc((void**)&heat_ws, total * sizeof(double)));
-        heat_budget_launch(heat_ws + (total - fs::HEAT_COLS));
-        std::vector<double> host(total - planes);        // the plane records, then the result
-        HIP_TRY(hipMemcpyAsync(host.data(), heat_ws + planes, host.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        memcpy(out, host.data() + (size_t)g.D * fs::HEAT_COLS, fs::HEAT_COLS * sizeof(double));
-        if (per_plane) memcpy(per_plane, host.data(), (size_t)g.D * fs::HEAT_COLS * sizeof(double));
-        return FS_OK;
-    }
-    int heat_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_heat_log: heat needs a single GPU handle");
-        const long n = heat_ring.at.retained();
-        int rc = heat_ring.fetch_begin({"fs_heat_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        std::vector<double> mine((size_t)n * fs::HEAT_COLS);
-        HIP_TRY(heat_ring.fetch_copy(S->stream, mine.data()));
-        for (long i = 0; i < n; ++i) {
-            double* o = rows + (size_t)i * FS_HEAT_LOG_COLS;
-            o[0] = (double)heat_ring.at.step_of(i);
-            memcpy(o + 1, &mine[(size_t)i * fs::HEAT_COLS], fs::HEAT_COLS * sizeof(double));
-        }
-        heat_ring.fetch_end();
-        return FS_OK;
-    }
-    int heat_get(void* dst, size_t n, int elem) override
-    {
-        int rc = heat_need("fs_heat_get");
-        if (rc) return rc;
-        return get_field(F_THETA, dst, n, elem);
-    }
-    int heat_set(const void* src, size_t n, int elem) override
-    {
-        int rc = heat_need("fs_heat_set");
-        if (rc) return rc;
-        return set_field(F_THETA, src, n, elem);
-    }
-
-    // ---- turbulent inflow (inflow.h; beyond the reference) -----------------------------------------------
-    // the parameters as they stand; FS_EINVAL where they do not make a finite amplitude or step t is out of range
-    int inflow_params(const char* who, long t, fs::InflowParams* p) const
-    {
-        p->seed = S->inflow_seed;
-        p->n = S->inflow_n;
-        p->h = g.H;
-        p->d = g.D;
-        p->sigma = S->inflow_sigma;
-        p->convect = S->inflow_convect_now();
-        p->amp = fs::inflow_amplitude(p->n, p->h, p->d, p->sigma, S->inflow_rms);
-        if (!std::isfinite(p->amp)) return fail(FS_EINVAL, "%s: the eddies' amplitude u_rms * sqrt(V / (N sigma^3)) is not finite", who);
-        if (!std::isfinite(p->convect) || !(p->convect >= 0.0)) return fail(FS_EINVAL, "%s: the convection dt * width * speed is negative or not finite", who);
-        if (!fs::inflow_step_ok(t, p->sigma, p->convect)) return fail(FS_EINVAL, "%s: step %ld is negative or beyond 2^53 eddy generations", who, t);
-        return FS_OK;
-    }
-    // the maps on the device as fs_inflow_profile last left them, and room in the table for the eddies
-    int ensure_inflow()
-    {
-        if (inflow_up_gen != S->inflow_gen) {
-            const size_t bytes = (size_t)g.H * (size_t)g.D * sizeof(double);
-            const std::vector<double>* host[2] = { &S->inflow_mean, &S->inflow_scale };
-            double** dev[2] = { &inflow_dmean, &inflow_dscale };
-            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued plane may still read the old maps
-            for (int k = 0; k < 2; ++k) {
-                if (host[k]->empty()) {
-                    if (*dev[k]) HIP_TRY(hipFree(*dev[k]));
-                    *dev[k] = nullptr;
-                    continue;
-                }
-                if (!*dev[k]) HIP_TRY(hipMalloc((void**)dev[k], bytes));
-                HIP_TRY(hipMemcpy(*dev[k], host[k]->data(), bytes, hipMemcpyHostToDevice));
-            }
-            inflow_up_gen = S->inflow_gen;
-        }
-        if (S->inflow_n > inflow_cap) {
-            HIP_TRY(hipStreamSynchronize(S->stream));
-            if (inflow_tab) HIP_TRY(hipFree(inflow_tab));
-            inflow_tab = nullptr;
-            inflow_cap = 0;
-            HIP_TRY(hipMalloc((void**)&inflow_tab, (size_t)S->inflow_n * sizeof(fs::InflowEntry)));
-            inflow_cap = S->inflow_n;
-        }
-        return FS_OK;
-    }
-    // the plane of step t: into the three velocities' x = 1 face, or (out not null) as 3 x d x h doubles into out
-    void inflow_launch(const fs::InflowParams& p, long t, double* out)
-    {
-        const double gust = fs::inflow_gust(S->gust_t.data(), S->gust_f.data(), (int)S->gust_t.size(), t);
-        ScopedSpan sp(S, FAM_INFLOW);
-        fs::launch_inflow_table(S->stream, p, t, inflow_tab, nullptr);
-        fs::launch_inflow_plane<T>(S->stream, g, p, inflow_tab, gust, (double)S->speed, inflow_dmean, inflow_dscale, arr[slot[FS_VX]],
-                                   arr[slot[FS_VY]], arr[slot[FS_VZ]], out);
-    }
-    int inflow_plane(long t, double* out) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_inflow_plane: the inflow generator needs a single-GPU handle");
-        fs::InflowParams p;
-        int rc = inflow_params("fs_inflow_plane", t, &p);
-        if (rc) return rc;
-        if ((rc = ensure_inflow())) return rc;
-        const size_t bytes = (size_t)3 * g.H * g.D * sizeof(double);
-        if (!inflow_out) HIP_TRY(hipMalloc((void**)&inflow_out, bytes));
-        inflow_launch(p, t, inflow_out);
-        HIP_TRY(hipMemcpyAsync(out, inflow_out, bytes, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-    int inflow_eddies(long t, double* out) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_inflow_eddies: the inflow generator needs a single-GPU handle");
-        fs::InflowParams p;
-        int rc = inflow_params("fs_inflow_eddies", t, &p);
-        if (rc) return rc;
-        if (p.n <= 0) return FS_OK;
-        const size_t bytes = (size_t)fs::INFLOW_EDDIES_MAX * 6 * sizeof(double);
-        if (!inflow_dbg) HIP_TRY(hipMalloc((void**)&inflow_dbg, bytes));
-        {
-            ScopedSpan sp(S, FAM_INFLOW);
-            fs::launch_inflow_table(S->stream, p, t, nullptr, inflow_dbg);
-        }
-        HIP_TRY(hipMemcpyAsync(out, inflow_dbg, (size_t)p.n * 6 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
         return FS_OK;
     }
 
     // ---- step (simulation.cpp:96-150) ---------------------------------------------------
-    int step() override
+    int step()
     {
         struct InStep {                                  // the reach bookkeeping of this step; cleared on every exit
             Engine* e;
@@ -2014,32 +1223,32 @@ struct Engine : EngineBase {
         } scope(this);
         int rc = ensure_flags();
         if (rc) return rc;
-        if ((rc = ensure_force_ring())) return rc;
-        if ((rc = ensure_residual_ring())) return rc;
-        if ((rc = flow_stats_config())) return rc;
-        if ((rc = ensure_probe_ring())) return rc;
-        if ((rc = ensure_body_ring())) return rc;
-        if ((rc = ensure_image_ring())) return rc;
-        if ((rc = ensure_volume_ring())) return rc;
-        if ((rc = ensure_tracers())) return rc;
-        if ((rc = ensure_monitor_ring())) return rc;
+        if ((rc = forces.ensure_ring())) return rc;
+        if ((rc = residual.ensure_ring())) return rc;
+        if ((rc = flow_stats.config())) return rc;
+        if ((rc = sampling.ensure_probe_ring())) return rc;
+        if ((rc = bodies.ensure_ring())) return rc;
+        if ((rc = images.ensure_ring())) return rc;
+        if ((rc = volume.ensure_ring())) return rc;
+        if ((rc = tracers.ensure())) return rc;
+        if ((rc = monitor.ensure_ring())) return rc;
         fs::InflowParams inflow_p;
         if (S->inflow) {
             if (S->comm.active()) return fail(FS_EINVAL, "fs_step: the inflow generator (option \"inflow\") needs a single-GPU handle");
-            if ((rc = inflow_params("fs_step", S->steps_total, &inflow_p))) return rc;
-            if ((rc = ensure_inflow())) return rc;
+            if ((rc = inflow.params("fs_step", S->steps_total, &inflow_p))) return rc;
+            if ((rc = inflow.ensure())) return rc;
         }
-        res_ran_now = 0;
+        residual.begin_step();
         // "vorticity_confinement": the pass comes before everything the reference's step does
-        if (S->confinement > 0.0 && (rc = confine_pass("fs_step", S->confinement))) return rc;
+        if (S->confinement > 0.0 && (rc = confine.pass("fs_step", S->confinement))) return rc;
         // heat, mode 2: inlet and wall temperatures and the buoyancy force come next, still before the reference's step
         const bool heat_step = S->heat_mode() == 2;
-        if (heat_step && (rc = heat_apply_pass("fs_step"))) return rc;
+        if (heat_step && (rc = heat.apply_pass("fs_step"))) return rc;
         const bool gs = (S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
         if (S->inflow) {                                 // "inflow": the face from the inflow generator, at step number steps_total
-            inflow_launch(inflow_p, S->steps_total, nullptr);
+            inflow.launch(inflow_p, S->steps_total, nullptr);
             ++S->n_inflow;
         } else {
             ScopedSpan sp(S, FAM_MISC);
@@ -2077,7 +1286,7 @@ struct Engine : EngineBase {
         SolveRun dens_run;
         if (split) {
             const T a = diffusion_a();
-            if ((rc = log_residual(5, 0, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
+            if ((rc = residual.log(5, 0, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
             if ((rc = solve_begin(dens_run, 0, slot[FS_DENS], slot[FS_BUFFER], a, (T)1 + (T)6 * a, S->acc))) return rc;   // :283
             if ((rc = solve_passes(dens_run, (int)dens_run.plan.size() / 2))) return rc;
             HIP_TRY(hipEventRecord(ev_slack, S->stream));
@@ -2104,46 +1313,42 @@ struct Engine : EngineBase {
             if ((rc = solve_end(dens_run, &res))) return rc;
             adopt(FS_DENS, res);
             const T a = diffusion_a();
-            if ((rc = log_residual(5, 1, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
+            if ((rc = residual.log(5, 1, 0, slot[FS_DENS], slot[FS_BUFFER], (double)a, (double)((T)1 + (T)6 * a)))) return rc;
             HIP_TRY(hipEventRecord(ev_slack, S->stream));
         } else if (!S->elide_dead) {                     // :135 (its result is overwritten by :136)
             if ((rc = diffuse_T(0, FS_DENS, FS_BUFFER, 5))) return rc;
         }
         if ((rc = advect(0, FS_DENS, FS_BUFFER))) return rc;   // :136
         slack_check();
-        if (heat_step && (rc = heat_transport_pass("fs_step"))) return rc;   // the temperature is diffused and carried last
+        if (heat_step && (rc = heat.transport_pass("fs_step"))) return rc;   // the temperature is diffused and carried last
         S->step_no++;
         S->steps_total++;
-        if (force_ring.on()) force_ring.at.commit(S->steps_total);
-        if (body_ring.on()) body_ring.at.commit(S->steps_total);
-        if (res_ring.on()) res_ring.at.commit(S->steps_total, res_ran_now);
+        forces.commit();
+        bodies.commit();
+        residual.commit();
         // the heat log: the budget of the state the transport left (three launches, no host synchronisation, the step's own stream)
-        if (heat_step && heat_ring.on()) {
-            heat_budget_launch((double*)heat_ring.slot(heat_ring.at.next()));
-            heat_ring.at.commit(S->steps_total);
-        }
+        if (heat_step) heat.record();
         // "flow_stats": the state as :136 left it is a sample (no host synchronisation, the step's own stream)
-        if (stat_nacc > 0 && S->steps_total > S->flow_stats_start &&
-            (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats_sample()))
+        if (flow_stats.on() && S->steps_total > S->flow_stats_start &&
+            (S->steps_total - S->flow_stats_start - 1) % S->flow_stats_every == 0 && (rc = flow_stats.sample()))
             return rc;
         // "monitor_log": the same state is a record of the flow monitor (three launches, no host synchronisation, the step's own stream)
-        if (mon_ring.on() && (S->steps_total - 1) % S->monitor_every == 0) monitor_record();
+        if (monitor.on() && (S->steps_total - 1) % S->monitor_every == 0) monitor.record();
         // "probe_log": the same state is a record of the probes (one launch, no host synchronisation, the step's own stream)
-        if (probe_ring.on()) probe_record();
+        sampling.probe_step();
         // "image_log": and a frame of the image views (the kernels of each view, no host synchronisation, the step's own stream)
-        if (img_ring.on() && (S->steps_total - 1) % S->image_every == 0 && (rc = image_record())) return rc;
+        if (images.on() && (S->steps_total - 1) % S->image_every == 0 && (rc = images.record())) return rc;
         // "volume_log": and a frame of the volume views (one launch per view, no host synchronisation, the step's own stream)
-        if (vol_ring.on() && (S->steps_total - 1) % S->volume_every == 0 && (rc = volume_record())) return rc;
+        if (volume.on() && (S->steps_total - 1) % S->volume_every == 0 && (rc = volume.record())) return rc;
         // "tracers": the particles move through the same state, the emitters release, a snapshot is taken (one launch, no host
         // synchronisation, the step's own stream)
-        if (tr_cap > 0)
-            tracer_pass((S->steps_total - 1) % S->tracer_emit_every == 0, (S->steps_total - 1) % S->tracer_every == 0);
+        tracers.step();
         if (S->in_run && S->dump_every > 0 && (S->step_no % S->dump_every) == 0) return dump_frame();   // :140-148
         return FS_OK;
     }
 
     // one iteration of Simulation::run()'s loop (simulation.cpp:63-71)
-    int run_one() override
+    int run_one()
     {
         int rc = ensure_halos();
         if (rc) return rc;
@@ -2163,7 +1368,7 @@ struct Engine : EngineBase {
     }
 
     // ---- data access ----------------------------------------------------------------
-    int get_field(int which, void* dst, size_t n, int elem) override
+    int get_field(int which, void* dst, size_t n, int elem)
     {
         if ((long)n != dense_cells()) return fail(FS_EINVAL, "get_field: expected %ld elements, got %zu", dense_cells(), n);
         const T* f = arr[slot[which]];
@@ -2172,16 +1377,16 @@ struct Engine : EngineBase {
             int rc = need_dense(n * (size_t)elem);
             if (rc) return rc;
         }
-        if (elem == 4) fs::launch_pack<T, float>(S->stream, g, f, (float*)dense, 0, g.D + 1);
-        else if (elem == 8) fs::launch_pack<T, double>(S->stream, g, f, (double*)dense, 0, g.D + 1);
-        else if (elem == 1) fs::launch_pack<T, uint8_t>(S->stream, g, f, (uint8_t*)dense, 0, g.D + 1);
+        if (elem == 4) fs::launch_pack<T, float>(S->stream, g, f, (float*)dense.get(), 0, g.D + 1);
+        else if (elem == 8) fs::launch_pack<T, double>(S->stream, g, f, (double*)dense.get(), 0, g.D + 1);
+        else if (elem == 1) fs::launch_pack<T, uint8_t>(S->stream, g, f, (uint8_t*)dense.get(), 0, g.D + 1);
         else return fail(FS_EINVAL, "elem_size must be 1, 4 or 8");
-        HIP_TRY(hipMemcpyAsync(dst, dense, n * elem, hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipMemcpyAsync(dst, dense.get(), n * elem, hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
         return FS_OK;
     }
 
-    int set_field(int which, const void* src, size_t n, int elem) override
+    int set_field(int which, const void* src, size_t n, int elem)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         if ((long)n != dense_cells()) return fail(FS_EINVAL, "set_field: expected %ld elements, got %zu", dense_cells(), n);
@@ -2196,20 +1401,20 @@ struct Engine : EngineBase {
             int rc = need_dense(n * (size_t)elem);
             if (rc) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(dense, src, n * elem, hipMemcpyHostToDevice, S->stream));
+        HIP_TRY(hipMemcpyAsync(dense.get(), src, n * elem, hipMemcpyHostToDevice, S->stream));
         T* f = arr[slot[which]];
-        if (elem == 4) fs::launch_unpack<T, float>(S->stream, g, (const float*)dense, f, 0, g.D + 1);
-        else if (elem == 8) fs::launch_unpack<T, double>(S->stream, g, (const double*)dense, f, 0, g.D + 1);
-        else fs::launch_unpack<T, uint8_t>(S->stream, g, (const uint8_t*)dense, f, 0, g.D + 1);
+        if (elem == 4) fs::launch_unpack<T, float>(S->stream, g, (const float*)dense.get(), f, 0, g.D + 1);
+        else if (elem == 8) fs::launch_unpack<T, double>(S->stream, g, (const double*)dense.get(), f, 0, g.D + 1);
+        else fs::launch_unpack<T, uint8_t>(S->stream, g, (const uint8_t*)dense.get(), f, 0, g.D + 1);
         HIP_TRY(hipStreamSynchronize(S->stream));       // `src` may be freed by the caller
         if (which == FS_OBS) flags_dirty = true;
         else halos_dirty = true;
         return FS_OK;
     }
 
-    int set_mask(const uint8_t* mask, size_t n) override { return set_field(FS_OBS, mask, n, 1); }
+    int set_mask(const uint8_t* mask, size_t n) { return set_field(FS_OBS, mask, n, 1); }
 
-    int point(int which, int x, int y, int z, float v, int set_instead) override
+    int point(int which, int x, int y, int z, float v, int set_instead)
     {
         if (!in_step) vzmax_prev = -1.0;             // a call from outside step(): what is known about v_z is void
         // x,y are global = local; z is global and must fall into this slab to have an effect.
@@ -2227,287 +1432,11 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int tuned_two() const override { return plan_two; }
-    int halo_depth() const override { return g.zh; }
-    int tuned_three() const override { return plan_three; }
+    int tuned_two() const { return plan_two; }
+    int halo_depth() const { return g.zh; }
+    int tuned_three() const { return plan_three; }
 
-    // ---- the viewer's streamlines (GUI/utils.py:118-213) -------------------------------------
-    // The device integrates every seed in both directions; what is left for the host is the
-    // reference's bookkeeping per seed: joining the two parts and the three filters.
-    int streamlines(int density, double proximity, int max_length, double step_size, double threshold) override
-    {
-        S->sl_offsets.assign(1, 0);
-        S->sl_points.clear();
-        S->sl_norm.clear();
-        if (S->comm.active()) return fail(FS_EINVAL, "streamlines are computed on a single-GPU handle");
-        if (density < 0 || max_length < 0) return fail(FS_EINVAL, "density and max_length must be >= 0");
-        if (density > 4096 || max_length > 1000000) return fail(FS_EINVAL, "density <= 4096 and max_length <= 1e6, please");
-        if (!(step_size == step_size) || !(proximity == proximity) || !(threshold == threshold))
-            return fail(FS_EINVAL, "streamline parameters must not be NaN");
-        const T* obs = arr[slot[FS_OBS]];
-        fs::StreamParams p;
-        p.nx = density; p.ny = density / 2; p.nz = density / 2;          // utils.py:136-138
-        p.half = max_length / 2;
-        p.step_size = step_size;
-        const int dims[3] = { g.W + 2, g.H + 2, g.D + 2 };               // config.width/height/depth
-        for (int k = 0; k < 3; ++k) {
-            p.clip_hi[k] = (double)dims[k] - 1.001;
-            p.bound_hi[k] = (double)(dims[k] - 1);
-        }
-        int* d_box = nullptr;
-        int box[6];
-        HIP_TRY(hipMalloc((void**)&d_box, sizeof box));
-        fs::launch_obs_bbox<T>(S->stream, g, obs, d_box);
-        HIP_TRY(hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        hipFree(d_box);
-        if (box[0] > box[3]) return FS_OK;                               // no obstacles: no streamlines (:134-135)
-        for (int k = 0; k < 3; ++k) {
-            p.lo[k] = (double)box[k] - proximity / 10;
-            p.hi[k] = (double)box[3 + k] + proximity / 10;
-        }
-        const long nseed = (long)p.nx * p.ny * p.nz;
-        if (nseed == 0) return FS_OK;
-        // np.linspace(1, dim - 2, n): arange(n) * step + start, last element = stop
-        std::vector<double> seeds((size_t)p.nx + p.ny + p.nz);
-        {
-            const int cnt[3] = { p.nx, p.ny, p.nz };
-            size_t o = 0;
-            for (int k = 0; k < 3; ++k) {
-                const double start = 1.0, stop = (double)(dims[k] - 2);
-                const int n = cnt[k];
-                const double step = n > 1 ? (stop - start) / (double)(n - 1) : 0.0;
-                for (int i = 0; i < n; ++i) seeds[o + i] = (double)i * step + start;
-                if (n > 1) seeds[o + n - 1] = stop;
-                o += n;
-            }
-        }
-        // utils.py:147-150: seeds outside the widened bounding box are skipped before anything else
-        std::vector<int> cand;
-        for (int iz = 0; iz < p.nz; ++iz)
-            for (int iy = 0; iy < p.ny; ++iy)
-                for (int ix = 0; ix < p.nx; ++ix) {
-                    const double sx = seeds[ix], sy = seeds[p.nx + iy], sz = seeds[(size_t)p.nx + p.ny + iz];
-                    if (sx < p.lo[0] || sx > p.hi[0] || sy < p.lo[1] || sy > p.hi[1] || sz < p.lo[2] || sz > p.hi[2]) continue;
-                    cand.push_back((iz * p.ny + iy) * p.nx + ix);
-                }
-        const long ncand = (long)cand.size();
-        if (ncand == 0) return FS_OK;
-        const size_t per = (size_t)(p.half + 1) * 3, npts = (size_t)ncand * 2 * per;
-        if (npts > ((size_t)1 << 29))                    // 2 x 4 GiB of points and velocities: split the call instead
-            return fail(FS_ENOMEM, "%ld seeds x %d steps is more than one call should integrate; lower density or max_length", ncand, max_length);
-        double *d_seeds = nullptr, *d_pts = nullptr, *d_vel = nullptr;
-        int *d_count = nullptr, *d_cand = nullptr, *d_nan = nullptr;
-        int rc = FS_OK, any_nan = 0;
-        std::vector<double> pts, vel;
-        std::vector<int> count((size_t)ncand * 2);
-        double mx[3][3];
-        do {
-            if (hipMalloc((void**)&d_seeds, seeds.size() * 8) != hipSuccess || hipMalloc((void**)&d_pts, npts * 8) != hipSuccess ||
-                hipMalloc((void**)&d_vel, npts * 8) != hipSuccess || hipMalloc((void**)&d_count, count.size() * 4) != hipSuccess ||
-                hipMalloc((void**)&d_cand, cand.size() * 4) != hipSuccess || hipMalloc((void**)&d_nan, 4) != hipSuccess) {
-                rc = fail(FS_ENOMEM, "streamline buffers");
-                break;
-            }
-            pts.resize(npts);
-            vel.resize(npts);
-            if (hipMemcpyAsync(d_seeds, seeds.data(), seeds.size() * 8, hipMemcpyHostToDevice, S->stream) != hipSuccess ||
-                hipMemcpyAsync(d_cand, cand.data(), cand.size() * 4, hipMemcpyHostToDevice, S->stream) != hipSuccess) { rc = fail(FS_EHIP, "seed upload"); break; }
-            fs::launch_streamlines<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], obs, p, d_seeds, d_cand,
-                                      (int)ncand, d_count, d_pts, d_vel);
-            if (hipMemsetAsync(d_nan, 0, 4, S->stream) != hipSuccess) { rc = fail(FS_EHIP, "streamline flag"); break; }
-            fs::launch_any_nan<T>(S->stream, g, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], d_nan);
-            if (hipMemcpyAsync(count.data(), d_count, count.size() * 4, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
-                hipMemcpyAsync(&any_nan, d_nan, 4, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
-                hipMemcpyAsync(pts.data(), d_pts, npts * 8, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
-                hipMemcpyAsync(vel.data(), d_vel, npts * 8, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
-                hipStreamSynchronize(S->stream) != hipSuccess) { rc = fail(FS_EHIP, "streamline kernel or copy failed"); break; }
-            for (int k = 0; k < 3; ++k)
-                if ((rc = stats_of(arr[slot[FS_VX + k]], mx[k]))) break;
-        } while (0);
-        hipFree(d_seeds); hipFree(d_pts); hipFree(d_vel); hipFree(d_count); hipFree(d_cand); hipFree(d_nan);
-        if (rc) return rc;
-        // np.max([vx, vy, vz]) + 1e-6 in the arrays' own precision (float32 for the reference's dumps).  np.max is NaN
-        // if any cell is; the maximum of the field statistics skips NaN (the reference's own loop), hence the flag.
-        const T vmax = (T)std::fmax(std::fmax(mx[0][2], mx[1][2]), mx[2][2]);
-        const double denom = any_nan ? std::numeric_limits<double>::quiet_NaN() : (double)(T)(vmax + (T)1e-6);
-        auto norm3 = [](double a, double b, double c) { return std::sqrt((a * a + b * b) + c * c); };
-        std::vector<double> line, lvel;
-        for (long sd = 0; sd < ncand; ++sd) {
-            const int nb = count[2 * sd], nf = count[2 * sd + 1];
-            if (nb == 0) continue;                                       // seed inside an obstacle
-            const double* B = &pts[(size_t)(2 * sd) * per], *F = &pts[(size_t)(2 * sd + 1) * per];
-            const double* VB = &vel[(size_t)(2 * sd) * per], *VF = &vel[(size_t)(2 * sd + 1) * per];
-            line.clear();
-            lvel.clear();
-            for (int i = nb - 1; i >= 1; --i)                            // backward[::-1][:-1]  (:167-168)
-                for (int c = 0; c < 3; ++c) { line.push_back(B[3 * i + c]); lvel.push_back(VB[3 * i + c]); }
-            for (int i = 0; i < nf; ++i)
-                for (int c = 0; c < 3; ++c) { line.push_back(F[3 * i + c]); lvel.push_back(VF[3 * i + c]); }
-            const int n = (int)(line.size() / 3);
-            if (n <= 5) continue;                                        // :171-172
-            double max_change = 0.0;                                     // :175-181
-            for (int i = 1; i < n; ++i) {
-                const double ch = norm3(lvel[3 * i] - lvel[3 * i - 3], lvel[3 * i + 1] - lvel[3 * i - 2], lvel[3 * i + 2] - lvel[3 * i - 1]);
-                if (ch > max_change) max_change = ch;
-            }
-            if (max_change < threshold) continue;
-            bool near = false;                                           // :184-195, every third point
-            for (int i = 0; i < n && !near; i += 3)
-                near = p.lo[0] <= line[3 * i] && line[3 * i] <= p.hi[0] && p.lo[1] <= line[3 * i + 1] && line[3 * i + 1] <= p.hi[1] &&
-                       p.lo[2] <= line[3 * i + 2] && line[3 * i + 2] <= p.hi[2];
-            if (!near) continue;
-            // :198-205 with Python's max and min: max keeps its first element unless a later one compares greater,
-            // min(r, 1.0) is r unless 1.0 < r -- a NaN ratio stays NaN
-            double max_speed = norm3(lvel[0], lvel[1], lvel[2]);
-            for (int i = 1; i < n; ++i) {
-                const double sp = norm3(lvel[3 * i], lvel[3 * i + 1], lvel[3 * i + 2]);
-                if (sp > max_speed) max_speed = sp;
-            }
-            const double ratio = max_speed / denom;
-            S->sl_norm.push_back(1.0 < ratio ? 1.0 : ratio);
-            S->sl_points.insert(S->sl_points.end(), line.begin(), line.end());
-            S->sl_offsets.push_back((long)(S->sl_points.size() / 3));
-        }
-        return FS_OK;
-    }
-
-    // ---- the viewer's obstacle mesh (GUI/utils.py:10-38) ------------------------------------------
-    // the mesh of `field` > `level` into one of the handle's two result slots
-    int surface_into(const T* field, T level, std::vector<float>& verts, std::vector<int>& tris, bool& valid)
-    {
-        verts.clear();
-        tris.clear();
-        valid = false;
-        fs::SurfaceResult r;
-        const char* msg = "";
-        int rc = fs::extract_surface<T>(S->stream, g, field, level, &r, &msg);
-        if (rc) return fail(rc, "%s", msg);
-        verts.resize((size_t)r.nverts * 3);
-        tris.resize((size_t)r.ntris * 3);
-        hipError_t e = hipSuccess;
-        if (r.nverts > 0) {
-            e = hipMemcpyAsync(verts.data(), r.d_verts, verts.size() * sizeof(float), hipMemcpyDeviceToHost, S->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(tris.data(), r.d_tris, tris.size() * sizeof(int), hipMemcpyDeviceToHost, S->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(S->stream);
-        }
-        fs::surface_free(&r);
-        if (e != hipSuccess) return fail(FS_EHIP, "copying the surface: %s", hipGetErrorString(e));
-        valid = true;
-        return FS_OK;
-    }
-
-    int obstacle_surface() override
-    {
-        S->surf_valid = false;
-        if (S->comm.active()) return fail(FS_EINVAL, "the obstacle surface is extracted on a single-GPU handle");
-        return surface_into(arr[slot[FS_OBS]], (T)0.5, S->surf_verts, S->surf_tris, S->surf_valid);
-    }
-
-    // ---- vortex identification (vortex.h; beyond the reference) and iso-surfaces of any field -------------
-    // the private array the vortex kernel writes, allocated and zeroed at first need
-    int ensure_vort(const char* who)
-    {
-        if (vort) return FS_OK;
-        T* base = nullptr;
-        const hipError_t e = hipMalloc((void**)&base, (size_t)g.n * sizeof(T));
-        if (e != hipSuccess) return fail(FS_ENOMEM, "%s: scratch array of %zu bytes: %s", who, (size_t)g.n * sizeof(T), hipGetErrorString(e));
-        vort = base + g.lead;
-        HIP_TRY(hipMemsetAsync(base, 0, (size_t)g.n * sizeof(T), S->stream));
-        return FS_OK;
-    }
-
-    // One field into `vort`.  Collective on slab handles: the stencil reads one plane of each neighbour.
-    int vortex_compute(const char* who, int which)
-    {
-        if (which < 0 || which >= FS_VORTEX_NFIELDS) return fail(FS_EINVAL, "%s: unknown vortex selector %d (0..%d)", who, which, FS_VORTEX_NFIELDS - 1);
-        if (S->comm.active() && S->comm.null_transport)
-            return fail(FS_EINVAL, "%s: vortex fields need the other slabs' planes; the FSNULL transport carries none", who);
-        int rc = ensure_flags();
-        if (rc) return rc;
-        for (int f : { FS_VX, FS_VY, FS_VZ })
-            if ((rc = halo(arr[slot[f]]))) return rc;
-        if ((rc = ensure_vort(who))) return rc;
-        ScopedSpan sp(S, FAM_VORTEX);
-        fs::launch_vortex<T>(S->stream, S->tune, g, sc, which, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], flags, vort);
-        return FS_OK;
-    }
-
-    int vortex_field(int which, void* dst, size_t n, int elem) override
-    {
-        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_vortex_field: expected %ld elements, got %zu", dense_cells(), n);
-        if (elem != 4 && elem != 8) return fail(FS_EINVAL, "fs_vortex_field: elem_size must be 4 or 8");
-        int rc = vortex_compute("fs_vortex_field", which);
-        if (rc) return rc;
-        if ((rc = need_dense(n * (size_t)elem))) return rc;
-        if (elem == 4) fs::launch_pack<T, float>(S->stream, g, vort, (float*)dense, 0, g.D + 1);
-        else fs::launch_pack<T, double>(S->stream, g, vort, (double*)dense, 0, g.D + 1);
-        HIP_TRY(hipMemcpyAsync(dst, dense, n * elem, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int vortex_dump(const char* dir) override
-    {
-        static const char* const names[FS_VORTEX_NFIELDS] = { "vort_x.bin", "vort_y.bin", "vort_z.bin", "vort_sq.bin", "q.bin" };
-        if (S->comm.active() && S->comm.null_transport)
-            return fail(FS_EINVAL, "fs_vortex_dump: vortex fields need the other slabs' planes; the FSNULL transport carries none");
-        int rc = FS_OK;
-        // rank 0 truncates; the other slab ranks open the files for update once they exist (as fs_flow_stats_dump does)
-        const bool lead = !S->comm.active() || S->comm.rank == 0;
-        FILE* fp[FS_VORTEX_NFIELDS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        bool ok = true;
-        for (int pass = 0; pass < 2; ++pass) {
-            if ((pass == 0) == lead)
-                for (int k = 0; k < FS_VORTEX_NFIELDS; ++k) {
-                    fp[k] = fopen((std::string(dir) + "/" + names[k]).c_str(), lead ? "wb" : "r+b");
-                    if (!fp[k]) ok = false;
-                }
-            if (pass == 0 && S->comm.active()) {
-                if (S->comm.shm && S->comm.shm_ready(g, S->D)) return fail(FS_ECOMM, "%s", S->comm.last_error());
-                if ((rc = slab_barrier())) return rc;
-            }
-        }
-        // local planes written by this rank: its interior planes, plus the physical ghost planes
-        const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
-        const size_t plane = (size_t)(g.W + 2) * (g.H + 2);
-        std::vector<float> h((size_t)dense_cells());
-        for (int k = 0; k < FS_VORTEX_NFIELDS && !rc; ++k) {     // every rank computes all five (collective), whatever its files do
-            rc = vortex_field(k, h.data(), h.size(), 4);
-            if (rc || !ok || !fp[k]) continue;
-            if (fseek(fp[k], (long)(plane * (size_t)(sc.zoff + zlo) * sizeof(float)), SEEK_SET) != 0 ||
-                fwrite(h.data() + plane * (size_t)zlo, sizeof(float), plane * (size_t)(zhi - zlo + 1), fp[k]) != plane * (size_t)(zhi - zlo + 1))
-                ok = false;
-        }
-        for (int k = 0; k < FS_VORTEX_NFIELDS; ++k)
-            if (fp[k] && fclose(fp[k]) != 0) ok = false;
-        if (S->comm.active() && !rc) rc = slab_barrier();     // every rank's planes are in the files
-        if (rc) return rc;
-        if (!ok) return fail(FS_EIO, "fs_vortex_dump: cannot write the vortex frames under '%s'", dir);
-        return FS_OK;
-    }
-
-    int isosurface(int source, double level) override
-    {
-        S->iso_valid = false;
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_isosurface: iso-surfaces are extracted on a single-GPU handle");
-        const T* field = nullptr;
-        if (source >= 0 && source < FS_NFIELDS) {
-            field = arr[slot[source]];
-        } else if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS) {
-            int rc = vortex_compute("fs_isosurface", source & (FS_ISO_VORTEX - 1));
-            if (rc) return rc;
-            field = vort;
-        } else if (source == FS_SOURCE_HEAT) {
-            if (!heat_on()) return fail(FS_EINVAL, "fs_isosurface: FS_SOURCE_HEAT while heat is off (fs_heat_params, mode 1 or 2)");
-            field = arr[slot[F_THETA]];
-        } else {
-            return fail(FS_EINVAL, "fs_isosurface: unknown source %d (a field selector, FS_SOURCE_HEAT, or FS_ISO_VORTEX | FS_VORTEX_*)", source);
-        }
-        return surface_into(field, (T)level, S->iso_verts, S->iso_tris, S->iso_valid);
-    }
-
-    int apply_solid_cells(const int* cells, long n) override
+    int apply_solid_cells(const int* cells, long n)
     {
         // cells: device array of packed global cell ids x + y*(W+2) + z*(W+2)*(H+2)
         int rc = unalias(FS_OBS);
@@ -2517,13 +1446,13 @@ struct Engine : EngineBase {
         return FS_OK;
     }
 
-    int stats(int which, double* out3) override { return stats_of(arr[slot[which]], out3); }
+    int stats(int which, double* out3) { return stats_of(arr[slot[which]], out3); }
 
     // The number Simulation::run() prints every 100 steps: std::reduce(dens.begin(), dens.end()) (simulation.cpp:76),
     // i.e. a sum in the field's own precision in libstdc++'s order -- groups of four as (a0 + a1) + (a2 + a3), added to the
     // running sum one group at a time (<numeric>, random-access branch).  A rounding chain cannot be reordered, so the
     // dense array comes to the host for it (once per 100 steps, console output only).
-    int reference_order_sum(int which, double* out) override
+    int reference_order_sum(int which, double* out)
     {
         const long n = dense_cells();
         std::vector<T> h((size_t)n);
@@ -2546,18 +1475,18 @@ struct Engine : EngineBase {
         // whole padded array (simulation.cpp:76, :82-89); a slab counts its own planes plus
         // the physical ghost planes it holds, and the partial results are all-reduced
         const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
-        fs::launch_stats<T>(S->stream, g, field, red + 3 * 1024, red, 3 * 1024, zlo, zhi);
+        fs::launch_stats<T>(S->stream, g, field, red.get() + 3 * 1024, red.get(), 3 * 1024, zlo, zhi);
         if (S->comm.active()) {
-            int rc = comm_op([&](hipStream_t cs) { return S->comm.reduce_stats(cs, red + 3 * 1024, g, S->D); }, "stats all-reduce");
+            int rc = comm_op([&](hipStream_t cs) { return S->comm.reduce_stats(cs, red.get() + 3 * 1024, g, S->D); }, "stats all-reduce");
             if (rc) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(out3, red + 3 * 1024, 3 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+        HIP_TRY(hipMemcpyAsync(out3, red.get() + 3 * 1024, 3 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
         HIP_TRY(hipStreamSynchronize(S->stream));
         return FS_OK;
     }
 
     // ---- frame dump (simulation.cpp:56-60, 140-148) ---------------------------------------
-    int dump_frame() override
+    int dump_frame()
     {
         static const char* const names[5] = { "data.bin", "obs.bin", "v_x.bin", "v_y.bin", "v_z.bin" };
         static const int which[5] = { FS_DENS, FS_OBS, FS_VX, FS_VY, FS_VZ };
@@ -2614,7 +1543,7 @@ struct Engine : EngineBase {
     }
 
     // ---- measurement ----------------------------------------------------------------
-    int time_sweeps(int b, int field, int prev, float a, float c, int reps, double* ms) override
+    int time_sweeps(int b, int field, int prev, float a, float c, int reps, double* ms)
     {
         int rc = ensure_flags();
         if (rc) return rc;
@@ -2648,1278 +1577,6 @@ struct Engine : EngineBase {
         *ms = (double)t / reps;
         return FS_OK;
     }
-
-    // ---- time-averaged flow statistics (flow_stats.h; beyond the reference) ---------------------------
-    size_t stat_bytes() const { return (size_t)fs::flow_stats_groups(g.sz, g.D) * 4 * sizeof(double); }
-
-    // allocate, free and clear after fs_set_option("flow_stats"); a reset needs no pass over memory (the first sample overwrites)
-    int flow_stats_config() override
-    {
-        if (stat_gen == S->flow_stats_gen) return FS_OK;
-        stat_gen = S->flow_stats_gen;
-        S->flow_stats_n = 0;
-        if (stat_nacc == S->flow_stats) return FS_OK;
-        HIP_TRY(hipStreamSynchronize(S->stream));        // a queued sample may still write what is freed here
-        for (int k = 0; k < stat_nacc; ++k) hipFree(stat_acc.a[k]);
-        stat_acc = fs::FlowStatsAcc{};
-        stat_nacc = 0;
-        for (int k = 0; k < S->flow_stats; ++k) {
-            const hipError_t e = hipMalloc((void**)&stat_acc.a[k], stat_bytes());
-            if (e != hipSuccess) {
-                for (int j = 0; j < k; ++j) hipFree(stat_acc.a[j]);
-                stat_acc = fs::FlowStatsAcc{};
-                const int want = S->flow_stats;
-                S->flow_stats = 0;
-                return fail(FS_ENOMEM, "flow_stats: %d accumulator arrays of %zu bytes: %s (the feature is off now)", want, stat_bytes(),
-                            hipGetErrorString(e));
-            }
-        }
-        stat_nacc = S->flow_stats;
-        return FS_OK;
-    }
-
-    int flow_stats_sample() override
-    {
-        int rc = flow_stats_config();
-        if (rc) return rc;
-        if (stat_nacc == 0) return fail(FS_EINVAL, "fs_flow_stats_sample: option \"flow_stats\" is off");
-        ScopedSpan sp(S, FAM_FLOWSTATS);
-        fs::launch_flow_stats<T>(S->stream, g, stat_nacc, S->flow_stats_n == 0, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]],
-                                 arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], stat_acc);
-        S->flow_stats_n++;
-        return FS_OK;
-    }
-
-    // which: selector without FS_STAT_RAW
-    int flow_stats_check(const char* who, int sel)
-    {
-        const int which = sel & ~FS_STAT_RAW;
-        const bool raw = (sel & FS_STAT_RAW) != 0;
-        if (which < 0 || which > FS_STAT_TKE) return fail(FS_EINVAL, "%s: unknown selector %d", who, sel);
-        if (stat_nacc == 0) return fail(FS_EINVAL, "%s: option \"flow_stats\" is off", who);
-        if (raw && which == FS_STAT_TKE) return fail(FS_EINVAL, "%s: FS_STAT_TKE has no raw sum", who);
-        if (which >= fs::ST_NMEAN && stat_nacc < fs::ST_NMOMENTS)
-            return fail(FS_EINVAL, "%s: selector %d needs \"flow_stats\" = \"moments\" (the mode is \"mean\")", who, which);
-        if (!raw && S->flow_stats_n == 0) return fail(FS_EINVAL, "%s: no samples taken yet (n = 0)", who);
-        return FS_OK;
-    }
-
-    // The derived field goes into the staging buffer in the accumulators' layout, and from there through launch_pack into
-    // the dense layout behind it.
-    int flow_stats_field(int sel, void* dst, size_t n, int elem) override
-    {
-        int rc = flow_stats_config();
-        if (rc) return rc;
-        if ((rc = flow_stats_check("fs_flow_stats_field", sel))) return rc;
-        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_flow_stats_field: expected %ld elements, got %zu", dense_cells(), n);
-        if (elem != 4 && elem != 8) return fail(FS_EINVAL, "elem_size must be 4 or 8");
-        if ((rc = need_dense(stat_bytes() + n * (size_t)elem))) return rc;
-        double* pitched = (double*)dense;
-        void* packed = (char*)dense + stat_bytes();
-        if (S->flow_stats_n == 0) {                      // a raw sum before the first sample: +0.0 (the arrays hold nothing yet)
-            HIP_TRY(hipMemsetAsync(packed, 0, n * (size_t)elem, S->stream));
-        } else {
-            fs::launch_flow_stats_finalize(S->stream, g, stat_acc, sel & ~FS_STAT_RAW, (sel & FS_STAT_RAW) != 0, S->flow_stats_n,
-                                           !sc.lo_wall, !sc.hi_wall, pitched);
-            if (elem == 4) fs::launch_pack<double, float>(S->stream, g, pitched + fs::LEAD, (float*)packed, 0, g.D + 1);
-            else fs::launch_pack<double, double>(S->stream, g, pitched + fs::LEAD, (double*)packed, 0, g.D + 1);
-        }
-        HIP_TRY(hipMemcpyAsync(dst, packed, n * elem, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int flow_stats_dump(const char* dir) override
-    {
-        int rc = flow_stats_config();
-        if (rc) return rc;
-        static const char* const names[7] = { "data.bin", "obs.bin", "v_x.bin", "v_y.bin", "v_z.bin", "p.bin", "tke.bin" };
-        static const int sel[7] = { FS_STAT_MEAN_DENS, -1, FS_STAT_MEAN_VX, FS_STAT_MEAN_VY, FS_STAT_MEAN_VZ, FS_STAT_MEAN_P, FS_STAT_TKE };
-        const int nfiles = stat_nacc >= fs::ST_NMOMENTS ? 7 : 6;
-        if ((rc = flow_stats_check("fs_flow_stats_dump", FS_STAT_MEAN_DENS))) return rc;
-        // rank 0 truncates; the other slab ranks open the files for update once they exist (as dump_frame does)
-        const bool lead = !S->comm.active() || S->comm.rank == 0;
-        FILE* fp[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        bool ok = true;
-        for (int pass = 0; pass < 2; ++pass) {
-            if ((pass == 0) == lead)
-                for (int k = 0; k < nfiles; ++k) {
-                    fp[k] = fopen((std::string(dir) + "/" + names[k]).c_str(), lead ? "wb" : "r+b");
-                    if (!fp[k]) ok = false;
-                }
-            if (pass == 0 && S->comm.active()) {
-                if (S->comm.shm && S->comm.shm_ready(g, S->D)) return fail(FS_ECOMM, "%s", S->comm.last_error());
-                if ((rc = slab_barrier())) return rc;
-            }
-        }
-        // local planes written by this rank: its interior planes, plus the physical ghost planes
-        const int zlo = sc.lo_wall ? 0 : 1, zhi = sc.hi_wall ? g.D + 1 : g.D;
-        const size_t plane = (size_t)(g.W + 2) * (g.H + 2);
-        std::vector<float> h((size_t)dense_cells());
-        for (int k = 0; k < nfiles && ok && !rc; ++k) {
-            rc = sel[k] < 0 ? get_field(FS_OBS, h.data(), h.size(), 4) : flow_stats_field(sel[k], h.data(), h.size(), 4);
-            if (rc) break;
-            if (fseek(fp[k], (long)(plane * (size_t)(sc.zoff + zlo) * sizeof(float)), SEEK_SET) != 0 ||
-                fwrite(h.data() + plane * (size_t)zlo, sizeof(float), plane * (size_t)(zhi - zlo + 1), fp[k]) != plane * (size_t)(zhi - zlo + 1))
-                ok = false;
-        }
-        for (int k = 0; k < nfiles; ++k)
-            if (fp[k] && fclose(fp[k]) != 0) ok = false;
-        if (S->comm.active() && !rc) rc = slab_barrier();     // every rank's planes are in the files
-        if (rc) return rc;
-        if (!ok) return fail(FS_EIO, "fs_flow_stats_dump: cannot write the mean-flow frames under '%s'", dir);
-        return FS_OK;
-    }
-
-    // ---- field sampling and point probes (sample.h; beyond the reference) -------------------------------
-    int sample_points(const double* xyz, long n) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample_points: fields are sampled on a single-GPU handle");
-        if (n > samp_room) {
-            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued sample may still use what is freed here
-            if (samp_pts) hipFree(samp_pts);
-            if (samp_out) hipFree(samp_out);
-            samp_pts = samp_out = nullptr;
-            samp_n = samp_room = 0;
-            hipError_t e = hipMalloc((void**)&samp_pts, (size_t)n * 3 * sizeof(double));
-            if (e == hipSuccess && (e = hipMalloc((void**)&samp_out, (size_t)n * sizeof(double))) != hipSuccess) {
-                hipFree(samp_pts);
-                samp_pts = nullptr;
-            }
-            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_sample_points: %ld points: %s", n, hipGetErrorString(e));
-            samp_room = n;
-        }
-        samp_n = n;
-        if (n > 0) {
-            HIP_TRY(hipMemcpyAsync(samp_pts, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
-            HIP_TRY(hipStreamSynchronize(S->stream));    // `xyz` may be freed by the caller
-        }
-        return FS_OK;
-    }
-
-    // The array behind a source of fs_sample and of the image entries: a field selector (-> field), FS_ISO_VORTEX |
-    // FS_VORTEX_* (the field is computed first, -> field), or FS_SAMPLE_STAT | sel (the derived field goes into the staging
-    // buffer in the accumulators' layout, which is the fields' pitched one, -> stat).  Both are LEAD-shifted.
-    int resolve_source(const char* who, int source, const T*& field, const double*& stat)
-    {
-        int rc;
-        field = nullptr;
-        stat = nullptr;
-        if (source >= 0 && source < FS_NFIELDS) {
-            field = arr[slot[source]];
-        } else if ((source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (source & (FS_ISO_VORTEX - 1)) < FS_VORTEX_NFIELDS) {
-            if ((rc = vortex_compute(who, source & (FS_ISO_VORTEX - 1)))) return rc;
-            field = vort;
-        } else if ((source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT) {
-            const int sel = source & (FS_SAMPLE_STAT - 1);
-            if ((rc = flow_stats_config())) return rc;
-            if ((rc = flow_stats_check(who, sel))) return rc;
-            if ((rc = need_dense(stat_bytes()))) return rc;
-            if (S->flow_stats_n == 0)                    // a raw sum before the first sample: +0.0
-                HIP_TRY(hipMemsetAsync(dense, 0, stat_bytes(), S->stream));
-            else
-                fs::launch_flow_stats_finalize(S->stream, g, stat_acc, sel & ~FS_STAT_RAW, (sel & FS_STAT_RAW) != 0, S->flow_stats_n,
-                                               false, false, (double*)dense);
-            stat = (const double*)dense + fs::LEAD;
-        } else if (source == FS_SOURCE_HEAT) {
-            if (!heat_on()) return fail(FS_EINVAL, "%s: FS_SOURCE_HEAT while heat is off (fs_heat_params, mode 1 or 2)", who);
-            field = arr[slot[F_THETA]];
-        } else {
-            return fail(FS_EINVAL, "%s: unknown source %d (a field selector, FS_SOURCE_HEAT, FS_ISO_VORTEX | FS_VORTEX_* or FS_SAMPLE_STAT | FS_STAT_*)", who, source);
-        }
-        return FS_OK;
-    }
-
-    // `source` in `mode` at the n device points `pts` into the device array `vals`, copied to `out`: fs_sample on the kept
-    // points, fs_tracer_sample on the pool's positions.  The caller has checked n against its point count.
-    int sample_at(const char* who, int source, int mode, const double* pts, double* vals, double* out, long n)
-    {
-        if (mode < 0 || mode >= fs::SAMPLE_NMODES) return fail(FS_EINVAL, "%s: unknown mode %d (FS_SAMPLE_NEAREST | LINEAR | FLUID)", who, mode);
-        const T* field = nullptr;
-        const double* stat = nullptr;
-        int rc = resolve_source(who, source, field, stat);
-        if (rc) return rc;
-        if (n == 0) return FS_OK;
-        if (!out) return fail(FS_EINVAL, "%s: null output", who);
-        const T* obs = arr[slot[FS_OBS]];
-        {
-            ScopedSpan sp(S, FAM_MISC);
-            if (stat) fs::launch_sample<double, T>(S->stream, g, mode, n, pts, stat, obs, vals);
-            else fs::launch_sample<T, T>(S->stream, g, mode, n, pts, field, obs, vals);
-        }
-        HIP_TRY(hipMemcpyAsync(out, vals, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int sample(int source, int mode, double* out, long n) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_sample: fields are sampled on a single-GPU handle");
-        if (n != samp_n) return fail(FS_EINVAL, "fs_sample: %ld points are kept (fs_sample_points), the call has room for %ld", samp_n, n);
-        return sample_at("fs_sample", source, mode, samp_pts, samp_out, out, n);
-    }
-
-    // ---- tracer particles (tracers.h; beyond the reference) ---------------------------------------------
-    // a ring slot is one frame's bytes, but the ring is laid out in two sections: every position frame, then every status frame
-    double* tracer_frame_xyz(long f) const { return (double*)tr_ring.base + (size_t)f * 3 * (size_t)tr_cap; }
-    int* tracer_frame_status(long f) const { return (int*)tracer_frame_xyz(tr_ring.at.cap) + (size_t)f * (size_t)tr_cap; }
-
-    int tracer_config() override { return ensure_tracers(); }
-
-    // (re)allocate and clear the pool after fs_set_option("tracers") and the ring after that or ("tracer_log"); upload the
-    // emitters after fs_tracer_emitters, so that an advance in mid-step allocates and copies nothing
-    int ensure_tracers()
-    {
-        if (tr_gen != S->tracer_gen) {
-            if (tr_xyz) {
-                HIP_TRY(hipStreamSynchronize(S->stream));    // a queued advance may still use what is freed here
-                HIP_TRY(hipFree(tr_xyz));
-                HIP_TRY(hipFree(tr_meta));
-                HIP_TRY(hipFree(tr_emit));
-                if (tr_out) HIP_TRY(hipFree(tr_out));
-            }
-            tr_xyz = tr_emit = tr_out = nullptr;
-            tr_meta = nullptr;
-            tr_cap = 0;
-            tr_emit_gen = -1;
-            tr_ring.gen = -1;                            // the frames are C slots wide: the ring goes with the pool
-            S->tracer_seeded = 0;
-            tr_gen = S->tracer_gen;
-            if (S->tracers > 0) {
-                if (S->comm.active()) return fail(FS_EINVAL, "tracers need a single-GPU handle");
-                const size_t C = (size_t)S->tracers;
-                hipError_t e = hipMalloc((void**)&tr_xyz, C * 3 * sizeof(double));
-                if (e == hipSuccess) e = hipMalloc((void**)&tr_meta, C * fs::TRACER_META * sizeof(int));
-                if (e == hipSuccess) e = hipMalloc((void**)&tr_emit, (size_t)FS_TRACER_EMITTERS_MAX * 3 * sizeof(double));
-                if (e != hipSuccess) {                   // the option goes back to off: capacity and entries agree, a later set tries again
-                    if (tr_xyz) hipFree(tr_xyz);
-                    if (tr_meta) hipFree(tr_meta);
-                    tr_xyz = nullptr;
-                    tr_meta = nullptr;
-                    S->tracers = 0;
-                    return fail(FS_ENOMEM, "tracers: %zu slots: %s (the option is 0 again)", C, hipGetErrorString(e));
-                }
-                HIP_TRY(hipMemsetAsync(tr_xyz, 0, C * 3 * sizeof(double), S->stream));
-                HIP_TRY(hipMemsetAsync(tr_meta, 0, C * fs::TRACER_META * sizeof(int), S->stream));   // every slot FREE
-                tr_cap = S->tracers;
-            }
-        }
-        if (tr_ring.gen != S->tracer_log_gen || (tr_cap == 0 && tr_ring.base)) {
-            const hipError_t e = tr_ring.setup(S->stream, S->tracer_log_gen, tr_cap > 0 ? S->tracer_log : 0, (size_t)tr_cap * fs::TRACER_FRAME_BYTES);
-            if (e != hipSuccess && !tr_ring.base) {      // no memory.  Likewise: the log is off until the option is set again
-                const int frames = S->tracer_log;
-                S->tracer_log = 0;
-                return fail(FS_ENOMEM, "tracer_log: %d frames of %d slots: %s (the option is 0 again)", frames, tr_cap, hipGetErrorString(e));
-            }
-            HIP_TRY(e);
-        }
-        if (tr_cap > 0 && tr_emit_gen != S->tracer_emit_gen) {
-            if (!S->tracer_emit.empty()) {
-                HIP_TRY(hipMemcpyAsync(tr_emit, S->tracer_emit.data(), S->tracer_emit.size() * sizeof(double), hipMemcpyHostToDevice, S->stream));
-                HIP_TRY(hipStreamSynchronize(S->stream));    // the host list may change before the copy has run
-            }
-            tr_emit_gen = S->tracer_emit_gen;
-        }
-        return FS_OK;
-    }
-
-    // one advance: the move of every ALIVE particle, the emitters' release (if `release`), a snapshot frame (if `snapshot`
-    // and the log is on).  One launch; the slot cursor is the host's.
-    void tracer_pass(bool release, bool snapshot)
-    {
-        fs::TracerPass pass;
-        pass.C = tr_cap;
-        pass.xyz = tr_xyz;
-        pass.meta = tr_meta;
-        pass.k[0] = (double)S->dt * (double)S->W;        // simulation.cpp:384-386, exact in fp64
-        pass.k[1] = (double)S->dt * (double)S->H;
-        pass.k[2] = (double)S->dt * (double)S->D;
-        pass.emit = tr_emit;
-        pass.n_emit = release ? (int)(S->tracer_emit.size() / 3) : 0;
-        pass.first = (int)(S->tracer_seeded % tr_cap);
-        pass.born = (int)S->steps_total;
-        const bool frame = snapshot && tr_ring.on();
-        pass.frame_xyz = frame ? tracer_frame_xyz(tr_ring.at.next()) : nullptr;
-        pass.frame_status = frame ? tracer_frame_status(tr_ring.at.next()) : nullptr;
-        {
-            ScopedSpan sp(S, FAM_TRACERS);
-            fs::launch_tracer_advance<T>(S->stream, g, pass, arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]], arr[slot[FS_OBS]]);
-        }
-        S->tracer_seeded += pass.n_emit;
-        if (frame) tr_ring.at.commit(S->steps_total);
-    }
-
-    int tracer_need(const char* who)
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "%s: tracers need a single-GPU handle", who);
-        int rc = ensure_tracers();
-        if (rc) return rc;
-        if (tr_cap == 0) return fail(FS_EINVAL, "%s: option \"tracers\" is 0", who);
-        return FS_OK;
-    }
-
-    int tracer_advance() override
-    {
-        int rc = tracer_need("fs_tracer_advance");
-        if (rc) return rc;
-        tracer_pass(true, true);
-        return FS_OK;
-    }
-
-    int tracer_seed(const double* xyz, long n) override
-    {
-        int rc = tracer_need("fs_tracer_seed");
-        if (rc) return rc;
-        if (n == 0) return FS_OK;
-        // the j-th particle ever seeded goes into slot j % C: of more than C only the last C remain
-        const long C = tr_cap, skip = n > C ? n - C : 0, m = n - skip;
-        const long first = (S->tracer_seeded + skip) % C, run = std::min<long>(m, C - first);
-        std::vector<int32_t> meta((size_t)m * fs::TRACER_META);
-        for (long j = 0; j < m; ++j) {
-            int32_t* w = &meta[(size_t)j * fs::TRACER_META];
-            w[0] = fs::TRACER_ALIVE; w[1] = -1; w[2] = (int32_t)S->steps_total; w[3] = 0;
-        }
-        const double* src = xyz + 3 * skip;
-        HIP_TRY(hipMemcpyAsync(tr_xyz + 3 * first, src, (size_t)run * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
-        HIP_TRY(hipMemcpyAsync(tr_meta + fs::TRACER_META * first, meta.data(), (size_t)run * fs::TRACER_META * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
-        if (m > run) {
-            HIP_TRY(hipMemcpyAsync(tr_xyz, src + 3 * run, (size_t)(m - run) * 3 * sizeof(double), hipMemcpyHostToDevice, S->stream));
-            HIP_TRY(hipMemcpyAsync(tr_meta, meta.data() + (size_t)run * fs::TRACER_META, (size_t)(m - run) * fs::TRACER_META * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, S->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(S->stream));        // `xyz` may be freed by the caller
-        S->tracer_seeded += n;
-        return FS_OK;
-    }
-
-    int tracer_clear() override
-    {
-        int rc = tracer_need("fs_tracer_clear");
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(tr_xyz, 0, (size_t)tr_cap * 3 * sizeof(double), S->stream));
-        HIP_TRY(hipMemsetAsync(tr_meta, 0, (size_t)tr_cap * fs::TRACER_META * sizeof(int), S->stream));
-        S->tracer_seeded = 0;
-        tr_ring.at.drain();
-        return FS_OK;
-    }
-
-    int tracer_fetch(double* xyz, int32_t* meta, long max, long* n) override
-    {
-        int rc = tracer_need("fs_tracer_fetch");
-        if (rc) return rc;
-        const long count = std::min<long>(S->tracer_seeded, tr_cap);
-        if (n) *n = count;
-        if (!xyz && !meta) return FS_OK;
-        if (max < count) return fail(FS_EINVAL, "fs_tracer_fetch: %ld particles, room for %ld (pass both arrays NULL to ask)", count, max);
-        if (count == 0) return FS_OK;
-        if (xyz) HIP_TRY(hipMemcpyAsync(xyz, tr_xyz, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        if (meta) HIP_TRY(hipMemcpyAsync(meta, tr_meta, (size_t)count * fs::TRACER_META * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int tracer_sample(int source, int mode, double* out, long n) override
-    {
-        int rc = tracer_need("fs_tracer_sample");
-        if (rc) return rc;
-        const long count = std::min<long>(S->tracer_seeded, tr_cap);
-        if (n != count) return fail(FS_EINVAL, "fs_tracer_sample: the pool holds %ld particles, the call has room for %ld", count, n);
-        if (!tr_out && n > 0 && out) {
-            const hipError_t e = hipMalloc((void**)&tr_out, (size_t)tr_cap * sizeof(double));
-            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_tracer_sample: %d values: %s", tr_cap, hipGetErrorString(e));
-        }
-        return sample_at("fs_tracer_sample", source, mode, tr_xyz, tr_out, out, n);
-    }
-
-    int tracer_log_fetch(double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_tracer_log: tracers need a single-GPU handle");
-        int rc = ensure_tracers();
-        if (rc) return rc;
-        rc = tr_ring.fetch_begin({"fs_tracer_log", "frames", "both arrays NULL"}, tr_ring.at.retained(), max_frames,
-                                 xyz || status, n_frames, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        HIP_TRY(tr_ring.fetch_copy(S->stream, xyz, tracer_frame_xyz(0), (size_t)tr_cap * 3 * sizeof(double),
-                                   status, tracer_frame_status(0), (size_t)tr_cap * sizeof(int32_t)));
-        tr_ring.fetch_end(steps);
-        return FS_OK;
-    }
-
-    double* probe_slot(long k) const { return (double*)probe_ring.slot(k); }
-
-    // set up the probe list and (re)allocate and clear the ring after fs_set_probes / fs_set_option("probe_log")
-    int ensure_probe_ring()
-    {
-        if (probe_ring.gen == S->probe_gen) return FS_OK;
-        if (probe_idx) {
-            HIP_TRY(hipStreamSynchronize(S->stream));    // a queued record may still use what is freed here
-            HIP_TRY(hipFree(probe_idx));
-        }
-        probe_idx = nullptr;
-        probe_n = 0;
-        HIP_TRY(probe_ring.setup(S->stream, S->probe_gen));   // off
-        const int n = (int)(S->probes.size() / 3);
-        if (n == 0 || S->probe_log <= 0) return FS_OK;
-        // the owner of a probe is the rank that owns its global plane (z = 0: the first, z = D + 1: the last)
-        std::vector<long> idx((size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const int x = S->probes[3 * (size_t)k], y = S->probes[3 * (size_t)k + 1], z = S->probes[3 * (size_t)k + 2];
-            const int zl = z - sc.zoff;
-            const bool mine = (zl >= 1 && zl <= g.D) || (z == 0 && sc.lo_wall) || (z == sc.Dglobal + 1 && sc.hi_wall);
-            idx[(size_t)k] = mine ? (long)x + (long)y * g.sy + (long)zl * g.sz : -1;
-        }
-        HIP_TRY(hipMalloc((void**)&probe_idx, idx.size() * sizeof(long)));
-        HIP_TRY(hipMemcpyAsync(probe_idx, idx.data(), idx.size() * sizeof(long), hipMemcpyHostToDevice, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));        // `idx` goes out of scope
-        probe_n = n;
-        HIP_TRY(probe_ring.setup(S->stream, S->probe_gen, S->probe_log, (size_t)n * fs::PROBE_VALUES * sizeof(double)));
-        return FS_OK;
-    }
-
-    // one record of the state as it is now into the next ring slot
-    void probe_record()
-    {
-        {
-            ScopedSpan sp(S, FAM_PROBES);
-            fs::launch_probe_record<T>(S->stream, probe_n, probe_idx, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]],
-                                       arr[slot[FS_VZ]], arr[slot[FS_PRESSURE]], probe_slot(probe_ring.at.next()));
-        }
-        probe_ring.at.commit(S->steps_total);
-    }
-
-    int probe_sample() override
-    {
-        int rc = ensure_probe_ring();
-        if (rc) return rc;
-        if (!probe_ring.on()) return fail(FS_EINVAL, "fs_probe_sample: no probes are set (fs_set_probes), or option \"probe_log\" is 0");
-        probe_record();
-        return FS_OK;
-    }
-
-    int probe_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        int rc = ensure_probe_ring();
-        if (rc) return rc;
-        const long n = probe_ring.at.retained();
-        rc = probe_ring.fetch_begin({"fs_probe_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "probe records need the other slabs' planes; the FSNULL transport carries none");
-        const size_t per = (size_t)probe_n * fs::PROBE_VALUES;   // one record
-        std::vector<double> mine((size_t)n * per), all;
-        HIP_TRY(probe_ring.fetch_copy(S->stream, mine.data()));
-        if ((rc = gather_plane_records(mine, all, "probe records"))) return rc;
-        const size_t blob = mine.size();
-        const int nr = S->comm.active() ? S->comm.nranks : 1, ld = S->D / nr;
-        std::vector<size_t> owner_off((size_t)probe_n);  // only the owner's value is used
-        for (int k = 0; k < probe_n; ++k) {
-            const int z = S->probes[3 * (size_t)k + 2];
-            const int r = z <= 0 ? 0 : z > S->D ? nr - 1 : (z - 1) / ld;
-            owner_off[(size_t)k] = (size_t)r * blob + (size_t)k * fs::PROBE_VALUES;
-        }
-        const size_t cols = 1 + per;
-        for (long i = 0; i < n; ++i) {
-            double* o = rows + (size_t)i * cols;
-            o[0] = (double)probe_ring.at.step_of(i);
-            for (int k = 0; k < probe_n; ++k)
-                for (int j = 0; j < fs::PROBE_VALUES; ++j)
-                    o[1 + (size_t)k * fs::PROBE_VALUES + j] = all[owner_off[(size_t)k] + (size_t)i * per + j];
-        }
-        probe_ring.fetch_end();
-        return FS_OK;
-    }
-
-    // ---- slice and projection images (image.h; the reference's 2-D viewer does this on the host, gui.py:61-79, 257-295) ----
-    long image_max_pixels() const
-    {
-        const long a = (long)(g.W + 2) * (g.H + 2), b = (long)(g.W + 2) * (g.D + 2), c = (long)(g.H + 2) * (g.D + 2);
-        return std::max(a, std::max(b, c));
-    }
-
-    // the scratch images and the device copy of the colour table, at first need and after fs_image_colormap
-    int ensure_image_scratch()
-    {
-        if (!img_val) {
-            const size_t np = ((size_t)image_max_pixels() + 15) / 16 * 16;
-            uint8_t* base = nullptr;
-            const hipError_t e = hipMalloc((void**)&base, np * 16 + 3 * (size_t)fs::IMG_TABLE_MAX);
-            if (e != hipSuccess) return fail(FS_ENOMEM, "image scratch of %zu bytes: %s", np * 16 + 3 * (size_t)fs::IMG_TABLE_MAX, hipGetErrorString(e));
-            img_val = (double*)base;
-            img_flag = base + 8 * np;
-            for (int a = 0; a < 3; ++a) img_sil[a] = base + (9 + (size_t)a) * np;
-            img_rgb = base + 12 * np;
-            img_table = base + 16 * np;
-            img_sil_ok[0] = img_sil_ok[1] = img_sil_ok[2] = false;
-            img_table_gen = -1;
-        }
-        if (img_table_gen != S->image_table_gen) {
-            const bool own = !S->image_table.empty();
-            img_table_n = own ? (int)(S->image_table.size() / 3) : fs::IMG_DEFAULT_N;
-            HIP_TRY(hipMemcpyAsync(img_table, own ? S->image_table.data() : fs::IMG_DEFAULT_TABLE, 3 * (size_t)img_table_n,
-                                   hipMemcpyHostToDevice, S->stream));
-            HIP_TRY(hipStreamSynchronize(S->stream));    // the handle's table may be replaced by the caller
-            img_table_gen = S->image_table_gen;
-        }
-        return FS_OK;
-    }
-
-    // One value image into img_val and its obstacle flags (-> flag): the kernels of one view.  The arguments are checked.
-    int image_render(const char* who, int source, int kind, int axis, int index, const uint8_t*& flag)
-    {
-        int rc = ensure_flags();                         // obs changed: the silhouettes are stale
-        if (rc) return rc;
-        const T* field = nullptr;
-        const double* stat = nullptr;
-        if ((rc = resolve_source(who, source, field, stat))) return rc;
-        const T* obs = arr[slot[FS_OBS]];
-        if (kind == fs::IMG_SLICE) {
-            if (stat) fs::launch_image_slice<double, T>(S->stream, g, axis, index, stat, obs, img_val, img_flag);
-            else fs::launch_image_slice<T, T>(S->stream, g, axis, index, field, obs, img_val, img_flag);
-            flag = img_flag;
-            return FS_OK;
-        }
-        if (stat) fs::launch_image_project<double>(S->stream, g, kind, axis, stat, img_val, nullptr);
-        else fs::launch_image_project<T>(S->stream, g, kind, axis, field, img_val, nullptr);
-        if (!img_sil_ok[axis]) {                         // the silhouette depends on obs and the axis only
-            fs::launch_image_project<T>(S->stream, g, fs::IMG_ANY, axis, obs, nullptr, img_sil[axis]);
-            img_sil_ok[axis] = true;
-        }
-        flag = img_sil[axis];
-        return FS_OK;
-    }
-
-    int image_args(const char* who, int kind, int axis, int index, int* cols, int* rows)
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "%s: images are taken on a single-GPU handle", who);
-        if (kind < 0 || kind >= fs::IMG_NKINDS) return fail(FS_EINVAL, "%s: unknown kind %d (FS_IMG_SLICE | SUM | MAX | MIN)", who, kind);
-        if (axis < 0 || axis > 2) return fail(FS_EINVAL, "%s: axis %d (0 = x, 1 = y, 2 = z)", who, axis);
-        const int N = axis == 0 ? g.W : axis == 1 ? g.H : g.D;
-        if (index < 0 || index > (kind == fs::IMG_SLICE ? N + 1 : 0))
-            return fail(FS_EINVAL, "%s: index %d (a slice: 0 .. %d; a projection: 0)", who, index, N + 1);
-        int c, r;
-        fs::image_dims(axis, g.W, g.H, g.D, &c, &r);
-        if (cols) *cols = c;
-        if (rows) *rows = r;
-        return FS_OK;
-    }
-
-    int image_values(int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows) override
-    {
-        int c, r;
-        int rc = image_args("fs_image_values", kind, axis, index, &c, &r);
-        if (rc) return rc;
-        if (!image_source_ok(source)) return fail(FS_EINVAL, "fs_image_values: unknown source %d", source);
-        if (cols) *cols = c;
-        if (rows) *rows = r;
-        if (!out) return FS_OK;
-        if (n != (size_t)c * (size_t)r) return fail(FS_EINVAL, "fs_image_values: the image has %d x %d values, the call has room for %zu", c, r, n);
-        if ((rc = ensure_image_scratch())) return rc;
-        const uint8_t* flag = nullptr;
-        {
-            ScopedSpan sp(S, FAM_MISC);
-            if ((rc = image_render("fs_image_values", source, kind, axis, index, flag))) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(out, img_val, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int image_rgb(int source, int kind, int axis, int index, double vmin, double vmax, double alpha, uint8_t* out, size_t n_bytes,
-                  int* cols, int* rows) override
-    {
-        int c, r;
-        int rc = image_args("fs_image_rgb", kind, axis, index, &c, &r);
-        if (rc) return rc;
-        if (!image_source_ok(source)) return fail(FS_EINVAL, "fs_image_rgb: unknown source %d", source);
-        if (!image_range_ok(vmin, vmax, alpha)) return fail(FS_EINVAL, "fs_image_rgb: vmin < vmax, both finite, and obstacle_alpha in [0, 1]");
-        if (cols) *cols = c;
-        if (rows) *rows = r;
-        if (!out) return FS_OK;
-        const size_t npix = (size_t)c * (size_t)r;
-        if (n_bytes != 3 * npix) return fail(FS_EINVAL, "fs_image_rgb: the image has %d x %d x 3 bytes, the call has room for %zu", c, r, n_bytes);
-        if ((rc = ensure_image_scratch())) return rc;
-        const uint8_t* flag = nullptr;
-        {
-            ScopedSpan sp(S, FAM_MISC);
-            if ((rc = image_render("fs_image_rgb", source, kind, axis, index, flag))) return rc;
-            fs::launch_image_colour(S->stream, (long)npix, img_val, flag, vmin, vmax, alpha, img_table, img_table_n, img_rgb);
-        }
-        HIP_TRY(hipMemcpyAsync(out, img_rgb, n_bytes, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int image_config() override { return ensure_image_ring(); }
-
-    // (re)allocate and clear the ring after fs_image_views / fs_set_option("image_log"), and set up whatever a view needs, so
-    // that a record in mid-step allocates nothing: the scratch images, the vortex array, the staging of a statistics source
-    int ensure_image_ring()
-    {
-        if (img_ring.gen == S->image_gen) return img_ring.on() ? ensure_image_scratch() : FS_OK;   // a new colour table
-        HIP_TRY(img_ring.setup(S->stream, S->image_gen));   // off, whatever fails below
-        if (S->image_views.empty() || S->image_log <= 0) return FS_OK;
-        if (S->comm.active()) return fail(FS_EINVAL, "the image log needs a single-GPU handle");
-        int rc = ensure_image_scratch();
-        if (rc) return rc;
-        size_t bytes = 0;
-        for (const ImageView& v : S->image_views) {
-            int c, r;
-            fs::image_dims(v.axis, g.W, g.H, g.D, &c, &r);
-            bytes += 3 * (size_t)c * (size_t)r;
-            if ((v.source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (rc = ensure_vort("fs_image_views"))) return rc;
-            if ((v.source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT && (rc = need_dense(stat_bytes()))) return rc;
-        }
-        const hipError_t e = img_ring.setup(S->stream, S->image_gen, S->image_log, bytes);
-        if (e != hipSuccess && !img_ring.base) return fail(FS_ENOMEM, "image_log: %d frames of %zu bytes: %s", S->image_log, bytes, hipGetErrorString(e));
-        HIP_TRY(e);
-        return FS_OK;
-    }
-
-    // one frame of the state as it is now into the next ring slot: every view's kernels, then its colouring
-    int image_record()
-    {
-        uint8_t* dst = (uint8_t*)img_ring.slot(img_ring.at.next());
-        for (const ImageView& v : S->image_views) {
-            int c, r;
-            fs::image_dims(v.axis, g.W, g.H, g.D, &c, &r);
-            const uint8_t* flag = nullptr;
-            ScopedSpan sp(S, FAM_IMAGES);
-            const int rc = image_render("the image log", v.source, v.kind, v.axis, v.index, flag);
-            if (rc) return rc;
-            fs::launch_image_colour(S->stream, (long)c * r, img_val, flag, v.vmin, v.vmax, v.alpha, img_table, img_table_n, dst);
-            dst += 3 * (size_t)c * (size_t)r;
-        }
-        img_ring.at.commit(S->steps_total);
-        return FS_OK;
-    }
-
-    int image_sample() override
-    {
-        int rc = ensure_image_ring();
-        if (rc) return rc;
-        if (!img_ring.on()) return fail(FS_EINVAL, "fs_image_sample: no views are set (fs_image_views), or option \"image_log\" is 0");
-        return image_record();
-    }
-
-    int image_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) override
-    {
-        int rc = ensure_image_ring();
-        if (rc) return rc;
-        rc = img_ring.fetch_begin({"fs_image_log", "frames", "frames = NULL"}, img_ring.at.retained(), max_frames,
-                                  frames != nullptr, n_frames, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        HIP_TRY(img_ring.fetch_copy(S->stream, frames));
-        img_ring.fetch_end(steps);
-        return FS_OK;
-    }
-
-    // ---- volume rendering (volume.h; the reference's 3-D viewer, GUI/gl_widget.py, renders no volume) -------------------
-    // A slot's ray set: uploaded into a new array, then the old one goes (a queued frame may still read it: the stream is
-    // synchronised first).  cols = rows = 0 frees the slot.  The arguments are checked by fs_volume_rays.
-    int volume_rays(int slot, const double* rays, int cols, int rows) override
-    {
-        double* fresh = nullptr;
-        const size_t bytes = (size_t)cols * (size_t)rows * 6 * sizeof(double);
-        if (bytes > 0) {
-            const hipError_t e = hipMalloc((void**)&fresh, bytes);
-            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_volume_rays: %d x %d rays: %s", cols, rows, hipGetErrorString(e));
-            hipError_t c = hipMemcpyAsync(fresh, rays, bytes, hipMemcpyHostToDevice, S->stream);
-            if (c == hipSuccess) c = hipStreamSynchronize(S->stream);   // `rays` may be freed by the caller
-            if (c != hipSuccess) { hipFree(fresh); HIP_TRY(c); }
-        }
-        if (vol_rays[slot]) {
-            HIP_TRY(hipStreamSynchronize(S->stream));
-            HIP_TRY(hipFree(vol_rays[slot]));
-        }
-        vol_rays[slot] = fresh;
-        return FS_OK;
-    }
-
-    // one view of the state as it is now: one launch.  The arguments are checked; rgb / acc are device arrays, either may be null.
-    int volume_launch(const char* who, int source, int cam, const double* par, uint8_t* rgb, double* acc)
-    {
-        fs::VolumeView vw = {};
-        if (!fs::volume_params_ok(par, g.W, g.H, g.D, &vw.kmax)) return fail(FS_EINVAL, "%s: bad view parameters", who);
-        for (int k = 0; k < fs::VOLUME_PARAMS; ++k) vw.par[k] = par[k];
-        vw.n = img_table_n;
-        const T* field = nullptr;
-        const double* stat = nullptr;
-        const int rc = resolve_source(who, source, field, stat);
-        if (rc) return rc;
-        const T* obs = arr[slot[FS_OBS]];
-        const int cols = S->vol_cols[cam], rows = S->vol_rows[cam];
-        if (stat) fs::launch_volume<double, T>(S->stream, g, vw, cols, rows, vol_rays[cam], stat, obs, img_table, rgb, acc);
-        else fs::launch_volume<T, T>(S->stream, g, vw, cols, rows, vol_rays[cam], field, obs, img_table, rgb, acc);
-        return FS_OK;
-    }
-
-    int volume_render(int source, int slot, const double* par, uint8_t* rgb, size_t n_bytes, double* acc, size_t n_acc) override
-    {
-        const size_t npix = (size_t)S->vol_cols[slot] * (size_t)S->vol_rows[slot];
-        int rc = ensure_image_scratch();                 // the colour table
-        if (rc) return rc;
-        if (npix > vol_room) {
-            if (vol_rgb) {
-                HIP_TRY(hipStreamSynchronize(S->stream));
-                HIP_TRY(hipFree(vol_rgb));
-                HIP_TRY(hipFree(vol_acc));
-            }
-            vol_rgb = nullptr;
-            vol_acc = nullptr;
-            vol_room = 0;
-            hipError_t e = hipMalloc((void**)&vol_acc, npix * 4 * sizeof(double));
-            if (e == hipSuccess && (e = hipMalloc((void**)&vol_rgb, npix * 3)) != hipSuccess) {
-                hipFree(vol_acc);
-                vol_acc = nullptr;
-            }
-            if (e != hipSuccess) return fail(FS_ENOMEM, "fs_volume_render: %zu pixels: %s", npix, hipGetErrorString(e));
-            vol_room = npix;
-        }
-        {
-            ScopedSpan sp(S, FAM_MISC);
-            if ((rc = volume_launch("fs_volume_render", source, slot, par, rgb ? vol_rgb : nullptr, acc ? vol_acc : nullptr))) return rc;
-        }
-        if (rgb) HIP_TRY(hipMemcpyAsync(rgb, vol_rgb, n_bytes, hipMemcpyDeviceToHost, S->stream));
-        if (acc) HIP_TRY(hipMemcpyAsync(acc, vol_acc, n_acc * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int volume_config() override { return ensure_volume_ring(); }
-
-    // (re)allocate and clear the ring after fs_volume_views / fs_volume_rays / fs_set_option("volume_log"), and set up whatever a
-    // view needs, so that a record in mid-step allocates nothing: the colour table, the vortex array, the staging of a
-    // statistics source
-    int ensure_volume_ring()
-    {
-        if (vol_ring.gen == S->volume_gen) return vol_ring.on() ? ensure_image_scratch() : FS_OK;   // a new colour table
-        HIP_TRY(vol_ring.setup(S->stream, S->volume_gen));   // off, whatever fails below
-        if (S->volume_views.empty() || S->volume_log <= 0) return FS_OK;
-        if (S->comm.active()) return fail(FS_EINVAL, "the volume log needs a single-GPU handle");
-        int rc = ensure_image_scratch();
-        if (rc) return rc;
-        for (const VolumeLogView& v : S->volume_views) {
-            if ((v.source & ~(FS_ISO_VORTEX - 1)) == FS_ISO_VORTEX && (rc = ensure_vort("fs_volume_views"))) return rc;
-            if ((v.source & ~(FS_SAMPLE_STAT - 1)) == FS_SAMPLE_STAT && (rc = need_dense(stat_bytes()))) return rc;
-        }
-        const size_t bytes = volume_frame_bytes(S, S->volume_views);
-        const hipError_t e = vol_ring.setup(S->stream, S->volume_gen, S->volume_log, bytes);
-        if (e != hipSuccess && !vol_ring.base) return fail(FS_ENOMEM, "volume_log: %d frames of %zu bytes: %s", S->volume_log, bytes, hipGetErrorString(e));
-        HIP_TRY(e);
-        return FS_OK;
-    }
-
-    // one frame of the state as it is now into the next ring slot: one launch per view
-    int volume_record()
-    {
-        uint8_t* dst = (uint8_t*)vol_ring.slot(vol_ring.at.next());
-        for (const VolumeLogView& v : S->volume_views) {
-            ScopedSpan sp(S, FAM_VOLUME);
-            const int rc = volume_launch("the volume log", v.source, v.slot, v.par, dst, nullptr);
-            if (rc) return rc;
-            dst += 3 * (size_t)S->vol_cols[v.slot] * (size_t)S->vol_rows[v.slot];
-        }
-        vol_ring.at.commit(S->steps_total);
-        return FS_OK;
-    }
-
-    int volume_sample() override
-    {
-        int rc = ensure_volume_ring();
-        if (rc) return rc;
-        if (!vol_ring.on()) return fail(FS_EINVAL, "fs_volume_sample: no views are set (fs_volume_views), or option \"volume_log\" is 0");
-        return volume_record();
-    }
-
-    int volume_log_fetch(uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped) override
-    {
-        int rc = ensure_volume_ring();
-        if (rc) return rc;
-        rc = vol_ring.fetch_begin({"fs_volume_log", "frames", "frames = NULL"}, vol_ring.at.retained(), max_frames,
-                                  frames != nullptr, n_frames, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        HIP_TRY(vol_ring.fetch_copy(S->stream, frames));
-        vol_ring.fetch_end(steps);
-        return FS_OK;
-    }
-
-    // ---- pressure force on the obstacles (forces.h; beyond the reference) ------------------------------
-    // ring slot k, projection j: g.D plane records
-    double* force_slot(long k, int j) const { return (double*)force_ring.slot(k) + (size_t)j * plane_doubles(); }
-    size_t plane_doubles() const { return (size_t)fs::FORCE_REC * (size_t)g.D; }
-
-    // (re)allocate and clear the ring after fs_set_option("force_log")
-    int ensure_force_ring()
-    {
-        if (force_ring.gen == S->force_log_gen) return FS_OK;
-        HIP_TRY(force_ring.setup(S->stream, S->force_log_gen, S->force_log, 2 * plane_doubles() * sizeof(double)));
-        return FS_OK;
-    }
-
-    // Every rank's plane records (`mine`: `blocks` blocks of g.D records each) -> `all`: rank r's blocks at r * mine.size()
-    // (a slab's planes follow the lower slabs' planes).  Collective on slab handles; the host holds everything afterwards.
-    // `what`: "obstacle forces" / "solve residuals" (the records of both travel the same way)
-    int gather_plane_records(const std::vector<double>& mine, std::vector<double>& all, const char* what)
-    {
-        if (!S->comm.active()) { all = mine; return FS_OK; }
-        if (S->comm.null_transport) return fail(FS_EINVAL, "%s need the other slabs' planes; the FSNULL transport carries none", what);
-        all.assign(mine.size() * (size_t)S->comm.nranks, 0.0);
-        if (mine.empty()) return FS_OK;
-        return comm_op([&](hipStream_t st) { return S->comm.allgather_host(st, mine.data(), all.data(), mine.size() * sizeof(double), g, S->D); },
-                       "gather of the plane records");
-    }
-
-    // Sum of the records of global planes 1..D in increasing z, in fp64: `rec(r, zl)` = record of local plane zl of rank r.
-    // Single-GPU and slab handles add the same numbers in the same order.
-    // Records of `ncols` columns; column `maxcol` (if any) is a maximum, not a sum.
-    template <class F>
-    void combine_planes(F&& rec, double* out, int ncols = fs::FORCE_REC, int maxcol = -1) const
-    {
-        const int nr = S->comm.active() ? S->comm.nranks : 1;
-        for (int k = 0; k < ncols; ++k) out[k] = 0.0;
-        for (int r = 0; r < nr; ++r)
-            for (int zl = 0; zl < g.D; ++zl) {
-                const double* q = rec(r, zl);
-                for (int k = 0; k < ncols; ++k) out[k] = (k == maxcol) ? std::fmax(out[k], q[k]) : out[k] + q[k];
-            }
-    }
-
-    int obstacle_force(double* out5, double* per_plane) override
-    {
-        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
-        int rc = ensure_flags();
-        if (rc) return rc;
-        const size_t n = plane_doubles();
-        if (!force_scratch) HIP_TRY(hipMalloc((void**)&force_scratch, n * sizeof(double)));
-        {
-            ScopedSpan sp(S, FAM_FORCES);
-            fs::launch_forces<T>(S->stream, g, sc, arr[slot[FS_PRESSURE]], flags, force_scratch);
-        }
-        std::vector<double> mine(n), all;
-        HIP_TRY(hipMemcpyAsync(mine.data(), force_scratch, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
-        combine_planes([&](int r, int zl) { return &all[(size_t)r * n + (size_t)zl * fs::FORCE_REC]; }, out5);
-        if (per_plane) memcpy(per_plane, all.data(), all.size() * sizeof(double));
-        return FS_OK;
-    }
-
-    int force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        int rc = ensure_force_ring();
-        if (rc) return rc;
-        const long n = force_ring.at.retained();
-        rc = force_ring.fetch_begin({"fs_force_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "obstacle forces need the other slabs' planes; the FSNULL transport carries none");
-        const size_t per = 2 * plane_doubles();   // one step: both projections
-        std::vector<double> mine((size_t)n * per), all;
-        HIP_TRY(force_ring.fetch_copy(S->stream, mine.data()));
-        if ((rc = gather_plane_records(mine, all, "obstacle forces"))) return rc;
-        const size_t blob = mine.size();
-        for (long i = 0; i < n; ++i) {
-            double s[2][fs::FORCE_REC];
-            for (int j = 0; j < 2; ++j)
-                combine_planes([&](int r, int zl) {
-                    return &all[(size_t)r * blob + (size_t)i * per + (size_t)j * (per / 2) + (size_t)zl * fs::FORCE_REC]; }, s[j]);
-            double* o = rows + (size_t)i * FS_FORCE_LOG_COLS;
-            o[0] = (double)force_ring.at.step_of(i);
-            for (int k = 0; k < 3; ++k) {
-                o[1 + k] = s[0][k];
-                o[4 + k] = s[1][k];
-            }
-            o[7] = s[1][3];
-            o[8] = s[1][4];
-        }
-        force_ring.fetch_end();
-        return FS_OK;
-    }
-
-    // ---- per-body forces and moments (bodies.h; beyond the reference) ------------------------------------
-    // Label the body cells if obs changed since the last labelling (or `force`).  Synchronises: a mask change is a set-up event.
-    int ensure_bodies(bool force = false)
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
-        int rc = ensure_flags();
-        if (rc) return rc;
-        if (!bodies_dirty && !force && body_L) return FS_OK;
-        const long N = dense_cells();
-        if (N >= (1L << 31)) return fail(FS_EINVAL, "body labels are 32-bit: %ld padded cells are too many", N);
-        struct Temp {                                    // freed on every path out
-            std::vector<void*> v;
-            ~Temp() { for (void* q : v) if (q) hipFree(q); }
-            hipError_t get(void** q, size_t bytes) { hipError_t e = hipMalloc(q, bytes ? bytes : 1); if (e == hipSuccess) v.push_back(*q); return e; }
-        } tmp;
-        constexpr int NINFO = (fs::BODY_MAX + 1) * fs::BODY_INFO;
-        if (!body_L) HIP_TRY(hipMalloc((void**)&body_L, (size_t)N * sizeof(int)));
-        if (!body_bbox) HIP_TRY(hipMalloc((void**)&body_bbox, (fs::BODY_MAX + 1) * 6 * sizeof(int)));
-        if (!body_planes) HIP_TRY(hipMalloc((void**)&body_planes, (size_t)g.D * (fs::BODY_MAX + 1) * fs::BODY_REC * sizeof(double)));
-        if (!body_total) HIP_TRY(hipMalloc((void**)&body_total, (fs::BODY_MAX + 1) * fs::BODY_REC * sizeof(double)));
-        int* cnt = nullptr;
-        unsigned long long* ctr = nullptr;               // body cells, components, cursor, changed; then the info table
-        HIP_TRY(tmp.get((void**)&cnt, (size_t)N * sizeof(int)));
-        HIP_TRY(tmp.get((void**)&ctr, (4 + NINFO) * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), S->stream));
-        fs::launch_body_init<T>(S->stream, g, arr[slot[FS_OBS]], body_L, ctr);
-        unsigned long long n_cells = 0;
-        HIP_TRY(hipMemcpyAsync(&n_cells, ctr, sizeof n_cells, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        for (unsigned long long round = 0;; ++round) {
-            if (round > n_cells + 1) return fail(FS_EHIP, "body labels did not settle within %llu rounds", round);
-            int changed = 0;
-            HIP_TRY(hipMemsetAsync(ctr + 3, 0, sizeof(unsigned long long), S->stream));
-            fs::launch_body_merge(S->stream, g, body_L, (int*)(ctr + 3));
-            HIP_TRY(hipMemcpyAsync(&changed, ctr + 3, sizeof changed, hipMemcpyDeviceToHost, S->stream));
-            HIP_TRY(hipStreamSynchronize(S->stream));
-            if (!changed) break;
-        }
-        HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), S->stream));
-        fs::launch_body_count(S->stream, g, body_L, cnt, ctr + 1);
-        unsigned long long n_roots = 0;
-        HIP_TRY(hipMemcpyAsync(&n_roots, ctr + 1, sizeof n_roots, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        long* pairs = nullptr;
-        int* lab = nullptr;
-        HIP_TRY(tmp.get((void**)&pairs, (size_t)n_roots * 2 * sizeof(long)));
-        HIP_TRY(tmp.get((void**)&lab, (size_t)n_roots * sizeof(int)));
-        fs::launch_body_compact(S->stream, g, body_L, cnt, pairs, ctr + 2);
-        std::vector<fs::BodyPair> hp((size_t)n_roots);
-        static_assert(sizeof(fs::BodyPair) == 2 * sizeof(long), "pairs travel as two longs");
-        if (n_roots) HIP_TRY(hipMemcpyAsync(hp.data(), pairs, (size_t)n_roots * 2 * sizeof(long), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        const std::vector<int> remap = fs::order_bodies(hp, fs::BODY_MAX);
-        if (n_roots) HIP_TRY(hipMemcpyAsync(lab, remap.data(), (size_t)n_roots * sizeof(int), hipMemcpyHostToDevice, S->stream));
-        fs::launch_body_relabel(S->stream, g, (long)n_roots, pairs, lab, body_L, cnt);
-        unsigned long long hinfo[NINFO];
-        for (int k = 0; k <= fs::BODY_MAX; ++k)
-            for (int c = 0; c < fs::BODY_INFO; ++c)
-                hinfo[k * fs::BODY_INFO + c] = (c == 1 || c == 2 || c == 4 || c == 6) ? ~0ull : 0ull;
-        HIP_TRY(hipMemcpyAsync(ctr + 4, hinfo, sizeof hinfo, hipMemcpyHostToDevice, S->stream));
-        fs::launch_body_info(S->stream, g, body_L, flags, ctr + 4);
-        HIP_TRY(hipMemcpyAsync(hinfo, ctr + 4, sizeof hinfo, hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        body_ncomp = (long)n_roots;
-        body_B = (int)std::min<unsigned long long>(n_roots, fs::BODY_MAX);
-        body_info_host.assign((size_t)(body_B + 1) * fs::BODY_INFO, 0.0);
-        int bbox[(fs::BODY_MAX + 1) * 6];
-        for (int k = 0; k <= fs::BODY_MAX; ++k) {
-            int* b = bbox + 6 * k;
-            b[0] = b[2] = b[4] = 1;
-            b[1] = b[3] = b[5] = 0;                     // empty
-            if (k > body_B) continue;
-            const unsigned long long* q = hinfo + k * fs::BODY_INFO;
-            double* o = &body_info_host[(size_t)k * fs::BODY_INFO];
-            if (q[0] == 0) {                             // only the REST can be empty
-                o[1] = -1.0;
-                continue;
-            }
-            for (int c = 0; c < fs::BODY_INFO; ++c) o[c] = (double)q[c];
-            if (k == 0) {                                // the REST scans whole planes
-                b[1] = g.W; b[3] = g.H; b[5] = g.D;
-            } else {
-                b[0] = std::max(1, (int)q[2] - 1); b[1] = std::min(g.W, (int)q[3] + 1);
-                b[2] = std::max(1, (int)q[4] - 1); b[3] = std::min(g.H, (int)q[5] + 1);
-                b[4] = std::max(1, (int)q[6] - 1); b[5] = std::min(g.D, (int)q[7] + 1);
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(body_bbox, bbox, sizeof bbox, hipMemcpyHostToDevice, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));       // `bbox` and the temporaries leave scope
-        bodies_dirty = false;
-        body_ring.gen = -1;
-        return FS_OK;
-    }
-
-    // ring slot k, projection j: body_B + 1 whole-grid records
-    size_t body_slot_doubles() const { return (size_t)(body_B + 1) * fs::BODY_REC; }
-    double* body_slot(long k, int j) const { return (double*)body_ring.slot(k) + (size_t)j * body_slot_doubles(); }
-
-    // "body_force_log" on: label anew if obs changed; (re)allocate and clear the ring after a relabelling,
-    // fs_set_option("body_force_log") and ("moment_origin").  Off: nothing is launched or allocated.
-    int ensure_body_ring()
-    {
-        if (S->body_log > 0) {
-            int rc = ensure_bodies();
-            if (rc) return rc;
-        }
-        if (body_ring.gen == S->body_log_gen) return FS_OK;
-        HIP_TRY(body_ring.setup(S->stream, S->body_log_gen, S->body_log, 2 * body_slot_doubles() * sizeof(double)));
-        return FS_OK;
-    }
-
-    int label_bodies(long* n_components, long* n_bodies) override
-    {
-        int rc = ensure_bodies(true);
-        if (rc) return rc;
-        if (n_components) *n_components = body_ncomp;
-        if (n_bodies) *n_bodies = body_B;
-        return FS_OK;
-    }
-
-    int body_counts(int* bodies, int* components) override
-    {
-        int rc = ensure_bodies();
-        if (rc) return rc;
-        *bodies = body_B;
-        *components = (int)std::min<long>(body_ncomp, 0x7fffffffL);
-        return FS_OK;
-    }
-
-    int body_labels(int32_t* dst, size_t n) override
-    {
-        int rc = ensure_bodies();
-        if (rc) return rc;
-        if ((long)n != dense_cells()) return fail(FS_EINVAL, "fs_body_labels: expected %ld elements, got %zu", dense_cells(), n);
-        HIP_TRY(hipMemcpyAsync(dst, body_L, n * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int body_info(double* rows, long max_rows, long* n_rows) override
-    {
-        int rc = ensure_bodies();
-        if (rc) return rc;
-        const long n = body_B + 1;
-        if (n_rows) *n_rows = n;
-        if (!rows) return FS_OK;
-        if (max_rows < n) return fail(FS_EINVAL, "fs_body_info: %ld rows, room for %ld (pass rows = NULL to ask)", n, max_rows);
-        memcpy(rows, body_info_host.data(), body_info_host.size() * sizeof(double));
-        return FS_OK;
-    }
-
-    int body_force(double* out, long max_rows, long* n_rows, double* per_plane) override
-    {
-        int rc = ensure_bodies();
-        if (rc) return rc;
-        const long n = body_B + 1;
-        if (n_rows) *n_rows = n;
-        if (!out) return FS_OK;
-        if (max_rows < n) return fail(FS_EINVAL, "fs_body_force: %ld rows, room for %ld (pass out = NULL to ask)", n, max_rows);
-        {
-            ScopedSpan sp(S, FAM_BODYFORCES);
-            fs::launch_body_forces<T>(S->stream, g, arr[slot[FS_PRESSURE]], flags, body_L, body_bbox, (int)n, S->moment_origin,
-                                      body_planes, body_total);
-        }
-        HIP_TRY(hipMemcpyAsync(out, body_total, (size_t)n * fs::BODY_REC * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        if (per_plane)
-            HIP_TRY(hipMemcpyAsync(per_plane, body_planes, (size_t)g.D * n * fs::BODY_REC * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        return FS_OK;
-    }
-
-    int body_force_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "bodies are labelled on a single-GPU handle");
-        int rc = ensure_body_ring();
-        if (rc) return rc;
-        const long nrec = body_B + 1;                    // rows of one step
-        const long steps = body_ring.at.retained(), n = steps * nrec;
-        rc = body_ring.fetch_begin({"fs_body_force_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        const size_t per = 2 * body_slot_doubles();      // one step: both projections
-        std::vector<double> mine((size_t)steps * per);
-        HIP_TRY(body_ring.fetch_copy(S->stream, mine.data()));
-        for (long i = 0; i < steps; ++i)
-            for (long k = 0; k < nrec; ++k) {
-                const double* a = &mine[(size_t)i * per + (size_t)k * fs::BODY_REC];
-                const double* b = a + per / 2;
-                double* o = rows + ((size_t)i * nrec + (size_t)k) * FS_BODY_LOG_COLS;
-                o[0] = (double)body_ring.at.step_of(i);
-                o[1] = (double)k;
-                for (int c = 0; c < 6; ++c) {
-                    o[2 + c] = a[c];
-                    o[8 + c] = b[c];
-                }
-                o[14] = b[6];
-                o[15] = b[7];
-            }
-        body_ring.fetch_end();
-        return FS_OK;
-    }
-
-    // ---- flow monitor (monitor.h; beyond the reference) --------------------------------------------------------
-    int ensure_monitor_ws()
-    {
-        if (!mon_ws) HIP_TRY(hipMalloc((void**)&mon_ws, fs::monitor_workspace_doubles(g) * sizeof(double)));
-        return FS_OK;
-    }
-
-    // (re)allocate and clear the ring after fs_set_option("monitor_log") / ("monitor_stations")
-    int ensure_monitor_ring()
-    {
-        if (mon_ring.gen == S->monitor_gen) return FS_OK;
-        HIP_TRY(mon_ring.setup(S->stream, S->monitor_gen));   // off, whatever fails below
-        if (S->monitor_log <= 0) return FS_OK;
-        if (S->comm.active()) return fail(FS_EINVAL, "monitor_log: the flow monitor needs a single-GPU handle");
-        int rc = ensure_monitor_ws();
-        if (rc) return rc;
-        HIP_TRY(mon_ring.setup(S->stream, S->monitor_gen, S->monitor_log, (size_t)fs::MON_RESULT * sizeof(double)));
-        return FS_OK;
-    }
-
-    // one record of the state as it is now into `result` (a ring slot or the workspace's result slot)
-    void monitor_launch(double* result)
-    {
-        ScopedSpan sp(S, FAM_MONITOR);
-        fs::launch_monitor<T>(S->stream, g, arr[slot[FS_DENS]], arr[slot[FS_VX]], arr[slot[FS_VY]], arr[slot[FS_VZ]],
-                              arr[slot[FS_PRESSURE]], flags, S->monitor_stations, mon_ws, result);
-    }
-    void monitor_record()
-    {
-        monitor_launch((double*)mon_ring.slot(mon_ring.at.next()));
-        mon_ring.at.commit(S->steps_total);
-    }
-
-    int monitor_sample() override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_monitor_sample: the flow monitor needs a single-GPU handle");
-        int rc = ensure_flags();
-        if (rc) return rc;
-        if ((rc = ensure_monitor_ring())) return rc;
-        if (!mon_ring.on()) return fail(FS_EINVAL, "fs_monitor_sample: option \"monitor_log\" is 0");
-        monitor_record();
-        return FS_OK;
-    }
-
-    int flow_monitor(double* out16, double* per_plane, double* x_profile) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_flow_monitor: the flow monitor needs a single-GPU handle");
-        int rc = ensure_flags();
-        if (rc) return rc;
-        if ((rc = ensure_monitor_ws())) return rc;
-        const fs::MonitorPlan pl = fs::monitor_plan(g.W, g.H, g.D);
-        monitor_launch(mon_ws + pl.result_off);
-        // planes, profile and result lie one behind the other (monitor_plan.h)
-        std::vector<double> host((size_t)(pl.doubles - pl.planes_off));
-        HIP_TRY(hipMemcpyAsync(host.data(), mon_ws + pl.planes_off, host.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        if (out16) memcpy(out16, host.data() + (pl.result_off - pl.planes_off), fs::MON_PLANE * sizeof(double));
-        if (per_plane) memcpy(per_plane, host.data(), (size_t)g.D * fs::MON_PLANE * sizeof(double));
-        if (x_profile) memcpy(x_profile, host.data() + (pl.profile_off - pl.planes_off), (size_t)g.W * fs::MON_PROFILE * sizeof(double));
-        return FS_OK;
-    }
-
-    int monitor_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        if (S->comm.active()) return fail(FS_EINVAL, "fs_monitor_log: the flow monitor needs a single-GPU handle");
-        int rc = ensure_monitor_ring();
-        if (rc) return rc;
-        const long n = mon_ring.at.retained();
-        rc = mon_ring.fetch_begin({"fs_monitor_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        std::vector<double> mine((size_t)n * fs::MON_RESULT);
-        HIP_TRY(mon_ring.fetch_copy(S->stream, mine.data()));
-        for (long i = 0; i < n; ++i) {
-            double* o = rows + (size_t)i * FS_MONITOR_LOG_COLS;
-            o[0] = (double)mon_ring.at.step_of(i);
-            memcpy(o + 1, &mine[(size_t)i * fs::MON_RESULT], fs::MON_RESULT * sizeof(double));
-        }
-        mon_ring.fetch_end();
-        return FS_OK;
-    }
-
-    // ---- residual of the linear solves (residual.h; beyond the reference) ------------------------------------
-    static constexpr int RES_SOLVES = FS_RESIDUAL_LOG_SOLVES;
-    size_t res_plane_doubles() const { return (size_t)fs::RESIDUAL_REC * (size_t)g.D; }
-    // ring slot k, solve j, when = 0 before the first sweep / 1 after the last: g.D plane records
-    double* res_slot(long k, int j, int when) const { return (double*)res_ring.slot(k) + ((size_t)j * 2 + (size_t)when) * res_plane_doubles(); }
-
-    int ensure_res_partial()
-    {
-        if (!res_partial) HIP_TRY(hipMalloc((void**)&res_partial, fs::residual_partial_doubles(g) * sizeof(double)));
-        return FS_OK;
-    }
-
-    // (re)allocate and clear the ring after fs_set_option("residual_log")
-    int ensure_residual_ring()
-    {
-        if (res_ring.gen == S->residual_log_gen) return FS_OK;
-        HIP_TRY(res_ring.setup(S->stream, S->residual_log_gen));   // off, whatever fails below
-        if (S->residual_log <= 0) return FS_OK;
-        int rc = ensure_res_partial();
-        if (rc) return rc;
-        HIP_TRY(res_ring.setup(S->stream, S->residual_log_gen, S->residual_log, (size_t)RES_SOLVES * 2 * res_plane_doubles() * sizeof(double)));
-        return FS_OK;
-    }
-
-    // "residual_log": solve k of the running step, before (when = 0) or after (1) its sweeps, straight into the step's ring
-    // slot on the compute stream (no host sync).  On a z-slab the halo planes of `x` are current at both points: the
-    // producer of x exchanged them (advection, inlet, the zeroed pressure), and so does the last pass of every solve.
-    int log_residual(int k, int when, int b, int x, int rhs, double a, double c)
-    {
-        if (k < 0 || !res_ring.on() || !in_step) return FS_OK;
-        ScopedSpan sp(S, FAM_RESIDUAL);
-        fs::launch_residual<T>(S->stream, g, b, arr[x], arr[rhs], flags, a, c, res_partial, res_slot(res_ring.at.next(), k, when));
-        if (when == 1) res_ran_now |= 1u << k;
-        return FS_OK;
-    }
-
-    int residual_query(int b, int field, int prev, double a, double c, double* out4, double* per_plane)
-    {
-        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
-        int rc = ensure_flags();
-        if (rc) return rc;
-        // a boundary plane's record reads the neighbour's plane of x: one exchange, on the query's account only
-        if ((rc = halo(arr[slot[field]]))) return rc;
-        if ((rc = ensure_res_partial())) return rc;
-        const size_t n = res_plane_doubles();
-        if (!res_scratch) HIP_TRY(hipMalloc((void**)&res_scratch, n * sizeof(double)));
-        {
-            ScopedSpan sp(S, FAM_RESIDUAL);
-            fs::launch_residual<T>(S->stream, g, b, arr[slot[field]], arr[slot[prev]], flags, a, c, res_partial, res_scratch);
-        }
-        std::vector<double> mine(n), all;
-        HIP_TRY(hipMemcpyAsync(mine.data(), res_scratch, n * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-        HIP_TRY(hipStreamSynchronize(S->stream));
-        if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
-        combine_planes([&](int r, int zl) { return &all[(size_t)r * n + (size_t)zl * fs::RESIDUAL_REC]; }, out4, fs::RESIDUAL_REC, 2);
-        if (per_plane) memcpy(per_plane, all.data(), all.size() * sizeof(double));
-        return FS_OK;
-    }
-    int solve_residual(int b, int field, int prev, double a, double c, double* out4, double* per_plane) override
-    {
-        if (!std::is_same<T, double>::value) { a = (double)(float)a; c = (double)(float)c; }   // what an fp32 solve would use
-        return residual_query(b, field, prev, a, c, out4, per_plane);
-    }
-    int diffuse_residual(int b, int field, int prev, double* out4, double* per_plane) override
-    {
-        const T a = diffusion_a();
-        return residual_query(b, field, prev, (double)a, (double)((T)1 + (T)6 * a), out4, per_plane);
-    }
-
-    int residual_log_fetch(double* rows, long max_rows, long* n_rows, long* n_dropped) override
-    {
-        int rc = ensure_residual_ring();
-        if (rc) return rc;
-        const long n = res_ring.at.retained();
-        rc = res_ring.fetch_begin({"fs_residual_log", "rows", "rows = NULL"}, n, max_rows, rows != nullptr, n_rows, n_dropped);
-        if (rc != LogRing::GO_ON) return rc;
-        if (S->comm.active() && S->comm.null_transport) return fail(FS_EINVAL, "solve residuals need the other slabs' planes; the FSNULL transport carries none");
-        const size_t rec = res_plane_doubles(), per = (size_t)RES_SOLVES * 2 * rec;   // one step: six solves, before and after
-        std::vector<double> mine((size_t)n * per), all;
-        HIP_TRY(res_ring.fetch_copy(S->stream, mine.data()));
-        if ((rc = gather_plane_records(mine, all, "solve residuals"))) return rc;
-        const size_t blob = mine.size();
-        const double nan = std::nan("");
-        for (long i = 0; i < n; ++i) {
-            double* o = rows + (size_t)i * FS_RESIDUAL_LOG_COLS;
-            o[0] = (double)res_ring.at.step_of(i);
-            for (int j = 0; j < RES_SOLVES; ++j) {
-                double* q = o + 1 + 5 * j;               // r0_sq, r_sq, r_max, rhs_sq, cells
-                if (!(res_ring.at.tag_of(i) >> j & 1u)) { q[0] = q[1] = q[2] = q[3] = nan; q[4] = 0.0; continue; }
-                double s[2][fs::RESIDUAL_REC];
-                for (int when = 0; when < 2; ++when)
-                    combine_planes([&](int r, int zl) {
-                        return &all[(size_t)r * blob + (size_t)i * per + ((size_t)j * 2 + (size_t)when) * rec + (size_t)zl * fs::RESIDUAL_REC]; },
-                        s[when], fs::RESIDUAL_REC, 2);
-                q[0] = s[0][0];
-                q[1] = s[1][0];
-                q[2] = s[1][2];
-                q[3] = s[1][1];
-                q[4] = s[1][3];
-            }
-        }
-        res_ring.fetch_end();
-        return FS_OK;
-    }
 };
 
 int ensure_engine(fs_sim* s)
@@ -3940,6 +1597,10 @@ int ensure_engine(fs_sim* s)
     }
     return FS_OK;
 }
+
+// The call `call` on the engine of the handle's precision: ENG(s, step()), ENG(s, monitor.sample()).  Its arguments are
+// evaluated once, in the branch taken.
+#define ENG(s, call) ((s)->fp64 ? static_cast<Engine<double>*>((s)->eng)->call : static_cast<Engine<float>*>((s)->eng)->call)
 
 bool in_box(fs_sim* s, int x, int y, int z) { return x >= 1 && x <= s->W && y >= 1 && y <= s->H && z >= 1 && z <= s->D; }
 
@@ -4098,7 +1759,7 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         s->image_gen++;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
-            return s->eng->image_config();
+            return ENG(s, images.config());
         }
     } else if (k == "tracers" || k == "tracer_log") {
         const bool pool = (k == "tracers");
@@ -4112,7 +1773,7 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         else { s->tracer_log = (int)num; s->tracer_log_gen++; }
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
-            return s->eng->tracer_config();
+            return ENG(s, tracers.config());
         }
         if (pool) s->tracer_seeded = 0;
     } else if (k == "tracer_every") {
@@ -4128,7 +1789,7 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         s->volume_gen++;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
-            return s->eng->volume_config();
+            return ENG(s, volume.config());
         }
     } else if (k == "monitor_log") {
         if (s->comm.active()) return fail(FS_EINVAL, "monitor_log: the flow monitor needs a single-GPU handle");
@@ -4178,7 +1839,7 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         s->flow_stats_n = 0;
         if (s->eng) {                                    // allocate or free now; a handle not yet in use does so at its first use
             hipSetDevice(s->device);
-            return s->eng->flow_stats_config();
+            return ENG(s, flow_stats.config());
         }
     } else if (k == "flow_stats_every" || k == "flow_stats_start") {
         const bool every = (k == "flow_stats_every");
@@ -4265,15 +1926,15 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "local_depth") *out = s->comm.active() ? s->comm.local_depth(s->D) : s->D;
     else if (n == "z_offset") *out = s->comm.active() ? s->comm.z_offset(s->D) : 0;
     else if (n == "last_advect_reach") *out = s->last_reach;
-    else if (n == "pair_shape") *out = s->eng ? s->eng->tuned_two() : -1;
-    else if (n == "triple_plan") *out = s->eng ? s->eng->tuned_three() : -1;
+    else if (n == "pair_shape") *out = s->eng ? ENG(s, tuned_two()) : -1;
+    else if (n == "triple_plan") *out = s->eng ? ENG(s, tuned_three()) : -1;
     else if (n == "zero_start_projections") *out = s->n_zero_start;        // projections whose solve started from unread zeros
     else if (n == "project_advect_steps") *out = s->n_project_advect;      // steps whose first gradient ran inside the advection
     else if (n == "two_sweep_fused")   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
-        *out = (s->eng && fs::decode_plan(false, s->eng->tuned_two()).kind == fs::SweepKernel::Fused2) ? 1 : 0;
-    else if (n == "halo_depth") *out = s->eng ? s->eng->halo_depth() : 0;
-    else if (n == "mg_levels") *out = s->eng ? s->eng->multigrid_levels() : 0;          // levels of the last solver=mg solve, level 0 included
-    else if (n == "mg_first_replicated") *out = s->eng ? s->eng->multigrid_first_replicated() : 0;   // ... the first held whole by every rank
+        *out = (s->eng && fs::decode_plan(false, ENG(s, tuned_two())).kind == fs::SweepKernel::Fused2) ? 1 : 0;
+    else if (n == "halo_depth") *out = s->eng ? ENG(s, halo_depth()) : 0;
+    else if (n == "mg_levels") *out = s->eng ? ENG(s, multigrid_levels()) : 0;          // levels of the last solver=mg solve, level 0 included
+    else if (n == "mg_first_replicated") *out = s->eng ? ENG(s, multigrid_first_replicated()) : 0;   // ... the first held whole by every rank
     // z-slab runs: the communication schedule in force (what "auto" chose), and the slab step's host-side waits
     else if (n == "overlap_plan") *out = s->overlap_plan;
     else if (n == "comm_cus_plan") *out = s->cus_plan;
@@ -4288,7 +1949,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
         int b = 0, c = 0;
         { int rc_ = ensure_engine(s); if (rc_) return rc_; }
         hipSetDevice(s->device);
-        const int rc = s->eng->body_counts(&b, &c);
+        const int rc = ENG(s, bodies.counts(&b, &c));
         if (rc) return rc;
         *out = (n == "body_count") ? b : c;
     }
@@ -4356,21 +2017,21 @@ int fs_add_obstacle(fs_sim* s, int x, int y, int z)
 {
     ENGINE_OR_RETURN(s);
     if (!in_box(s, x, y, z)) return fail(FS_EINVAL, "addObstacle(%d,%d,%d) outside 1..%dx1..%dx1..%d", x, y, z, s->W, s->H, s->D);
-    return s->eng->point(FS_OBS, x, y, z, 1.0f, 1);
+    return ENG(s, point(FS_OBS, x, y, z, 1.0f, 1));
 }
 int fs_add_density(fs_sim* s, int x, int y, int z, float amount)
 {
     ENGINE_OR_RETURN(s);
     if (!in_box(s, x, y, z)) return fail(FS_EINVAL, "addDensity(%d,%d,%d) outside the grid", x, y, z);
-    return s->eng->point(FS_DENS, x, y, z, amount, 0);
+    return ENG(s, point(FS_DENS, x, y, z, amount, 0));
 }
 int fs_set_velocity(fs_sim* s, int x, int y, int z, float ax, float ay, float az)
 {
     ENGINE_OR_RETURN(s);
     if (!in_box(s, x, y, z)) return fail(FS_EINVAL, "setVelocity(%d,%d,%d) outside the grid", x, y, z);
-    int rc = s->eng->point(FS_VX, x, y, z, ax, 1);
-    if (!rc) rc = s->eng->point(FS_VY, x, y, z, ay, 1);
-    if (!rc) rc = s->eng->point(FS_VZ, x, y, z, az, 1);
+    int rc = ENG(s, point(FS_VX, x, y, z, ax, 1));
+    if (!rc) rc = ENG(s, point(FS_VY, x, y, z, ay, 1));
+    if (!rc) rc = ENG(s, point(FS_VZ, x, y, z, az, 1));
     return rc;
 }
 
@@ -4378,7 +2039,7 @@ int fs_set_obstacle_mask(fs_sim* s, const uint8_t* mask, size_t n)
 {
     ENGINE_OR_RETURN(s);
     if (!mask) return fail(FS_EINVAL, "null mask");
-    return s->eng->set_mask(mask, n);
+    return ENG(s, set_mask(mask, n));
 }
 
 int fs_load_stl(fs_sim* s, const char* stl_file, float scale, float rot_x, float rot_y, float rot_z,
@@ -4404,14 +2065,14 @@ int fs_load_stl(fs_sim* s, const char* stl_file, float scale, float rot_x, float
         return rc == FS_EIO ? fail(FS_EIO, "%s", msg.c_str()) : fail(rc, "voxelizer: %s", msg.c_str());
     }
     if (added) *added = vr.added;
-    rc = s->eng->apply_solid_cells(vr.d_cells, vr.added);
+    rc = ENG(s, apply_solid_cells(vr.d_cells, vr.added));
     hipStreamSynchronize(s->stream);
     fs::voxelize_free(&vr);
     return rc;
 }
 
-int fs_step(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->step(); }
-int fs_run_one(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->run_one(); }
+int fs_step(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, step()); }
+int fs_run_one(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, run_one()); }
 
 int fs_sync(fs_sim* s)
 {
@@ -4441,17 +2102,17 @@ int fs_run(fs_sim* s)
     s->step_no = 0;
     int rc = FS_OK;
     for (int i = 0; i < s->iter && !rc; ++i) {
-        rc = s->eng->run_one();
+        rc = ENG(s, run_one());
         if (!rc && (i + 1) % 100 == 0 && i > 0) {         // :73-77
             // one GPU: the reference's own float sum, digit for digit; z-slabs: the all-reduced double sum (a rounding
             // chain over the whole array does not split over ranks)
             double st[3] = {0, 0, 0};
-            if (s->comm.active()) rc = s->eng->stats(FS_DENS, st);
-            else if (talk) rc = s->eng->reference_order_sum(FS_DENS, &st[0]);
+            if (s->comm.active()) rc = ENG(s, stats(FS_DENS, st));
+            else if (talk) rc = ENG(s, reference_order_sum(FS_DENS, &st[0]));
             if (!rc && talk) printf("step %d\n  density sum = %g\n", i + 1, st[0]);
         }
     }
-    if (!rc && s->dump_every == -1) rc = s->eng->dump_frame();
+    if (!rc && s->dump_every == -1) rc = ENG(s, dump_frame());
     s->in_run = false;
     {
         std::string werr;
@@ -4463,7 +2124,7 @@ int fs_run(fs_sim* s)
     if (talk) printf("\n--- statistics -------------------------------------------------\n");   // :81
     for (int k = 0; k < 4; ++k) {
         double st[3];
-        rc = s->eng->stats(which[k], st);
+        rc = ENG(s, stats(which[k], st));
         if (rc) return rc;
         if (talk) printf("%s min = %g\n%s max = %g\n", label[k], st[1], label[k], st[2]);          // :82-89
     }
@@ -4474,38 +2135,38 @@ int fs_run(fs_sim* s)
 #define CHECK_FIELD(f) if ((f) < 0 || (f) >= FS_NFIELDS) return fail(FS_EINVAL, "bad field selector %d", (f));
 #define CHECK_B(b) if ((b) < 0 || (b) > 3) return fail(FS_EINVAL, "bad boundary code %d", (b));
 
-int fs_set_bounds(fs_sim* s, int b, int field) { ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); return s->eng->set_bounds(b, field); }
+int fs_set_bounds(fs_sim* s, int b, int field) { ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); return ENG(s, set_bounds(b, field)); }
 int fs_linear_solver(fs_sim* s, int b, int field, int prev, float a, float c)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (field == prev) return fail(FS_EINVAL, "field and prev must differ");
-    return s->eng->linear_solver(b, field, prev, a, c);
+    return ENG(s, linear_solver(b, field, prev, a, c));
 }
 int fs_diffuse(fs_sim* s, int b, int field, int prev)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (field == prev) return fail(FS_EINVAL, "field and prev must differ");
-    return s->eng->diffuse(b, field, prev);
+    return ENG(s, diffuse(b, field, prev));
 }
-int fs_project(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->project(); }
+int fs_project(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, project()); }
 int fs_advect(fs_sim* s, int b, int field, int prev)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (field == prev) return fail(FS_EINVAL, "field and prev must differ");
-    return s->eng->advect(b, field, prev);
+    return ENG(s, advect(b, field, prev));
 }
 
 int fs_get_field(fs_sim* s, int which, void* dst, size_t n, int elem_size)
 {
     ENGINE_OR_RETURN(s); CHECK_FIELD(which);
     if (!dst) return fail(FS_EINVAL, "null buffer");
-    return s->eng->get_field(which, dst, n, elem_size);
+    return ENG(s, get_field(which, dst, n, elem_size));
 }
 int fs_set_field(fs_sim* s, int which, const void* src, size_t n, int elem_size)
 {
     ENGINE_OR_RETURN(s); CHECK_FIELD(which);
     if (!src) return fail(FS_EINVAL, "null buffer");
-    return s->eng->set_field(which, src, n, elem_size);
+    return ENG(s, set_field(which, src, n, elem_size));
 }
 size_t fs_padded_size(fs_sim* s)
 {
@@ -4514,13 +2175,13 @@ size_t fs_padded_size(fs_sim* s)
     return (size_t)(s->W + 2) * (s->H + 2) * (d + 2);
 }
 
-int fs_dump_frame(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->dump_frame(); }
+int fs_dump_frame(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, dump_frame()); }
 
 int fs_field_stats(fs_sim* s, int which, double* sum, double* mn, double* mx)
 {
     ENGINE_OR_RETURN(s); CHECK_FIELD(which);
     double st[3];
-    int rc = s->eng->stats(which, st);
+    int rc = ENG(s, stats(which, st));
     if (rc) return rc;
     if (sum) *sum = st[0];
     if (mn) *mn = st[1];
@@ -4554,14 +2215,14 @@ int fs_time_sweeps(fs_sim* s, int b, int field, int prev, float a, float c, int 
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (!ms_per_sweep) return fail(FS_EINVAL, "null output");
-    return s->eng->time_sweeps(b, field, prev, a, c, reps, ms_per_sweep);
+    return ENG(s, time_sweeps(b, field, prev, a, c, reps, ms_per_sweep));
 }
 
 int fs_streamlines(fs_sim* s, int density, double proximity, int max_length, double step_size,
                    double vel_change_threshold, long* n_lines, long* n_points)
 {
     ENGINE_OR_RETURN(s);
-    int rc = s->eng->streamlines(density, proximity, max_length, step_size, vel_change_threshold);
+    int rc = ENG(s, viewer.streamlines(density, proximity, max_length, step_size, vel_change_threshold));
     if (rc) return rc;
     if (n_lines) *n_lines = (long)s->sl_norm.size();
     if (n_points) *n_points = (long)(s->sl_points.size() / 3);
@@ -4581,7 +2242,7 @@ int fs_streamlines_fetch(fs_sim* s, long* offsets, double* points, double* norm_
 int fs_obstacle_surface(fs_sim* s, long* n_vertices, long* n_triangles)
 {
     ENGINE_OR_RETURN(s);
-    int rc = s->eng->obstacle_surface();
+    int rc = ENG(s, viewer.obstacle_surface());
     if (rc) return rc;
     if (n_vertices) *n_vertices = (long)(s->surf_verts.size() / 3);
     if (n_triangles) *n_triangles = (long)(s->surf_tris.size() / 3);
@@ -4600,7 +2261,7 @@ int fs_obstacle_surface_fetch(fs_sim* s, float* vertices, int* triangles)
 int fs_isosurface(fs_sim* s, int source, double level, long* n_vertices, long* n_triangles)
 {
     ENGINE_OR_RETURN(s);
-    int rc = s->eng->isosurface(source, level);
+    int rc = ENG(s, vortex.isosurface(source, level));
     if (rc) return rc;
     if (n_vertices) *n_vertices = (long)(s->iso_verts.size() / 3);
     if (n_triangles) *n_triangles = (long)(s->iso_tris.size() / 3);
@@ -4628,63 +2289,63 @@ int fs_obstacle_force(fs_sim* s, double out[5], double* per_plane)
 {
     ENGINE_OR_RETURN(s);
     if (!out) return fail(FS_EINVAL, "null output");
-    return s->eng->obstacle_force(out, per_plane);
+    return ENG(s, forces.obstacle_force(out, per_plane));
 }
 
 int fs_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->force_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, forces.log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 
 int fs_label_bodies(fs_sim* s, long* n_components, long* n_bodies)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->label_bodies(n_components, n_bodies);
+    return ENG(s, bodies.label(n_components, n_bodies));
 }
 int fs_body_labels(fs_sim* s, int32_t* dst, size_t n)
 {
     ENGINE_OR_RETURN(s);
     if (!dst) return fail(FS_EINVAL, "null buffer");
-    return s->eng->body_labels(dst, n);
+    return ENG(s, bodies.labels(dst, n));
 }
 int fs_body_info(fs_sim* s, double* rows, long max_rows, long* n_rows)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->body_info(rows, max_rows, n_rows);
+    return ENG(s, bodies.info(rows, max_rows, n_rows));
 }
 int fs_body_force(fs_sim* s, double* out, long max_rows, long* n_rows, double* per_plane)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->body_force(out, max_rows, n_rows, per_plane);
+    return ENG(s, bodies.query(out, max_rows, n_rows, per_plane));
 }
 int fs_body_force_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->body_force_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, bodies.log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 
 int fs_solve_residual(fs_sim* s, int b, int field, int prev, double a, double c, double out[4], double* per_plane)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (!out) return fail(FS_EINVAL, "null output");
-    return s->eng->solve_residual(b, field, prev, a, c, out, per_plane);
+    return ENG(s, residual.solve_residual(b, field, prev, a, c, out, per_plane));
 }
 
 int fs_diffuse_residual(fs_sim* s, int b, int field, int prev, double out[4], double* per_plane)
 {
     ENGINE_OR_RETURN(s); CHECK_B(b); CHECK_FIELD(field); CHECK_FIELD(prev);
     if (!out) return fail(FS_EINVAL, "null output");
-    return s->eng->diffuse_residual(b, field, prev, out, per_plane);
+    return ENG(s, residual.diffuse_residual(b, field, prev, out, per_plane));
 }
 
 int fs_residual_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->residual_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, residual.log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 
-int fs_flow_stats_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->flow_stats_sample(); }
+int fs_flow_stats_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, flow_stats.sample()); }
 int fs_flow_stats_reset(fs_sim* s)
 {
     if (!s) return fail(FS_EINVAL, "null handle");
@@ -4695,37 +2356,37 @@ int fs_flow_stats_field(fs_sim* s, int which, void* dst, size_t n_elems, int ele
 {
     ENGINE_OR_RETURN(s);
     if (!dst) return fail(FS_EINVAL, "null buffer");
-    return s->eng->flow_stats_field(which, dst, n_elems, elem_size);
+    return ENG(s, flow_stats.field(which, dst, n_elems, elem_size));
 }
 int fs_flow_stats_dump(fs_sim* s, const char* dir)
 {
     ENGINE_OR_RETURN(s);
     if (!dir) return fail(FS_EINVAL, "null directory");
-    return s->eng->flow_stats_dump(dir);
+    return ENG(s, flow_stats.dump(dir));
 }
 
 int fs_vortex_field(fs_sim* s, int which, void* dst, size_t n_elems, int elem_size)
 {
     ENGINE_OR_RETURN(s);
     if (!dst) return fail(FS_EINVAL, "null buffer");
-    return s->eng->vortex_field(which, dst, n_elems, elem_size);
+    return ENG(s, vortex.fetch(which, dst, n_elems, elem_size));
 }
 int fs_flow_monitor(fs_sim* s, double out[16], double* per_plane, double* x_profile)
 {
     ENGINE_OR_RETURN(s);
     if (!out) return fail(FS_EINVAL, "null argument");
-    return s->eng->flow_monitor(out, per_plane, x_profile);
+    return ENG(s, monitor.query(out, per_plane, x_profile));
 }
-int fs_monitor_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->monitor_sample(); }
+int fs_monitor_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, monitor.sample()); }
 int fs_monitor_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->monitor_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, monitor.log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 int fs_confine_vorticity(fs_sim* s, double epsilon)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->confine_vorticity(epsilon);
+    return ENG(s, confine.vorticity(epsilon));
 }
 int fs_heat_params(fs_sim* s, const double* par, int n)
 {
@@ -4750,7 +2411,7 @@ int fs_heat_params(fs_sim* s, const double* par, int n)
                         name[lo], name[hi], ext[a]);
     }
     if (!whole(fs::HP_LOG, 0, 1048576)) return fail(FS_EINVAL, "fs_heat_params: par[14] (log) is a record count 0 .. 2^20");
-    return s->eng->heat_config(par);
+    return ENG(s, heat.config(par));
 }
 int fs_heat_params_get(fs_sim* s, double* par, int n)
 {
@@ -4759,30 +2420,30 @@ int fs_heat_params_get(fs_sim* s, double* par, int n)
     for (int k = 0; k < FS_HEAT_PARAMS; ++k) par[k] = s->heat[k];
     return FS_OK;
 }
-int fs_heat_apply(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->heat_apply(); }
-int fs_heat_transport(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->heat_transport(); }
+int fs_heat_apply(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, heat.apply()); }
+int fs_heat_transport(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, heat.transport()); }
 int fs_heat_budget(fs_sim* s, double out[FS_HEAT_COLS], double* per_plane)
 {
     ENGINE_OR_RETURN(s);
     if (!out) return fail(FS_EINVAL, "fs_heat_budget: null argument");
-    return s->eng->heat_budget(out, per_plane);
+    return ENG(s, heat.budget(out, per_plane));
 }
 int fs_heat_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->heat_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, heat.log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 int fs_heat_get(fs_sim* s, void* dst, size_t n_elems, int elem_size)
 {
     ENGINE_OR_RETURN(s);
     if (!dst) return fail(FS_EINVAL, "fs_heat_get: null buffer");
-    return s->eng->heat_get(dst, n_elems, elem_size);
+    return ENG(s, heat.get(dst, n_elems, elem_size));
 }
 int fs_heat_set(fs_sim* s, const void* src, size_t n_elems, int elem_size)
 {
     ENGINE_OR_RETURN(s);
     if (!src) return fail(FS_EINVAL, "fs_heat_set: null buffer");
-    return s->eng->heat_set(src, n_elems, elem_size);
+    return ENG(s, heat.set(src, n_elems, elem_size));
 }
 int fs_inflow_profile(fs_sim* s, const double* u, const double* rms, size_t n)
 {
@@ -4816,7 +2477,7 @@ int fs_inflow_plane(fs_sim* s, long step, double* out, size_t n)
     ENGINE_OR_RETURN(s);
     if (!out) return fail(FS_EINVAL, "null buffer");
     if (n != (size_t)3 * s->H * s->D) return fail(FS_EINVAL, "fs_inflow_plane: room for %zu values, the plane has 3 * height * depth = %zu", n, (size_t)3 * s->H * s->D);
-    return s->eng->inflow_plane(step, out);
+    return ENG(s, inflow.plane(step, out));
 }
 int fs_inflow_eddies(fs_sim* s, long step, double* out, size_t n)
 {
@@ -4824,13 +2485,13 @@ int fs_inflow_eddies(fs_sim* s, long step, double* out, size_t n)
     if (n != (size_t)6 * s->inflow_n) return fail(FS_EINVAL, "fs_inflow_eddies: room for %zu values, there are 6 * %d", n, s->inflow_n);
     if (n == 0) return FS_OK;
     if (!out) return fail(FS_EINVAL, "null buffer");
-    return s->eng->inflow_eddies(step, out);
+    return ENG(s, inflow.eddies(step, out));
 }
 int fs_vortex_dump(fs_sim* s, const char* dir)
 {
     ENGINE_OR_RETURN(s);
     if (!dir) return fail(FS_EINVAL, "null directory");
-    return s->eng->vortex_dump(dir);
+    return ENG(s, vortex.dump(dir));
 }
 
 int fs_sample_points(fs_sim* s, const double* xyz, long n)
@@ -4838,12 +2499,12 @@ int fs_sample_points(fs_sim* s, const double* xyz, long n)
     ENGINE_OR_RETURN(s);
     if (n < 0 || n > (1L << 24)) return fail(FS_EINVAL, "fs_sample_points: 0 .. 16777216 points, got %ld", n);
     if (n > 0 && !xyz) return fail(FS_EINVAL, "fs_sample_points: null points");
-    return s->eng->sample_points(xyz, n);
+    return ENG(s, sampling.points(xyz, n));
 }
 int fs_sample(fs_sim* s, int source, int mode, double* out, long n)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->sample(source, mode, out, n);
+    return ENG(s, sampling.sample(source, mode, out, n));
 }
 int fs_set_probes(fs_sim* s, const int* cells_xyz, long n)
 {
@@ -4861,24 +2522,24 @@ int fs_set_probes(fs_sim* s, const int* cells_xyz, long n)
     s->probe_gen++;
     return FS_OK;
 }
-int fs_probe_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->probe_sample(); }
+int fs_probe_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, sampling.probe_sample()); }
 int fs_probe_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->probe_log_fetch(rows, max_rows, n_rows, n_dropped);
+    return ENG(s, sampling.probe_log_fetch(rows, max_rows, n_rows, n_dropped));
 }
 
 // ---- slice and projection images ------------------------------------------------------------------------------
 int fs_image_values(fs_sim* s, int source, int kind, int axis, int index, double* out, size_t n, int* cols, int* rows)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->image_values(source, kind, axis, index, out, n, cols, rows);
+    return ENG(s, images.values(source, kind, axis, index, out, n, cols, rows));
 }
 int fs_image_rgb(fs_sim* s, int source, int kind, int axis, int index, double vmin, double vmax, double obstacle_alpha,
                  uint8_t* out, size_t n_bytes, int* cols, int* rows)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->image_rgb(source, kind, axis, index, vmin, vmax, obstacle_alpha, out, n_bytes, cols, rows);
+    return ENG(s, images.rgb(source, kind, axis, index, vmin, vmax, obstacle_alpha, out, n_bytes, cols, rows));
 }
 int fs_image_colormap(fs_sim* s, const uint8_t* rgb, int n)
 {
@@ -4916,15 +2577,15 @@ int fs_image_views(fs_sim* s, const int* spec, const double* range, int n)
     s->image_gen++;
     if (s->eng) {
         hipSetDevice(s->device);
-        return s->eng->image_config();
+        return ENG(s, images.config());
     }
     return FS_OK;
 }
-int fs_image_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->image_sample(); }
+int fs_image_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, images.sample()); }
 int fs_image_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->image_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
+    return ENG(s, images.log_fetch(frames, steps, max_frames, n_frames, n_dropped));
 }
 
 // ---- volume rendering -------------------------------------------------------------------------------------------------------
@@ -4943,13 +2604,13 @@ int volume_set_rays(fs_sim* s, const char* who, int slot, const double* rays, in
     if (used && (size_t)s->volume_log * volume_frame_bytes(s, s->volume_views, slot, cols, rows) > ((size_t)1 << 30))
         return fail(FS_EINVAL, "%s: %d frames (\"volume_log\") of %zu bytes exceed 1 GiB", who, s->volume_log,
                     volume_frame_bytes(s, s->volume_views, slot, cols, rows));
-    const int rc = s->eng->volume_rays(slot, rays, cols, rows);
+    const int rc = ENG(s, volume.set_rays(slot, rays, cols, rows));
     if (rc) return rc;
     s->vol_cols[slot] = cols;
     s->vol_rows[slot] = rows;
     if (!used) return FS_OK;
     s->volume_gen++;                                     // a view uses the slot: the log is cleared
-    return s->eng->volume_config();
+    return ENG(s, volume.config());
 }
 int volume_rays_args(fs_sim* s, const char* who, int slot, int cols, int rows, bool may_free)
 {
@@ -4999,7 +2660,7 @@ int fs_volume_render(fs_sim* s, int source, int slot, const double* par, uint8_t
         return fail(FS_EINVAL, "fs_volume_render: the image has %d x %d x 3 bytes, the call has room for %zu", s->vol_cols[slot], s->vol_rows[slot], n_bytes);
     if (acc && n_acc != 4 * npix)
         return fail(FS_EINVAL, "fs_volume_render: the image has %d x %d x 4 values, the call has room for %zu", s->vol_cols[slot], s->vol_rows[slot], n_acc);
-    return s->eng->volume_render(source, slot, par, rgb, n_bytes, acc, n_acc);
+    return ENG(s, volume.render(source, slot, par, rgb, n_bytes, acc, n_acc));
 }
 int fs_volume_views(fs_sim* s, const int* spec, const double* par, int n)
 {
@@ -5024,15 +2685,15 @@ int fs_volume_views(fs_sim* s, const int* spec, const double* par, int n)
     s->volume_gen++;
     if (s->eng) {
         hipSetDevice(s->device);
-        return s->eng->volume_config();
+        return ENG(s, volume.config());
     }
     return FS_OK;
 }
-int fs_volume_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->volume_sample(); }
+int fs_volume_sample(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, volume.sample()); }
 int fs_volume_log(fs_sim* s, uint8_t* frames, long* steps, long max_frames, long* n_frames, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->volume_log_fetch(frames, steps, max_frames, n_frames, n_dropped);
+    return ENG(s, volume.log_fetch(frames, steps, max_frames, n_frames, n_dropped));
 }
 
 // ---- tracer particles -----------------------------------------------------------------------------------------------------
@@ -5054,7 +2715,7 @@ int fs_tracer_seed(fs_sim* s, const double* xyz, long n)
     if (!tracer_points_ok(s, xyz, n, &bad))
         return fail(FS_EINVAL, "fs_tracer_seed: point %ld (%g,%g,%g) outside 0.5..%d.5 x 0.5..%d.5 x 0.5..%d.5", bad, xyz[3 * bad],
                     xyz[3 * bad + 1], xyz[3 * bad + 2], s->W, s->H, s->D);
-    return s->eng->tracer_seed(xyz, n);
+    return ENG(s, tracers.seed(xyz, n));
 }
 int fs_tracer_emitters(fs_sim* s, const double* xyz, long n, long every)
 {
@@ -5072,22 +2733,22 @@ int fs_tracer_emitters(fs_sim* s, const double* xyz, long n, long every)
     s->tracer_emit_gen++;
     return FS_OK;
 }
-int fs_tracer_clear(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->tracer_clear(); }
-int fs_tracer_advance(fs_sim* s) { ENGINE_OR_RETURN(s); return s->eng->tracer_advance(); }
+int fs_tracer_clear(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, tracers.clear()); }
+int fs_tracer_advance(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, tracers.advance()); }
 int fs_tracer_fetch(fs_sim* s, double* xyz, int32_t* meta, long max, long* n)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->tracer_fetch(xyz, meta, max, n);
+    return ENG(s, tracers.fetch(xyz, meta, max, n));
 }
 int fs_tracer_sample(fs_sim* s, int source, int mode, double* out, long n)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->tracer_sample(source, mode, out, n);
+    return ENG(s, tracers.sample(source, mode, out, n));
 }
 int fs_tracer_log(fs_sim* s, double* xyz, int32_t* status, long* steps, long max_frames, long* n_frames, long* n_dropped)
 {
     ENGINE_OR_RETURN(s);
-    return s->eng->tracer_log_fetch(xyz, status, steps, max_frames, n_frames, n_dropped);
+    return ENG(s, tracers.log_fetch(xyz, status, steps, max_frames, n_frames, n_dropped));
 }
 
 // An 8-bit RGB, non-interlaced PNG whose one IDAT chunk is a zlib stream of stored deflate blocks: filter type 0 on every
