@@ -6,7 +6,7 @@
 // there is no CPU fallback: without a usable HIP device fs_create fails.
 //
 // Orchestration follows Simulation::step()/run() of the reference (simulation.cpp:49-150);
-// every numeric expression lives in kernels.hip.
+// every numeric expression lives in the kernel files (kernels_dev.h lists them).
 //
 // One translation unit: this file holds the core of Engine<T> (the reference's step) and the C entries; each feature
 // beyond the reference is a part of the engine in driver/<feature>.h, over driver/common.h.

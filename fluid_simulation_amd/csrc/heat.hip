@@ -18,42 +18,10 @@ static_assert(HEAT_SOLID == F_SOLID && HEAT_NEAR == F_NEAR, "heat.h restates two
 
 constexpr int HEAT_RY = 2;
 
-// The lane's four cells of an interior row of a field with boundary code b, the way set_bounds leaves them: `u` un-zeroed
-// values, `killmask` bit e set => cell e is zeroed; the ghost faces this row determines take the un-zeroed values (both z
-// walls are physical: single GPU).  Writes cells x0-1 .. x0+4 <= W+3 < sy of rows y-1 .. y+1 of planes z-1 .. z+1.
-template <class T>
-__device__ __forceinline__ void heat_store_row(const GridDesc& g, T* dst, long base, int x0, int y, int z, const T (&u)[4],
-                                               unsigned killmask, int b)
-{
-    const T zero = (T)0;
-    V4<T> st;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int x = x0 + e;
-        const T ghost_src = (e > 0) ? u[e - 1] : zero;   // the ghost face x = W + 1 (e > 0 there: x0 <= W)
-        st.e[e] = (x <= g.W) ? (((killmask >> e) & 1u) ? zero : u[e]) : ((x == g.W + 1) ? ghost_src : zero);
-    }
-    *reinterpret_cast<V4<T>*>(dst + base) = st;
-    if (x0 == 1) dst[base - 1] = (b == 1) ? -u[0] : u[0];
-    if (x0 + 3 == g.W) dst[base + 4] = u[3];
-    if (y == 1 || y == g.H || z == 1 || z == g.D) {
-        V4<T> gy, gz;                                    // the box edges beyond x = W take +0.0
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = (x0 + e <= g.W);
-            gy.e[e] = in ? ((b == 2) ? -u[e] : u[e]) : zero;
-            gz.e[e] = in ? ((b == 3) ? -u[e] : u[e]) : zero;
-        }
-        if (y == 1) *reinterpret_cast<V4<T>*>(dst + base - g.sy) = gy;
-        if (y == g.H) *reinterpret_cast<V4<T>*>(dst + base + g.sy) = gy;
-        if (z == 1) *reinterpret_cast<V4<T>*>(dst + base - g.sz) = gz;
-        if (z == g.D) *reinterpret_cast<V4<T>*>(dst + base + g.sz) = gz;
-    }
-}
-
 // FORCE = false (beta = alpha = 0): the velocity and the density are neither read nor written.
 // Reads and writes rows 1..H of planes zbeg..zend at the 16-byte groups that start at cells x0 <= W (inside the padded row:
-// x0 + 3 <= W + 3 < sy), and the ghost cells beside them (heat_store_row); the flag bytes as one word at the same index.
+// x0 + 3 <= W + 3 < sy), and the ghost cells beside them (store_row_bounds, kernels_dev.h:
+// cells x0-1 .. x0+4 <= W+3 < sy of rows y-1 .. y+1 of planes z-1 .. z+1); the flag bytes as one word at the same index.
 template <class T, bool FORCE>
 __global__ __launch_bounds__(256) void heat_apply_kernel(GridDesc g, HeatPass hp, T* __restrict__ theta, T* __restrict__ vup,
                                                           const T* __restrict__ dens, const uint8_t* __restrict__ flags,
@@ -63,6 +31,7 @@ __global__ __launch_bounds__(256) void heat_apply_kernel(GridDesc g, HeatPass hp
     const MarchTile<T> t = march_tile<T, RY>(g, zc_len, nxw, nybg, nblk);
     if (!t.live) return;                                 // wave-uniform
     const int bv = 1 + (hp.up >> 1);                     // the boundary code of the component along `up`
+    const SlabCtx whole = { 0, g.D, 1, 1 };              // both z walls are physical: single GPU
     for (int z = t.zbeg; z <= t.zend; ++z) {
         const long off = t.row0 + (long)z * g.sz;
         T th[RY][4], v[RY][4], q[RY][4];
@@ -92,8 +61,8 @@ __global__ __launch_bounds__(256) void heat_apply_kernel(GridDesc g, HeatPass hp
                 tn[e] = heat_working<T>(hp, th[r][e], f, t.x0 + e, y, z);
                 if constexpr (FORCE) vn[e] = heat_buoyancy<T>(hp, v[r][e], tn[e], q[r][e]);
             }
-            heat_store_row<T>(g, theta, base, t.x0, y, z, tn, kill_t, 0);
-            if constexpr (FORCE) heat_store_row<T>(g, vup, base, t.x0, y, z, vn, kill_v, bv);
+            store_row_bounds<T>(g, whole, theta, base, t.x0, y, z, tn, kill_t, 0);
+            if constexpr (FORCE) store_row_bounds<T>(g, whole, vup, base, t.x0, y, z, vn, kill_v, bv);
         }
     }
 }

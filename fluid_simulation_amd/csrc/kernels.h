@@ -1,5 +1,5 @@
 // kernels.h -- launch interface between the host driver (fluidsim.cpp) and the gfx950
-// kernels (kernels.hip, voxelize.hip).  Internal to libfluidsim.so.
+// kernels (kernels.hip, sweep_fused.hip, project.hip, advect.hip, fields.hip, voxelize.hip).  Internal to libfluidsim.so.
 #pragma once
 #include "chunk_plan.h"
 #include "launch_plan.h"
@@ -169,7 +169,7 @@ void launch_gradient_advect_velocity(hipStream_t st, const GridDesc& g, const Sl
 template <class T>
 void launch_build_flags(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const T* obs, uint8_t* flags);
 
-// one kill byte per four cells for the sweep kernels (see kernels.hip); `kill` is shifted so
+// one kill byte per four cells for the sweep kernels (see kernels.hip, sweep_fused.hip); `kill` is shifted so
 // that byte (cell + 3) / 4 belongs to the lane group starting at `cell`
 void launch_build_kill(hipStream_t st, const GridDesc& g, const SlabCtx& sc, const uint8_t* flags, uint8_t* kill);
 

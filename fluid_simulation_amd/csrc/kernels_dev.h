@@ -1,5 +1,14 @@
-// kernels_dev.h -- device-side helpers shared by the kernel translation units (kernels.hip,
-// sweep_fused.hip, multigrid.hip).  Internal to libfluidsim.so.
+// kernels_dev.h -- device-side helpers shared by the kernel translation units.  Internal to libfluidsim.so.
+//
+// Which file holds which kernels of the step:
+//   kernels.hip      the solver passes outside sweep_fused.hip: single-sweep and pair Jacobi, Gauss-Seidel
+//   sweep_fused.hip  the fused two- and three-sweep Jacobi kernel (compiled in slices, see the Makefile)
+//   project.hip      divergence and gradient, z-marching and per-cell
+//   advect.hip       the advection forms, the clamp tables, gradient + velocity advection
+//   fields.hip       stand-alone setBounds, flag / kill / clean tables, inlet, pack / unpack, copy, stats, point
+// Here: what more than one of them (and heat.hip, confine.hip, multigrid.hip, vortex.hip) needs -- the cell index, the ghost
+// writes of the per-cell kernels, the row store with setBounds fused in (store_row_bounds), the one-sided pressure gradient,
+// the peer-push store, the XCD remap, the z-march tile and the launch grids.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -30,6 +39,57 @@ __device__ __forceinline__ void write_face_ghosts(const GridDesc& g, const SlabC
     if (z == g.D && sc.hi_wall) q[c + g.sz] = (b == 3) ? -u : u;
 }
 
+// Store the lane's four cells of an interior row of a field with boundary code b, the way
+// setBounds leaves them (simulation.cpp:183-246): `u` un-zeroed values, `killmask` bit e set =>
+// cell e is zeroed; ghost faces determined by this row are written from the un-zeroed values.
+// The projection, advection and heat passes call it.  The Jacobi kernels keep their own stores, which carry the peer push and
+// the nontemporal variants; confine_kernel and mg_prolong0_kernel restate it, because the call made them longer.
+template <class T>
+__device__ __forceinline__ void store_row_bounds(const GridDesc& g, const SlabCtx& sc, T* dst, long base, int x0, int y, int z,
+                                                 const T (&u)[4], unsigned killmask, int b)
+{
+    const T zero = (T)0;
+    V4<T> st;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int x = x0 + e;
+        T ghost_src = (e > 0) ? u[e - 1] : zero;
+        st.e[e] = (x <= g.W) ? (((killmask >> e) & 1u) ? zero : u[e]) : ((x == g.W + 1) ? ghost_src : zero);
+    }
+    *reinterpret_cast<V4<T>*>(dst + base) = st;
+    if (x0 == 1) dst[base - 1] = (b == 1) ? -u[0] : u[0];
+    if (x0 + 3 == g.W) dst[base + 4] = u[3];
+    const bool zlo = (z == 1) && sc.lo_wall, zhi = (z == g.D) && sc.hi_wall;
+    if (y == 1 || y == g.H || zlo || zhi) {
+        V4<T> gy, gz;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = (x0 + e <= g.W);
+            gy.e[e] = in ? ((b == 2) ? -u[e] : u[e]) : zero;
+            gz.e[e] = in ? ((b == 3) ? -u[e] : u[e]) : zero;
+        }
+        if (y == 1) *reinterpret_cast<V4<T>*>(dst + base - g.sy) = gy;
+        if (y == g.H) *reinterpret_cast<V4<T>*>(dst + base + g.sy) = gy;
+        if (zlo) *reinterpret_cast<V4<T>*>(dst + base - g.sz) = gz;
+        if (zhi) *reinterpret_cast<V4<T>*>(dst + base + g.sz) = gz;
+    }
+}
+
+// d p / d x at a fluid cell from the neighbours that are fluid (fp, fm): centred, one-sided or none (simulation.cpp:326-334)
+template <class T>
+__device__ __forceinline__ T one_sided_grad(bool fp, bool fm, T pp, T pc, T pm, T h, T two_h)
+{
+    if (fp && fm) return (pp - pm) / two_h;              // :329-330
+    if (fp) return (pp - pc) / h;                        // :331-332
+    if (fm) return (pc - pm) / h;                        // :333-334
+    return (T)0;
+}
+
+// launch grids: a thread per cell in blocks of 64 x 4 (a wave is one row), and a lane per four cells of a row
+inline dim3 cell_grid(const GridDesc& g) { return dim3((g.W + 63) / 64, (g.H + 3) / 4, g.D); }
+inline dim3 cell_block() { return dim3(64, 4, 1); }
+inline dim3 row_grid(const GridDesc& g) { return dim3((g.W + 255) / 256, (g.H + 3) / 4, g.D); }
+
 // A store of a solver pass, and (PUSH) its copies into the neighbours' halo planes: dl / dh = PeerPush::lo / hi where the
 // plane being written is one the lower / upper neighbour needs, else 0 (wave-uniform).
 template <bool PUSH, class V>
@@ -51,7 +111,7 @@ __device__ __forceinline__ int xcd_contiguous(int b, int nblk)
     return k * q + (k < r ? k : r) + (b >> 3);
 }
 
-// The tile of a z-marching kernel (the two projection passes in kernels.hip, the vortex fields in vortex.hip): a wave owns
+// The tile of a z-marching kernel (the two projection passes in project.hip, the vortex fields in vortex.hip): a wave owns
 // 256 x-consecutive cells x RY rows, a lane four x-consecutive cells of each (one 16-byte access per row), and walks planes
 // zbeg..zend; workgroup = four waves = 4 * RY rows.
 template <class T>

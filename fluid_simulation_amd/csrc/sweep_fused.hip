@@ -565,8 +565,8 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
 // ---------------------------------------------------------------------------------------------
 // The mask-free build's per-workgroup table of one launch shape on the device: made and uploaded at its first launch after a mask
 // change (host work and one upload, no wait on the device), then reused.  z chunks balanced per band by `cost`, or equal ones of
-// zc_len planes when it is off.
-static const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& cost, const GridDesc& g, int BY, int nbands,
+// zc_len planes when it is off.  (inline: a slice without a three-sweep build does not call it)
+inline const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& cost, const GridDesc& g, int BY, int nbands,
                                  int nzc, int zc_len)
 {
     const bool bal = cost.general > 0;
@@ -590,21 +590,10 @@ static const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& 
     return k.dev;
 }
 
-void MaskPlan::clear_chunks()
-{
-    for (Chunks& c : chunks) hipFree(c.dev);
-    chunks.clear();
-}
-void MaskPlan::release()
-{
-    clear_chunks();
-    if (tab) hipFree(tab);
-    tab = nullptr;
-    host.clear();
-}
-
+// One build of the kernel: all the forms of it that a launch can pick.  Explicitly instantiated per build in the slice that
+// the list below assigns it to; the dispatcher reaches the other slices' through `extern template`.
 template <class T, int NL, int NXW, int NYW, int RY>
-static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
+void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
                            const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last,
                            const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src)
 {
@@ -678,6 +667,67 @@ static void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc
 #undef FS_LAUNCH_Z0
 }
 
+// ---------------------------------------------------------------------------------------------
+// The builds of jacobi_fused_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them), written once
+// and grouped by the slice that compiles them.  The device compiler works through one translation unit on one thread, a
+// three-sweep fp32 build (eight forms of the kernel) costs it 22 s and a two-sweep or fp64 build (three forms) 4 to 6 s, so the
+// Makefile compiles this file once per slice (-DFS_FUSED_SLICE=<k> -> sweep_fused_<k>.o) and the slices build side by side.
+// X(T, NL, NXW, NYW, RY); SEP() stands between two entries.  A slice holds one element type.  DESIGN.md section 6 has the
+// measured compile time of each build and slice, from which this assignment comes.  A new slice also goes into FUSED_SLICES
+// of the Makefile.
+// ---------------------------------------------------------------------------------------------
+#ifndef FS_FUSED_SLICE
+#error "sweep_fused.hip is compiled in slices: -DFS_FUSED_SLICE=<k>, one object per slice (see the Makefile)"
+#endif
+#define FS_FUSED_SLICE_0(X, SEP) X(float, 3, 1, 10, 2)
+#define FS_FUSED_SLICE_1(X, SEP) X(float, 3, 1, 8, 2) SEP() X(float, 2, 3, 4, 2)
+#define FS_FUSED_SLICE_2(X, SEP) X(float, 3, 1, 6, 2) SEP() X(float, 2, 4, 4, 2)
+#define FS_FUSED_SLICE_3(X, SEP) X(float, 3, 2, 6, 2) SEP() X(float, 2, 4, 3, 3)
+#define FS_FUSED_SLICE_4(X, SEP) X(float, 3, 2, 5, 2)
+#define FS_FUSED_SLICE_5(X, SEP) X(double, 2, 1, 10, 2) SEP() X(double, 2, 2, 5, 2) SEP() X(double, 2, 2, 4, 2)
+#define FS_FUSED_BUILDS_F32(X, SEP) \
+    FS_FUSED_SLICE_0(X, SEP) SEP() FS_FUSED_SLICE_1(X, SEP) SEP() FS_FUSED_SLICE_2(X, SEP) SEP() FS_FUSED_SLICE_3(X, SEP) SEP() FS_FUSED_SLICE_4(X, SEP)
+#define FS_FUSED_BUILDS_F64(X, SEP) FS_FUSED_SLICE_5(X, SEP)
+#define FS_COMMA() ,
+#define FS_NOTHING()
+#define FS_PASTE_(a, b) a##b
+#define FS_PASTE(a, b) FS_PASTE_(a, b)
+
+#define FS_AS_BUILD(T, NL, NXW, NYW, RY) Build<NL, NXW, NYW, RY>
+using FusedBuildsF32 = Builds<FS_FUSED_BUILDS_F32(FS_AS_BUILD, FS_COMMA)>;
+using FusedBuildsF64 = Builds<FS_FUSED_BUILDS_F64(FS_AS_BUILD, FS_COMMA)>;
+static_assert(FusedBuildsF32::covers(4, SweepKernel::Three) && FusedBuildsF32::covers(4, SweepKernel::Fused2) &&
+                  FusedBuildsF64::covers(8, SweepKernel::Fused2) && FusedBuildsF64::covers(8, SweepKernel::Three),
+              "a fused-kernel shape of SHAPE_TABLE has no build here");
+
+// every build is declared as instantiated elsewhere; then this slice's own are instantiated (a build that is in the lists but
+// in no compiled slice fails to link)
+#define FS_INSTANTIATE(T, NL, NXW, NYW, RY)                                                                                    \
+    template void launch_fused_v<T, NL, NXW, NYW, RY>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const T*, \
+                                                      const T*, T*, const uint8_t*, int, T, T, int, int, const SweepShape&, int, \
+                                                      int, const PeerPush*, MaskPlan*, bool);
+#define FS_DECLARE(T, NL, NXW, NYW, RY) extern FS_INSTANTIATE(T, NL, NXW, NYW, RY)
+FS_FUSED_BUILDS_F32(FS_DECLARE, FS_NOTHING)
+FS_FUSED_BUILDS_F64(FS_DECLARE, FS_NOTHING)
+FS_PASTE(FS_FUSED_SLICE_, FS_FUSED_SLICE)(FS_INSTANTIATE, FS_NOTHING)
+
+// ---------------------------------------------------------------------------------------------
+// What exists once, in slice 0: the MaskPlan members, the zero-start query and the dispatchers
+// ---------------------------------------------------------------------------------------------
+#if FS_FUSED_SLICE == 0
+void MaskPlan::clear_chunks()
+{
+    for (Chunks& c : chunks) hipFree(c.dev);
+    chunks.clear();
+}
+void MaskPlan::release()
+{
+    clear_chunks();
+    if (tab) hipFree(tab);
+    tab = nullptr;
+    host.clear();
+}
+
 // Whether a whole-range launch of the three-sweep kernel with this plan reaches a build that has the zero-start form: the
 // conditions launch_fused_v tests on its way to FS_LAUNCH_Z0 (fp32, lane-aligned rows of 256 or 512 cells, whole domain, the
 // two-body builds), asked by the host before it decides not to zero the iterate in memory.
@@ -687,14 +737,6 @@ bool jacobi_fused_zero_start(const SweepTune& tune, const GridDesc& g, const Sla
     const SweepShape* shape = launch_shape(4, SweepKernel::Three, g.W, decode_plan(true, plan).shape);
     return shape && shape->NL == 3 && g.W == shape->NXW * 256;
 }
-
-// The builds of jacobi_fused_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them).
-using FusedBuildsF32 = Builds<Build<3, 1, 10, 2>, Build<3, 1, 8, 2>, Build<3, 1, 6, 2>, Build<3, 2, 6, 2>, Build<3, 2, 5, 2>,
-                              Build<2, 3, 4, 2>, Build<2, 4, 4, 2>, Build<2, 4, 3, 3>>;
-using FusedBuildsF64 = Builds<Build<2, 1, 10, 2>, Build<2, 2, 5, 2>, Build<2, 2, 4, 2>>;
-static_assert(FusedBuildsF32::covers(4, SweepKernel::Three) && FusedBuildsF32::covers(4, SweepKernel::Fused2) &&
-                  FusedBuildsF64::covers(8, SweepKernel::Fused2) && FusedBuildsF64::covers(8, SweepKernel::Three),
-              "a fused-kernel shape of SHAPE_TABLE has no build here");
 
 // plan = the three-sweep id (levels == 3) or the two-sweep id of the fused kernel (levels == 2); < 0: plan 0.  All plans give
 // the same bits, the host driver times them once per grid.
@@ -731,5 +773,6 @@ template void launch_jacobi_fused<float>(hipStream_t, const SweepTune&, const Gr
 template void launch_jacobi_fused<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const double*,
                                           const double*, double*, const uint8_t*, int, double, double, int, int, int, int,
                                           const PeerPush*, MaskPlan*, bool);
+#endif  // FS_FUSED_SLICE == 0
 
 }  // namespace fs

@@ -1,6 +1,6 @@
 """Rough inputs for the semi-Lagrangian advection and a numpy classifier of its back-traces (numpy only).
 
-The advection kernels of csrc/kernels.hip come in several forms (option advect_kernels) that are claimed bit-identical;
+The advection kernels of csrc/advect.hip come in several forms (option advect_kernels) that are claimed bit-identical;
 which branch of a form a trace takes depends on where it ends: clamped to the inlet side (px == 0.5: the clamp tables, and
 in the tile form the LDS window or the fallback to the global table), clamped to the outlet side (px == W + 0.5: side 1 of
 the tables), not clamped in x (the gather from the big array), clamped in y or z (table rows 0 / H + 1, planes 0 / D + 1).
@@ -67,7 +67,7 @@ def rough_mask(W, H, D, seed=SEED):
 
 
 def tile_window(want, nf, itemsize):
-    """tile_window<T>(want, nf) of kernels.hip: the largest r <= want (at least 1) whose nf windows of (9 + 2r)^2 values
+    """tile_window<T>(want, nf) of advect.hip: the largest r <= want (at least 1) whose nf windows of (9 + 2r)^2 values
     fit LDS_BYTES."""
     r = max(1, int(want))
     while r > 1 and nf * (TILE + 2 * r + 1) ** 2 * itemsize > LDS_BYTES:

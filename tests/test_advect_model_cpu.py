@@ -1,5 +1,5 @@
 """The rough advection inputs of tests/advect_model.py on the CPU: every class of back-trace that a kernel form of
-csrc/kernels.hip treats differently holds at least FLOOR cells at every (grid, window radius) pair the GPU test
+csrc/advect.hip treats differently holds at least FLOOR cells at every (grid, window radius) pair the GPU test
 (tests/test_gpu_advect_rough.py) leans on, the oracle stays finite and non-trivial under them, and the restated
 tile_window() gives the radii the LDS cap leaves.  The counts recorded here are the ones the GPU module's coverage table
 quotes; they come from the numpy model alone."""

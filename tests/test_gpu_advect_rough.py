@@ -1,6 +1,6 @@
 """Every form of the semi-Lagrangian advection kernels under rough flows, bit for bit against the CPU oracle.
 
-csrc/kernels.hip holds the advection in four forms (option advect_kernels) plus the kernel that fuses the first
+csrc/advect.hip holds the advection in four forms (option advect_kernels) plus the kernel that fuses the first
 projection's gradient into the velocity advection; DESIGN.md section 4 calls them bit-identical.  Which branch of a form a
 back-trace takes depends on where it ends, and the tunnel's own start reaches few of them (tests/test_gpu_edge.py,
 test_advection_row_kernels_match_cell_kernels_and_oracle).  The flow here is the seeded recipe of tests/advect_model.py;
