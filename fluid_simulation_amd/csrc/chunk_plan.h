@@ -85,6 +85,16 @@ inline std::vector<int> balanced_chunks(const std::vector<uint32_t>& tab, int wo
     return out;
 }
 
+// The clean table of the z-mirrored problem: plane z of the result is plane D + 1 - z of `tab`.  A reversed march (sweep_fused.hip,
+// ZREV) numbers its planes that way, so its chunks and its mask-free plan are the upward ones of this table.
+inline std::vector<uint32_t> mirrored_clean(const std::vector<uint32_t>& tab, int words, int D)
+{
+    std::vector<uint32_t> out(tab.size());
+    for (int z = 0; z <= D + 1; ++z)
+        std::copy(tab.begin() + (size_t)(D + 1 - z) * words, tab.begin() + (size_t)(D + 2 - z) * words, out.begin() + (size_t)z * words);
+    return out;
+}
+
 // What a workgroup of the mask-free build reads at its start: {zbeg, zend, ga, gb} per workgroup, from its (zbeg, zend).  Its
 // wall-free groups [g0, g1) (as jacobi_fused_kernel numbers them) run mask-free [g0, ga), wall-free [ga, gb), mask-free
 // [gb, g1): ga / gb - 1 are the first / last group that is not clean.  Group k (iterations Z = lo1 + 3k .. Z + 2) is clean when

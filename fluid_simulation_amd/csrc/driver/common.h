@@ -107,6 +107,7 @@ struct fs_sim {
     bool fuse_advect = true;     // one kernel for the three velocity advections of a step (single GPU)
     // "zero_start" / "fuse_project_advect": -1 = auto, 0, 1.  What auto means is decided by measurement.
     int zero_start = -1;         // project(): the divergence pass does not zero p in memory, the first pass of the solve takes zeros
+    int z_alternate = -1;        // fs_set_int, -1 = auto, 0, 1.  Solves: a three-sweep pass behind an upward one marches downward in z (sweep_fused.hip, ZREV)
     int fuse_project_advect = -1;   // step(): the first projection's gradient pass runs inside the velocity advection's kernel
     double confinement = 0.0;    // "vorticity_confinement": strength of the confinement pass at the start of a step, 0 = off
     long n_confine = 0;          // confinement passes done, inside steps and by fs_confine_vorticity (fs_get_int)
@@ -126,6 +127,7 @@ struct fs_sim {
     long n_inflow = 0;           // planes written by steps ("inflow_passes")
     double inflow_convect_now() const { return inflow_convect < 0.0 ? ((double)dt * (double)W) * (double)speed : inflow_convect; }
     long n_zero_start = 0, n_project_advect = 0;   // projections / steps that took those paths (fs_get_int)
+    long n_reversed = 0;         // three-sweep passes that marched downward ("reversed_passes")
     int overlap = -1;            // z-slabs, how a pass and its halo exchange are scheduled: 0 the pass, then the exchange; 1 boundary
                                  // planes first, their exchange on the communication stream while the interior is computed; 2 boundary
                                  // launch + exchange on the communication stream beside the interior launch; -1 (default) = "auto":

@@ -61,6 +61,13 @@ namespace {
 #define FS_PROJECT_ADVECT_AUTO 1
 #endif
 constexpr bool ZERO_START_AUTO = FS_ZERO_START_AUTO != 0, PROJECT_ADVECT_AUTO = FS_PROJECT_ADVECT_AUTO != 0;
+// ... and for fs_set_int "z_alternate" (-DFS_Z_ALTERNATE_AUTO=0|1), on grids whose iterate, target and right-hand side together outgrow the
+// Infinity Cache; smaller grids stay in it whichever way a pass runs, and auto leaves them alone.
+#ifndef FS_Z_ALTERNATE_AUTO
+#define FS_Z_ALTERNATE_AUTO 1
+#endif
+constexpr bool Z_ALTERNATE_AUTO = FS_Z_ALTERNATE_AUTO != 0;
+constexpr size_t INFINITY_CACHE_BYTES = (size_t)256 << 20;
 const char* const kFamilyNames[FAM_HEAT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
 // the families added since (tests/test_inflow_cpu.py pins the text of the table above): FAM_HEAT onwards
 const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT] = { "heat" };
@@ -380,13 +387,13 @@ struct Engine : EngineBase {
     // second >= 0, to the equally long range starting there).
     // push: the pass also stores the planes its z neighbours need into their halo planes (plain Jacobi passes, FSIPC)
     void launch_pass(hipStream_t st, int levels, bool rb, const T* src_, const T* rhs_, T* dst_, int b, T a, T inv_c, int zf,
-                     int zl, int second = -1, const fs::PeerPush* push = nullptr, bool zero_src = false)
+                     int zl, int second = -1, const fs::PeerPush* push = nullptr, bool zero_src = false, bool zrev = false)
     {
         const T omega = rb ? rb_omega : (T)0;
         const bool fused2 = fs::decode_plan(false, plan_two).kind == fs::SweepKernel::Fused2;
         if (levels == 3)
             fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 3, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_three, second, push,
-                                       &maskplan, zero_src);
+                                       &maskplan, zero_src, zrev);
         else if (levels == 2 && !rb && fused2)
             fs::launch_jacobi_fused<T>(st, S->tune, g, sc, 2, src_, rhs_, dst_, kill, b, a, inv_c, zf, zl, plan_two, second, push);
         else if (levels == 2)
@@ -517,6 +524,7 @@ struct Engine : EngineBase {
         int b = 0, rhs = -1, src = -1;
         bool src_temp = false, rb = false, damped = false;
         bool zero_src = false;       // the initial iterate is all zeros and its array is not read (zero_start_ok)
+        bool prev_up = false;        // the previous pass of this solve marched upward in z (none yet: false)
         T a = (T)0, inv_c = (T)1, omega = (T)1;
     };
 
@@ -647,8 +655,13 @@ struct Engine : EngineBase {
             if (span < 0) { span = S->span_begin(fam); span_fam = fam; }
             ++span_launches;
             if (!S->comm.active()) {
-                launch_pass(S->stream, lv, r.rb, arr[r.src], arr[r.rhs], arr[dst], r.b, r.a, r.inv_c, 1, g.D, -1, nullptr,
-                            r.zero_src && i == 0);
+                // a three-sweep pass behind an upward pass of the same solve marches downward where such a build exists: it
+                // starts on the planes the pass before it read and wrote last
+                const bool zero = r.zero_src && i == 0;
+                const bool zrev = lv == 3 && r.prev_up && !zero && !r.rb && z_alternate_ok();
+                launch_pass(S->stream, lv, r.rb, arr[r.src], arr[r.rhs], arr[dst], r.b, r.a, r.inv_c, 1, g.D, -1, nullptr, zero, zrev);
+                r.prev_up = !zrev;
+                if (zrev) ++S->n_reversed;
             } else {
                 // planes a neighbour needs of this pass's result: as many as its next pass has levels; after
                 // the last pass the halos are brought to their full depth (what every other kernel assumes)
@@ -919,6 +932,15 @@ struct Engine : EngineBase {
     }
 
     // ---- project (simulation.cpp:289-362) ----------------------------------------------
+    // fs_set_int "z_alternate": may a three-sweep pass of a solve march downward?  Where the launch has the reversed build; "auto" asks
+    // also that the three arrays of a pass outgrow the Infinity Cache.
+    bool z_alternate_ok() const
+    {
+        if (S->z_alternate == 0 || S->comm.active() || plan_three < 0) return false;
+        if (S->z_alternate < 0 && !(Z_ALTERNATE_AUTO && 3 * (size_t)g.n * sizeof(T) > INFINITY_CACHE_BYTES)) return false;
+        return fs::jacobi_fused_reversed(S->tune, g, sc, (int)sizeof(T), plan_three);
+    }
+
     // "zero_start": may this projection leave p unzeroed in memory and start its solve from zeros that are not read?  Only
     // where the solve is `acc` >= 3 Jacobi sweeps whose first pass is the three-sweep kernel in a build that has the zero-start
     // form, the launch plans are already chosen (timing them reads the iterate), there are no slabs (the halo exchange of p
@@ -1929,6 +1951,8 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "pair_shape") *out = s->eng ? ENG(s, tuned_two()) : -1;
     else if (n == "triple_plan") *out = s->eng ? ENG(s, tuned_three()) : -1;
     else if (n == "zero_start_projections") *out = s->n_zero_start;        // projections whose solve started from unread zeros
+    else if (n == "z_alternate") *out = s->z_alternate;
+    else if (n == "reversed_passes") *out = (int)s->n_reversed;            // three-sweep passes that marched downward in z
     else if (n == "project_advect_steps") *out = s->n_project_advect;      // steps whose first gradient ran inside the advection
     else if (n == "two_sweep_fused")   // 1: jacobi_fused_kernel<NL=2>, 0: jacobi_pair_kernel
         *out = (s->eng && fs::decode_plan(false, ENG(s, tuned_two())).kind == fs::SweepKernel::Fused2) ? 1 : 0;
@@ -1982,6 +2006,7 @@ int fs_set_int(fs_sim* s, const char* name, int value)
     if (n == "speed") s->speed = value;
     else if (n == "acc") { if (value < 0) return fail(FS_EINVAL, "acc < 0"); s->acc = value; }
     else if (n == "iter") { if (value < 0) return fail(FS_EINVAL, "iter < 0"); s->iter = value; }
+    else if (n == "z_alternate") { if (value < -1 || value > 1) return fail(FS_EINVAL, "z_alternate: -1 (auto) | 0 | 1"); s->z_alternate = value; }
     else return fail(FS_EINVAL, "member '%s' is fixed after construction", name);
     return FS_OK;
 }

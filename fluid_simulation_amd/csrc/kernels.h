@@ -76,8 +76,10 @@ struct MaskPlan {
     uint32_t* tab = nullptr;             // device staging of `host`, (D + 2) planes x `words`
     int words = 0;                       // per plane: (H + 2 + 31) / 32 rows' words + one pad word
     std::vector<uint32_t> host;          // copy of `tab`
+    std::vector<uint32_t> host_rev;      // chunk_plan.h: mirrored_clean(host), made when a reversed pass first asks for a plan
     struct Chunks {
         int BY, nbands, nzc, zc_len;     // zc_len: equal chunks of that length, 0 = balanced by `cost`
+        bool zrev;                       // the plan of a reversed pass: logical planes, from host_rev
         ChunkCost cost;
         std::vector<int> plan;           // chunk_plan.h: mask_free_plan
         int* dev;
@@ -120,12 +122,17 @@ void launch_jacobi_pair(hipStream_t st, const SweepTune& tune, const GridDesc& g
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
-                         int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr, bool zero_src = false);
+                         int second_first = -1, const PeerPush* push = nullptr, MaskPlan* mp = nullptr, bool zero_src = false,
+                         bool zrev = false);
 // mp: the single-GPU clean table (fp32 three sweeps only; nullptr = no mask-free body)
 // zero_src: level 0 is all zeros and `src` is not read (the first pass of a pressure solve, whose iterate the divergence pass
 // would otherwise have to zero in memory first).  Only where jacobi_fused_zero_start says the launch has such a build: the
 // same launch plan, workgroups and arithmetic as the reading build, bit-identical with it on a zeroed `src`.
 bool jacobi_fused_zero_start(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int elem_size, int plan);
+// zrev: the pass marches from plane D down to plane 1 (same bits; a pass after an upward one then starts on the planes the
+// Infinity Cache still holds).  Only where jacobi_fused_reversed says the launch has such a build (fp32 rows of 512 cells,
+// whole domain, the two-body builds), and never together with zero_src.
+bool jacobi_fused_reversed(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int elem_size, int plan);
 
 template <class T>
 void launch_gs_lex(hipStream_t st, const GridDesc& g, T* q, const T* rhs, const uint8_t* flags, int b, T a, T inv_c,

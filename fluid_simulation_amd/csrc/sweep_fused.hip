@@ -57,6 +57,8 @@ struct IC {
 // Experiment switch (build with -DFS_EXP_NT=1|2|3): nontemporal loads of the right-hand side (1) and / or nontemporal
 // stores of the result (2).  Measured at 512^3 on one box (profiles/r02k_nontemporal_ab_c3.json): 0 -> 0.1465, 1 -> 0.150,
 // 2 -> 0.146, 3 -> 0.148 ms per sweep; the shipped library is built with 0.
+// Nontemporal loads of level 0 (dead after the pass; tried with the reversed march so that the Infinity Cache might keep more of the two
+// arrays that are read again) are not a switch here: 84.1 against 59.7-60.3 ms per step at 512^3 (profiles/r18a_z_alternate.json).
 #ifndef FS_EXP_NT
 #define FS_EXP_NT 0
 #endif
@@ -87,7 +89,15 @@ struct CleanArgs {
 // Z0 (zero start): level 0 is all zeros and is not read -- no load_core, no hb / ht / eL / eR loads, L0 held as constants.  The
 // level-1 expression stays (rh + a * nb) * inv_c on nb = 0 + 0 + ..., the operations a zeroed `src` would feed it (no
 // fast-math, -ffp-contract=off), so the result is bit-identical with reading zeros; `src` is never dereferenced.
-template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL, bool Z0 = false>
+//
+// ZREV (reversed march): the workgroup marches from plane D down to plane 1, so that a pass which follows an upward one starts
+// on the planes that pass touched last (what the Infinity Cache still holds).  Everything below works on LOGICAL planes
+// z' = D + 1 - z and is the upward march of the z-mirrored problem; only three things know the real plane: the plane addresses
+// (plane_of, the kill bytes, the stores -- one mapping, `zorg_b` + z' * `zdir_b`), the sum of the two z neighbours in relax4 (the
+// reference adds z+1 before z-1 in REAL coordinates, and fp32 sums do not commute in the last bit), and the host's mask-free
+// table, which is made from the mirrored clean table (chunk_plan.h).  Both z walls are physical and treated alike (face4 on
+// b == 3 at either), so nothing else changes.
+template <class T, int NL, int NXW, int NYW, int RY, bool ALIGNED, bool SLAB, int WALLSEL, bool Z0 = false, bool ZREV = false>
 __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g, SlabCtx sc, const T* __restrict__ src,
                                                                       const T* __restrict__ rhs, T* __restrict__ dst,
                                                                       const uint8_t* __restrict__ flags, int b, T a, T inv_c,
@@ -97,6 +107,8 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     static_assert(NL == 2 || NL == 3, "two or three sweeps per pass");
     static_assert(!Z0 || (NL == 3 && ALIGNED && !SLAB && sizeof(T) == 4 && (WALLSEL == 1 || WALLSEL == 3)),
                   "the zero-start form exists for the whole-domain lane-aligned fp32 three-sweep builds");
+    static_assert(!ZREV || (NL == 3 && ALIGNED && !SLAB && sizeof(T) == 4 && (WALLSEL == 1 || WALLSEL == 3) && !Z0),
+                  "the reversed march exists for the whole-domain lane-aligned fp32 three-sweep builds that read level 0");
     constexpr int BY = NYW * RY, TW = NXW * 256 + 8, RW = NXW * 256;
     constexpr int OV = NL - 1;                           // rows / planes a band / chunk loses per side
     constexpr int ES = (int)sizeof(T);
@@ -192,7 +204,9 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     const long plane_b = (long)g.sz * ES, plane_f = (long)(g.sz >> 2), row_b = (long)g.sy * ES;
     // rows below / above the patch: the first / last own row's offset with a wave-uniform step (0 where clamped)
     const long step_b = (long)(clampy(y0) - clampy(y0 - 1)) * row_b, step_t = (long)(clampy(y0 + RY) - clampy(y0 + RY - 1)) * row_b;
-    auto plane_of = [&](const T* base, int z) { return reinterpret_cast<const char*>(base) + (long)z * plane_b; };   // wave-uniform
+    // logical plane z -> bytes from an array's plane 0 (ZREV: real plane D + 1 - z)
+    const long zorg_b = ZREV ? (long)(D + 1) * plane_b : 0, zdir_b = ZREV ? -plane_b : plane_b;
+    auto plane_of = [&](const T* base, int z) { return reinterpret_cast<const char*>(base) + zorg_b + (long)z * zdir_b; };   // wave-uniform
     auto ld4 = [&](const char* ptr, T (&out)[4]) {
         V4<T> q = *reinterpret_cast<const V4<T>*>(ptr);
 #pragma unroll
@@ -208,7 +222,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
     auto load_side = [&](int z) {                        // what level 1 of plane z needs beside the wave's own cells
         const char* sp = plane_of(src, z);
         const char* rp = plane_of(rhs, z);
-        const uint8_t* fp = flags + (long)z * plane_f;
+        const uint8_t* fp = flags + (long)(ZREV ? D + 1 - z : z) * plane_f;
         if constexpr (!Z0) {
             ld4(sp - step_b + oc[0], hb);
             ld4(sp + step_t + oc[RY - 1], ht);
@@ -243,7 +257,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         for (int e = 0; e < 4; ++e) {
             T xp1 = (e < 3) ? cc[e + 1] : right;
             T xm1 = (e > 0) ? cc[e - 1] : left;
-            T nb = xp1 + xm1 + yp[e] + ym[e] + zp[e] + zm[e];
+            T nb = xp1 + xm1 + yp[e] + ym[e] + (ZREV ? zm[e] : zp[e]) + (ZREV ? zp[e] : zm[e]);   // (real z+1 first)
             u[e] = (rh[e] + a * nb) * inv_c;
         }
     };
@@ -336,7 +350,7 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
         const int y = y0 + r;
         T st[4];
         settle4(u, fl, st);
-        char* base = reinterpret_cast<char*>(dst) + (long)zo * plane_b + oc[r];
+        char* base = reinterpret_cast<char*>(dst) + zorg_b + (long)zo * zdir_b + oc[r];
         // z-slab push exchange: the planes the neighbours need next also go straight into their halo planes (wave-uniform)
         const long dl = (SLAB && zo <= pp.planes) ? pp.lo : 0, dh = (SLAB && zo > D - pp.planes) ? pp.hi : 0;
         if (FS_EXP_NT & 2) {
@@ -368,8 +382,8 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
             face4(u, b == 3, f);
 #pragma unroll
             for (int e = 0; e < 4; ++e) qq.e[e] = f[e];
-            if (zlo_face) *reinterpret_cast<V4<T>*>(base - plane_b) = qq;                           // :208-214
-            if (zhi_face) *reinterpret_cast<V4<T>*>(base + plane_b) = qq;
+            if (zlo_face) *reinterpret_cast<V4<T>*>(base - zdir_b) = qq;                            // :208-214
+            if (zhi_face) *reinterpret_cast<V4<T>*>(base + zdir_b) = qq;
         }
     };
 
@@ -566,23 +580,26 @@ __global__ __launch_bounds__(NXW* NYW * 64) void jacobi_fused_kernel(GridDesc g,
 // The mask-free build's per-workgroup table of one launch shape on the device: made and uploaded at its first launch after a mask
 // change (host work and one upload, no wait on the device), then reused.  z chunks balanced per band by `cost`, or equal ones of
 // zc_len planes when it is off.  (inline: a slice without a three-sweep build does not call it)
+// zrev: the table of a reversed pass -- the same, in its logical planes, from the z-mirrored clean table.
 inline const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& cost, const GridDesc& g, int BY, int nbands,
-                                 int nzc, int zc_len)
+                                 int nzc, int zc_len, bool zrev)
 {
     const bool bal = cost.general > 0;
     for (const MaskPlan::Chunks& c : mp.chunks)
-        if (c.BY == BY && c.nbands == nbands && c.nzc == nzc && c.zc_len == (bal ? 0 : zc_len) && c.cost.general == cost.general &&
-            c.cost.wall_free == cost.wall_free && c.cost.mask_free == cost.mask_free)
+        if (c.BY == BY && c.nbands == nbands && c.nzc == nzc && c.zc_len == (bal ? 0 : zc_len) && c.zrev == zrev &&
+            c.cost.general == cost.general && c.cost.wall_free == cost.wall_free && c.cost.mask_free == cost.mask_free)
             return c.dev;
+    if (zrev && mp.host_rev.empty()) mp.host_rev = mirrored_clean(mp.host, mp.words, g.D);
+    const std::vector<uint32_t>& tab = zrev ? mp.host_rev : mp.host;
     std::vector<int> chunks;
-    if (bal) chunks = balanced_chunks(mp.host, mp.words, g.H, g.D, BY, nbands, nzc, cost);
+    if (bal) chunks = balanced_chunks(tab, mp.words, g.H, g.D, BY, nbands, nzc, cost);
     else
         for (int zc = 0; zc < nzc; ++zc)
             for (int band = 0; band < nbands; ++band) {
                 chunks.push_back(1 + zc * zc_len);
                 chunks.push_back(std::min(g.D, zc * zc_len + zc_len));
             }
-    MaskPlan::Chunks c{BY, nbands, nzc, bal ? 0 : zc_len, cost, mask_free_plan(mp.host, mp.words, g.H, g.D, BY, nbands, chunks), nullptr};
+    MaskPlan::Chunks c{BY, nbands, nzc, bal ? 0 : zc_len, zrev, cost, mask_free_plan(tab, mp.words, g.H, g.D, BY, nbands, chunks), nullptr};
     if (hipMalloc((void**)&c.dev, c.plan.size() * sizeof(int)) != hipSuccess) return nullptr;
     mp.chunks.push_back(std::move(c));
     MaskPlan::Chunks& k = mp.chunks.back();
@@ -595,7 +612,8 @@ inline const int* mask_free_plan(hipStream_t st, MaskPlan& mp, const ChunkCost& 
 template <class T, int NL, int NXW, int NYW, int RY>
 void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, const T* src,
                            const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last,
-                           const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src)
+                           const SweepShape& shape, int alt, int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src,
+                           bool zrev)
 {
     const PeerPush pp = (push && second_first < 0) ? *push : PeerPush();
     constexpr int BY = NYW * RY, THREADS = NXW * NYW * 64;
@@ -632,6 +650,13 @@ void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, co
 #define FS_LAUNCH_Z0(WS)                                                                                                  \
     hipLaunchKernelGGL((jacobi_fused_kernel<T, NL, NXW, NYW, RY, true, false, WS, true>), dim3(nblk), dim3(THREADS), 0, st, g, sc, \
                        src, rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp, ca)
+    // ... and with the reversed march: the same launch of the z-mirrored problem (chunks and plan in logical planes)
+#define FS_LAUNCH_ZREV(WS)                                                                                                \
+    hipLaunchKernelGGL((jacobi_fused_kernel<T, NL, NXW, NYW, RY, true, false, WS, false, true>), dim3(nblk), dim3(THREADS), 0, st, g, \
+                       sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, zc_len, z_stride, nbands, nblk, pp, ca)
+    // the reversed builds: rows of two waves (512 cells), where the three arrays of a solve outgrow the Infinity Cache
+    constexpr bool HAS_ZREV = (NL == 3 && NXW == 2 && sizeof(T) == 4);
+    zrev = zrev && HAS_ZREV && !zero_src;
     // The wall-free second body exists for the three-sweep kernel on lane-aligned whole-domain grids (the benchmark grids).
     // Rounds 1-2 selected a body per WORKGROUP: 9 % (512^3) to 14 % (256^3) faster for the interior ones, but a pass ends with its
     // slowest workgroup, and at 512^3 (256 workgroups, one per CU) half of them touch a z wall.  Round 3 selects per GROUP OF
@@ -645,15 +670,21 @@ void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, co
             // mask_free "auto": rows of two waves only -- on 256-cell rows (c2) this build measured slower (4.70 -> 4.81 ms per step)
             const bool mask_free = tune.mask_free >= 2 || (tune.mask_free == 1 && NXW >= 2);
             if (whole && mask_free && mp && !mp->host.empty() &&
-                (ca.plan = mask_free_plan(st, *mp, tune.chunk_cost, g, BY, nbands, nblk / nbands, zc_len))) {
+                (ca.plan = mask_free_plan(st, *mp, tune.chunk_cost, g, BY, nbands, nblk / nbands, zc_len, zrev && whole))) {
                 // the mask-free build, on z chunks balanced per band unless the cost model is off
                 if constexpr (sizeof(T) == 4) {
                     if (zero_src) { FS_LAUNCH_Z0(3); return; }
+                }
+                if constexpr (HAS_ZREV) {
+                    if (zrev) { FS_LAUNCH_ZREV(3); return; }
                 }
                 FS_LAUNCH(true, false, 3);
             } else if (whole) {
                 if constexpr (sizeof(T) == 4) {
                     if (zero_src) { FS_LAUNCH_Z0(1); return; }
+                }
+                if constexpr (HAS_ZREV) {
+                    if (zrev) { FS_LAUNCH_ZREV(1); return; }
                 }
                 FS_LAUNCH(true, false, 1);
             } else FS_LAUNCH(true, true, 1);             // z-slabs: an inner rank has no z wall at all
@@ -665,13 +696,15 @@ void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, co
     else FS_LAUNCH(false, true, 0);
 #undef FS_LAUNCH
 #undef FS_LAUNCH_Z0
+#undef FS_LAUNCH_ZREV
 }
 
 // ---------------------------------------------------------------------------------------------
 // The builds of jacobi_fused_kernel (launch_plan.h: SHAPE_TABLE says which row widths and shape ids reach them), written once
 // and grouped by the slice that compiles them.  The device compiler works through one translation unit on one thread, a
-// three-sweep fp32 build (eight forms of the kernel) costs it 22 s and a two-sweep or fp64 build (three forms) 4 to 6 s, so the
-// Makefile compiles this file once per slice (-DFS_FUSED_SLICE=<k> -> sweep_fused_<k>.o) and the slices build side by side.
+// three-sweep fp32 build (eight forms of the kernel, ten with the reversed march) costs it 22 to 35 s and a two-sweep or fp64
+// build (three forms) 4 to 6 s, so the Makefile compiles this file once per slice (-DFS_FUSED_SLICE=<k> -> sweep_fused_<k>.o)
+// and the slices build side by side.
 // X(T, NL, NXW, NYW, RY); SEP() stands between two entries.  A slice holds one element type.  DESIGN.md section 6 has the
 // measured compile time of each build and slice, from which this assignment comes.  A new slice also goes into FUSED_SLICES
 // of the Makefile.
@@ -679,10 +712,10 @@ void launch_fused_v(hipStream_t st, const SweepTune& tune, const GridDesc& g, co
 #ifndef FS_FUSED_SLICE
 #error "sweep_fused.hip is compiled in slices: -DFS_FUSED_SLICE=<k>, one object per slice (see the Makefile)"
 #endif
-#define FS_FUSED_SLICE_0(X, SEP) X(float, 3, 1, 10, 2)
+#define FS_FUSED_SLICE_0(X, SEP) X(float, 3, 1, 10, 2) SEP() X(float, 2, 4, 3, 3)
 #define FS_FUSED_SLICE_1(X, SEP) X(float, 3, 1, 8, 2) SEP() X(float, 2, 3, 4, 2)
 #define FS_FUSED_SLICE_2(X, SEP) X(float, 3, 1, 6, 2) SEP() X(float, 2, 4, 4, 2)
-#define FS_FUSED_SLICE_3(X, SEP) X(float, 3, 2, 6, 2) SEP() X(float, 2, 4, 3, 3)
+#define FS_FUSED_SLICE_3(X, SEP) X(float, 3, 2, 6, 2)
 #define FS_FUSED_SLICE_4(X, SEP) X(float, 3, 2, 5, 2)
 #define FS_FUSED_SLICE_5(X, SEP) X(double, 2, 1, 10, 2) SEP() X(double, 2, 2, 5, 2) SEP() X(double, 2, 2, 4, 2)
 #define FS_FUSED_BUILDS_F32(X, SEP) \
@@ -705,7 +738,7 @@ static_assert(FusedBuildsF32::covers(4, SweepKernel::Three) && FusedBuildsF32::c
 #define FS_INSTANTIATE(T, NL, NXW, NYW, RY)                                                                                    \
     template void launch_fused_v<T, NL, NXW, NYW, RY>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, const T*, \
                                                       const T*, T*, const uint8_t*, int, T, T, int, int, const SweepShape&, int, \
-                                                      int, const PeerPush*, MaskPlan*, bool);
+                                                      int, const PeerPush*, MaskPlan*, bool, bool);
 #define FS_DECLARE(T, NL, NXW, NYW, RY) extern FS_INSTANTIATE(T, NL, NXW, NYW, RY)
 FS_FUSED_BUILDS_F32(FS_DECLARE, FS_NOTHING)
 FS_FUSED_BUILDS_F64(FS_DECLARE, FS_NOTHING)
@@ -719,6 +752,7 @@ void MaskPlan::clear_chunks()
 {
     for (Chunks& c : chunks) hipFree(c.dev);
     chunks.clear();
+    host_rev.clear();
 }
 void MaskPlan::release()
 {
@@ -738,12 +772,20 @@ bool jacobi_fused_zero_start(const SweepTune& tune, const GridDesc& g, const Sla
     return shape && shape->NL == 3 && g.W == shape->NXW * 256;
 }
 
+// The same question for the reversed march (launch_fused_v: HAS_ZREV and the way to FS_LAUNCH_ZREV): rows of 512 cells only.
+bool jacobi_fused_reversed(const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int elem_size, int plan)
+{
+    if (!jacobi_fused_zero_start(tune, g, sc, elem_size, plan)) return false;
+    const SweepShape* shape = launch_shape(4, SweepKernel::Three, g.W, decode_plan(true, plan).shape);
+    return shape->NXW == 2;
+}
+
 // plan = the three-sweep id (levels == 3) or the two-sweep id of the fused kernel (levels == 2); < 0: plan 0.  All plans give
 // the same bits, the host driver times them once per grid.
 template <class T>
 void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& g, const SlabCtx& sc, int levels, const T* src,
                          const T* rhs, T* dst, const uint8_t* flags, int b, T a, T inv_c, int z_first, int z_last, int plan,
-                         int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src)
+                         int second_first, const PeerPush* push, MaskPlan* mp, bool zero_src, bool zrev)
 {
     const PlanId p = decode_plan(levels == 3, plan);
     const SweepKernel kind = levels == 3 ? SweepKernel::Three : SweepKernel::Fused2;
@@ -764,15 +806,15 @@ void launch_jacobi_fused(hipStream_t st, const SweepTune& tune, const GridDesc& 
     List::run(*shape, [&](auto build) {
         using B = decltype(build);
         launch_fused_v<T, B::NL, B::NXW, B::NYW, B::RY>(st, tune, g, sc, src, rhs, dst, flags, b, a, inv_c, z_first, z_last, *shape,
-                                                        p.alt, second_first, push, sizeof(T) == 4 ? mp : nullptr, zero_src);
+                                                        p.alt, second_first, push, sizeof(T) == 4 ? mp : nullptr, zero_src, zrev);
     });
 }
 template void launch_jacobi_fused<float>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const float*,
                                          const float*, float*, const uint8_t*, int, float, float, int, int, int, int,
-                                         const PeerPush*, MaskPlan*, bool);
+                                         const PeerPush*, MaskPlan*, bool, bool);
 template void launch_jacobi_fused<double>(hipStream_t, const SweepTune&, const GridDesc&, const SlabCtx&, int, const double*,
                                           const double*, double*, const uint8_t*, int, double, double, int, int, int, int,
-                                          const PeerPush*, MaskPlan*, bool);
+                                          const PeerPush*, MaskPlan*, bool, bool);
 #endif  // FS_FUSED_SLICE == 0
 
 }  // namespace fs

@@ -191,6 +191,7 @@ class Simulation:
     dt = property(lambda s: s._getf("dt"), lambda s, v: check(s._L.fs_set_float(s._h, b"dt", float(v))))
     diff = property(lambda s: s._getf("diff"), lambda s, v: check(s._L.fs_set_float(s._h, b"diff", float(v))))
     visc = property(lambda s: s._getf("visc"), lambda s, v: check(s._L.fs_set_float(s._h, b"visc", float(v))))
+    z_alternate = property(lambda s: s._geti("z_alternate"), lambda s, v: check(s._L.fs_set_int(s._h, b"z_alternate", int(v))))
     local_depth = property(lambda s: s._geti("local_depth"))
     z_offset = property(lambda s: s._geti("z_offset"))
 

@@ -201,7 +201,12 @@ int fs_set_option(fs_sim* s, const char* key, const char* value);
 /* Public data members of class Simulation (simulation.h:44-54), by name:
  * "width" "height" "depth" "speed" "acc" "iter" (int) and "dt" "diff" "visc" (float). */
 int fs_get_int(fs_sim* s, const char* name, int* out);
-int fs_set_int(fs_sim* s, const char* name, int value);      /* speed, acc, iter only */
+int fs_set_int(fs_sim* s, const char* name, int value);      /* speed, acc, iter, z_alternate only */
+/* "z_alternate" = -1 (auto, the default) | 0 | 1, never changes results: within a solve, a three-sweep pass that follows an upward
+ * pass marches from plane D down to plane 1, so that it starts on the planes the pass before it touched last (what the 256 MiB
+ * Infinity Cache still holds); fp32 rows of 512 cells on one GPU, elsewhere every pass runs upward.  Auto: only where iterate,
+ * target and right-hand side together are larger than that cache; 0 = the launches without it.  fs_get_int "reversed_passes"
+ * counts the passes that ran downward. */
 int fs_get_float(fs_sim* s, const char* name, float* out);
 int fs_set_float(fs_sim* s, const char* name, float value);
 

@@ -34,7 +34,9 @@ if len(sys.argv) > 4:
 import re  # noqa: E402
 
 # json key -> pattern of the kernel name as rocprofv3 prints it (first match wins)
-KEYS = (("jacobi_fused_kernel<NL=3, zero start>", r"jacobi_fused_kernel<\w+, 3,[^>]*, true>"),
+# (the last two template arguments of the three-sweep kernel: zero start, reversed march)
+KEYS = (("jacobi_fused_kernel<NL=3, zero start>", r"jacobi_fused_kernel<\w+, 3,[^>]*, true, false>"),
+        ("jacobi_fused_kernel<NL=3, reversed>", r"jacobi_fused_kernel<\w+, 3,[^>]*, false, true>"),
         ("gradient_advect_velocity_kernel", "gradient_advect_velocity_kernel"),
         ("jacobi_fused_kernel<NL=3>", r"jacobi_fused_kernel<\w+, 3,"), ("jacobi_fused_kernel<NL=2>", r"jacobi_fused_kernel<\w+, 2,"),
         ("jacobi_pair_kernel", "jacobi_pair_kernel"), ("jacobi_sweep_kernel", "jacobi_sweep_kernel"),
