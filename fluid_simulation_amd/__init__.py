@@ -10,11 +10,12 @@ from ._lib import (BUFFER, DENS, DIVERGENCE, FIELD_NAMES, OBS, PRESSURE, VX, VX_
                    SAMPLE_STAT, IMG_SLICE, IMG_SUM, IMG_MAX, IMG_MIN, IMAGE_VIEWS_MAX, TRACER_ALIVE, TRACER_EMITTERS_MAX,
                    TRACER_FRAME_BYTES, TRACER_FREE, TRACER_HIT, TRACER_OUT, TRACER_STATUS_NAMES, BODY_COLS, BODY_INFO_COLS, BODY_LOG_COLS, BODY_MAX,
                    MONITOR_COLS, MONITOR_LOG_COLS, MONITOR_PROFILE_COLS, MONITOR_STATIONS_MAX, HEAT_COLS, HEAT_LOG_COLS, HEAT_NAMES, HEAT_PARAMS,
-                   HEAT_UP, SOURCE_HEAT, FluidsimError)
+                   HEAT_UP, SOURCE_HEAT, ZONE_COLS, ZONE_MAX, ZONE_MODES, ZONE_NAMES, ZONE_PARAMS, FluidsimError)
 from .simulation import (FORCE_LOG_DTYPE, RESIDUAL_LOG_DTYPE, Simulation, comm_unique_id, loadSTLIntoObstacles, pressure_force,
                          solve_reduction, BODY_INFO_DTYPE, BODY_LOG_DTYPE, pressure_moment, shift_moment,
                          MONITOR_LOG_NAMES, MONITOR_NAMES, MONITOR_PROFILE_NAMES, monitor_cfl)
 from . import inflow  # noqa: F401  (host-side helpers of Simulation.set_inflow)
+from . import zones  # noqa: F401  (rows for Simulation.set_zones)
 
 __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_force", "FORCE_LOG_DTYPE", "FluidsimError",
            "RESIDUAL_LOG_DTYPE", "solve_reduction",
@@ -23,6 +24,7 @@ __all__ = ["Simulation", "loadSTLIntoObstacles", "comm_unique_id", "pressure_for
            "inflow", "MONITOR_COLS", "MONITOR_PROFILE_COLS", "MONITOR_STATIONS_MAX", "MONITOR_LOG_COLS", "MONITOR_NAMES",
            "MONITOR_PROFILE_NAMES", "MONITOR_LOG_NAMES", "monitor_cfl",
            "HEAT_PARAMS", "HEAT_COLS", "HEAT_LOG_COLS", "HEAT_NAMES", "HEAT_UP", "SOURCE_HEAT",
+           "zones", "ZONE_MAX", "ZONE_PARAMS", "ZONE_COLS", "ZONE_NAMES", "ZONE_MODES",
            "FIELD_NAMES", "STAT_NAMES",
            "STAT_MEAN_DENS", "STAT_MEAN_VX", "STAT_MEAN_VY", "STAT_MEAN_VZ", "STAT_MEAN_P", "STAT_UU", "STAT_VV", "STAT_WW",
            "STAT_UV", "STAT_UW", "STAT_VW", "STAT_PP", "STAT_TKE", "STAT_RAW",

@@ -73,6 +73,12 @@ HEAT_LOG_COLS = 10      # FS_HEAT_LOG_COLS: step, then the budget
 SOURCE_HEAT = 8192      # FS_SOURCE_HEAT
 HEAT_NAMES = ["cells", "sum", "sum_sq", "max", "min", "held", "loss", "outflow", "inflow"]
 HEAT_UP = {"+x": 0, "-x": 1, "+y": 2, "-y": 3, "+z": 4, "-z": 5}
+# momentum zones: zones of a handle, entries of a zone's row, columns of a zone's budget, modes of fs_zones
+ZONE_MAX = 8            # FS_ZONE_MAX
+ZONE_PARAMS = 20        # FS_ZONE_PARAMS
+ZONE_COLS = 7           # FS_ZONE_COLS
+ZONE_NAMES = ["cells", "dvx", "dvy", "dvz", "dke", "flux", "max_speed"]
+ZONE_MODES = {"off": 0, "manual": 1, "step": 2}
 
 
 class FluidsimError(RuntimeError):
@@ -145,6 +151,12 @@ _SIGNATURES = {
     "fs_heat_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "fs_heat_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     "fs_heat_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    "fs_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "fs_zones_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fs_zone_apply": (C.c_int, [C.c_void_p]),
+    "fs_zone_budget": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fs_zone_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "fs_zone_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "fs_inflow_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "fs_inflow_gust": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fs_inflow_plane": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_size_t]),

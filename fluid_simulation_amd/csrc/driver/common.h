@@ -9,6 +9,7 @@
 #include "../volume.h"
 #include "../monitor.h"
 #include "../heat.h"
+#include "../zones.h"
 #include "../step_ring.h"
 
 #include <hip/hip_runtime_api.h>
@@ -48,7 +49,7 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(FS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_HEAT, FAM_COUNT };
+enum Family { FAM_SWEEP = 0, FAM_PAIR, FAM_TRIPLE, FAM_DIV, FAM_GRAD, FAM_ADVECT, FAM_BOUNDS, FAM_MISC, FAM_COMM, FAM_MG, FAM_FORCES, FAM_RESIDUAL, FAM_FLOWSTATS, FAM_VORTEX, FAM_PROBES, FAM_BODYFORCES, FAM_IMAGES, FAM_TRACERS, FAM_VOLUME, FAM_CONFINE, FAM_MONITOR, FAM_INFLOW, FAM_HEAT, FAM_ZONES, FAM_COUNT };
 // the names: two tables that stay in fluidsim.cpp (tests/test_inflow_cpu.py reads the first one's text there)
 extern const char* const kFamilyNames[FAM_HEAT];
 extern const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT];
@@ -60,6 +61,7 @@ constexpr int NPOOL = FS_NFIELDS + 3;   // named fields + ping-pong scratch
 constexpr int NHEAT = 2, NSLOT = FS_NFIELDS + NHEAT, NPOOL_MAX = NPOOL + NHEAT;
 constexpr int F_THETA = FS_NFIELDS, F_THETA_PREV = FS_NFIELDS + 1;
 static_assert(fs::HEAT_PARAMS == FS_HEAT_PARAMS && fs::HEAT_COLS == FS_HEAT_COLS && FS_HEAT_LOG_COLS == 1 + FS_HEAT_COLS, "heat.h restates the header");
+static_assert(fs::ZONE_PARAMS == FS_ZONE_PARAMS && fs::ZONE_COLS == FS_ZONE_COLS && fs::ZONE_MAX == FS_ZONE_MAX, "zones.h restates the header");
 
 struct Span {
     hipEvent_t a, b;
@@ -115,6 +117,10 @@ struct fs_sim {
     double heat[fs::HEAT_PARAMS] = {0, 0, 0, 0, 2, 0, 0, 0, 1, 1, 1, 1, 1, 1, 0};
     int heat_mode() const { return (int)heat[fs::HP_MODE]; }
     long n_heat_apply = 0, n_heat_transport = 0;   // passes done, inside steps and by fs_heat_apply / fs_heat_transport (fs_get_int)
+    // momentum zones (zones.h): the rows as fs_zones last set them; mode 0 = off, 1 = manual, 2 = in fs_step
+    double zones[fs::ZONE_MAX * fs::ZONE_PARAMS] = {0};
+    int zone_n = 0, zone_mode = 0, zone_log = 0;
+    long n_zone_apply = 0;       // passes done, inside steps and by fs_zone_apply (fs_get_int)
     // turbulent inflow (inflow.h): with "inflow" on, fs_step writes the x = 1 face from these instead of (speed, 0, 0)
     bool inflow = false;
     int inflow_n = 0;            // "inflow_eddies"

@@ -30,6 +30,7 @@
 #include "confine.h"
 #include "inflow.h"
 #include "heat.h"
+#include "zones.h"
 #include "sample.h"
 #include "step_ring.h"
 #include "options.h"
@@ -47,6 +48,7 @@
 #include "driver/monitor.h"
 #include "driver/inflow.h"
 #include "driver/heat.h"
+#include "driver/zones.h"
 #include "driver/confine.h"
 #include "driver/viewer.h"
 
@@ -70,7 +72,7 @@ constexpr bool Z_ALTERNATE_AUTO = FS_Z_ALTERNATE_AUTO != 0;
 constexpr size_t INFINITY_CACHE_BYTES = (size_t)256 << 20;
 const char* const kFamilyNames[FAM_HEAT] = { "sweep", "sweep_pair", "sweep_triple", "divergence", "gradient", "advect", "bounds", "misc", "comm", "multigrid", "forces", "residual", "flow_stats", "vortex", "probes", "body_forces", "images", "tracers", "volume", "confinement", "monitor", "inflow" };
 // the families added since (tests/test_inflow_cpu.py pins the text of the table above): FAM_HEAT onwards
-const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT] = { "heat" };
+const char* const kLaterFamilyNames[FAM_COUNT - FAM_HEAT] = { "heat", "zones" };
 
 // ---------------------------------------------------------------------------------------
 template <class T>
@@ -139,6 +141,7 @@ struct Engine : EngineBase {
     Monitor<T> monitor{*this};
     Inflow<T> inflow{*this};
     Heat<T> heat{*this};
+    Zones<T> zones{*this};
     Confine<T> confine{*this};
     Viewer<T> viewer{*this};
     static constexpr int SLOT_POOL = 0, SLOT_GATHER = NPOOL, SLOT_MG = NPOOL + 4;   // FSIPC export slots: one per arena chunk
@@ -1266,7 +1269,14 @@ struct Engine : EngineBase {
         // heat, mode 2: inlet and wall temperatures and the buoyancy force come next, still before the reference's step
         const bool heat_step = S->heat_mode() == 2;
         if (heat_step && (rc = heat.apply_pass("fs_step"))) return rc;
-        const bool gs = (S->solver == FS_SOLVER_GS_LEX);
+        // zones, mode 2: the log record -- the budget of the state the pass is about to change -- then the pass, the last thing
+        // before the reference's step
+        if (S->zone_mode == 2) {
+            if ((rc = zones.need("fs_step"))) return rc;
+            zones.record();
+            if ((rc = zones.apply_pass("fs_step"))) return rc;
+        }
+        const bool gs =(S->solver == FS_SOLVER_GS_LEX);
         for (int f : { FS_VX, FS_VY, FS_VZ })
             if ((rc = unalias(f))) return rc;
         if (S->inflow) {                                 // "inflow": the face from the inflow generator, at step number steps_total
@@ -1991,6 +2001,8 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "heat_mode") *out = s->heat_mode();                     // 0 off, 1 manual, 2 in fs_step (fs_heat_params)
     else if (n == "heat_applies") *out = (int)std::min<long>(s->n_heat_apply, 2147483647L);       // passes A done, in steps and by fs_heat_apply
     else if (n == "heat_transports") *out = (int)std::min<long>(s->n_heat_transport, 2147483647L);   // passes B done, in steps and by fs_heat_transport
+    else if (n == "zone_mode") *out = s->zone_mode;                       // 0 off, 1 manual, 2 in fs_step (fs_zones)
+    else if (n == "zone_applies") *out = (int)std::min<long>(s->n_zone_apply, 2147483647L);       // zone passes done, in steps and by fs_zone_apply
     else if (n == "confinement_passes") *out = (int)std::min<long>(s->n_confine, 2147483647L);   // confinement passes done, in steps and by fs_confine_vorticity
     else if (n == "monitor_log") *out = s->monitor_log;
     else if (n == "monitor_every") *out = (int)s->monitor_every;
@@ -2469,6 +2481,63 @@ int fs_heat_set(fs_sim* s, const void* src, size_t n_elems, int elem_size)
     ENGINE_OR_RETURN(s);
     if (!src) return fail(FS_EINVAL, "fs_heat_set: null buffer");
     return ENG(s, heat.set(src, n_elems, elem_size));
+}
+int fs_zones(fs_sim* s, const double* par, int n_zones, int mode, int log)
+{
+    ENGINE_OR_RETURN(s);
+    if (mode < 0 || mode > 2) return fail(FS_EINVAL, "fs_zones: mode = %d, it is 0 (off), 1 (manual) or 2 (in fs_step)", mode);
+    if (n_zones < 0 || n_zones > FS_ZONE_MAX) return fail(FS_EINVAL, "fs_zones: n_zones = %d, a handle takes 0 .. FS_ZONE_MAX = %d zones", n_zones, FS_ZONE_MAX);
+    if (log < 0 || log > 1048576) return fail(FS_EINVAL, "fs_zones: log = %d, it is a record count 0 .. 2^20", log);
+    if (n_zones == 0 || mode == 0) return ENG(s, zones.config(nullptr, 0, 0, 0));
+    if (!par) return fail(FS_EINVAL, "fs_zones: null argument");
+    static const char* const name[FS_ZONE_PARAMS] = { "shape", "axis", "box x0", "box x1", "box y0", "box y1", "box z0", "box z1",
+                                                      "centre 1", "centre 2", "radius", "g x", "g y", "g z", "D x", "D y", "D z",
+                                                      "F x", "F y", "F z" };
+    const int ext[3] = { s->W, s->H, s->D };
+    for (int z = 0; z < n_zones; ++z) {
+        const double* p = par + (size_t)z * FS_ZONE_PARAMS;
+        for (int k = 0; k < FS_ZONE_PARAMS; ++k)
+            if (!std::isfinite(p[k])) return fail(FS_EINVAL, "fs_zones: zone %d, par[%d] (%s) is not finite", z, k, name[k]);
+        auto whole = [&](int k, double lo, double hi) { return p[k] >= lo && p[k] <= hi && p[k] == std::floor(p[k]); };
+        if (!whole(fs::ZP_SHAPE, 0, 1)) return fail(FS_EINVAL, "fs_zones: zone %d, par[0] (shape) is 0 (box) or 1 (cylinder)", z);
+        if (!whole(fs::ZP_AXIS, 0, 2)) return fail(FS_EINVAL, "fs_zones: zone %d, par[1] (axis) is 0, 1 or 2 = x, y, z", z);
+        for (int a = 0; a < 3; ++a) {
+            const int lo = fs::ZP_X0 + 2 * a, hi = lo + 1;
+            if (!whole(lo, 1, ext[a]) || !whole(hi, 1, ext[a]) || p[lo] > p[hi])
+                return fail(FS_EINVAL, "fs_zones: zone %d, par[%d], par[%d] (%s, %s) must be whole cells with 1 <= lo <= hi <= %d", z, lo,
+                            hi, name[lo], name[hi], ext[a]);
+        }
+        for (int k : { (int)fs::ZP_RADIUS, (int)fs::ZP_DX, (int)fs::ZP_DY, (int)fs::ZP_DZ, (int)fs::ZP_FX, (int)fs::ZP_FY, (int)fs::ZP_FZ })
+            if (!(p[k] >= 0.0)) return fail(FS_EINVAL, "fs_zones: zone %d, par[%d] (%s) must be >= 0", z, k, name[k]);
+    }
+    return ENG(s, zones.config(par, n_zones, mode, log));
+}
+int fs_zones_get(fs_sim* s, double* par, int* n_zones, int* mode, int* log)
+{
+    if (!s) return fail(FS_EINVAL, "fs_zones_get: null handle");
+    if (par) memcpy(par, s->zones, (size_t)s->zone_n * FS_ZONE_PARAMS * sizeof(double));
+    if (n_zones) *n_zones = s->zone_n;
+    if (mode) *mode = s->zone_mode;
+    if (log) *log = s->zone_log;
+    return FS_OK;
+}
+int fs_zone_apply(fs_sim* s) { ENGINE_OR_RETURN(s); return ENG(s, zones.apply()); }
+int fs_zone_budget(fs_sim* s, double* out, double* per_plane)
+{
+    ENGINE_OR_RETURN(s);
+    if (!out) return fail(FS_EINVAL, "fs_zone_budget: null argument");
+    return ENG(s, zones.budget(out, per_plane));
+}
+int fs_zone_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped)
+{
+    ENGINE_OR_RETURN(s);
+    return ENG(s, zones.log_fetch(rows, max_rows, n_rows, n_dropped));
+}
+int fs_zone_mask(fs_sim* s, uint8_t* dst, size_t n)
+{
+    ENGINE_OR_RETURN(s);
+    if (!dst) return fail(FS_EINVAL, "fs_zone_mask: null buffer");
+    return ENG(s, zones.mask(dst, n));
 }
 int fs_inflow_profile(fs_sim* s, const double* u, const double* rms, size_t n)
 {

@@ -264,4 +264,21 @@ template <class T>
 void launch_heat_budget(hipStream_t st, const GridDesc& g, const HeatPass& p, const T* theta, const T* u, const uint8_t* flags,
                         double* ws, double* result);
 
+// Momentum zones (zones.h has the arithmetic, zones.hip the kernels).  launch_zone_apply: one streaming pass, in place, over the
+// three velocity components; they come out as set_bounds(1, .), (2, .), (3, .) would leave them.
+// launch_zone_budget: the budget of zt.n zones in three launches -- the COLUMN records, the PLANE records, the WHOLE records
+// into `result` (zt.n * ZONE_COLS doubles on the device) -- through the workspace `ws` (zone_workspace_doubles for that many
+// zones, whose PLANE records start at zone_planes_offset); no atomics, every sum in its written order; nothing else is written.
+// launch_zone_mask: bit k of byte (x, y, z) of the dense padded array `dst` ((W+2)(H+2)(D+2) bytes on the device) is set where
+// the cell is a target cell in zone k.  Single GPU (g.zh == 1, both z walls physical).
+struct ZoneTable;
+template <class T>
+void launch_zone_apply(hipStream_t st, const GridDesc& g, const ZoneTable& zt, T* vx, T* vy, T* vz, const uint8_t* flags);
+size_t zone_workspace_doubles(const GridDesc& g, int n_zones);
+size_t zone_planes_offset(const GridDesc& g, int n_zones);
+template <class T>
+void launch_zone_budget(hipStream_t st, const GridDesc& g, const ZoneTable& zt, const T* vx, const T* vy, const T* vz,
+                        const uint8_t* flags, double* ws, double* result);
+void launch_zone_mask(hipStream_t st, const GridDesc& g, const ZoneTable& zt, const uint8_t* flags, uint8_t* dst);
+
 }  // namespace fs

@@ -1,6 +1,6 @@
 // step_ring.h -- the bookkeeping of a per-step log that lives in a ring of `cap` slots: which slot the next record goes
-// to, which records are retained, in which order, and which step each belongs to.  The nine logs of the host driver's parts (driver/*.h: forces,
-// body forces, residuals, probes, images, tracers, volumes, flow monitor, heat) keep their records in device memory and their books here.  Plain C++
+// to, which records are retained, in which order, and which step each belongs to.  The ten logs of the host driver's parts (driver/*.h: forces,
+// body forces, residuals, probes, images, tracers, volumes, flow monitor, heat, zones) keep their records in device memory and their books here.  Plain C++
 // without HIP, so that tests/test_step_ring_cpu.py can run it against a model on the CPU.  Internal to libfluidsim.so.
 #pragma once
 

@@ -608,6 +608,54 @@ class Simulation:
         check(self._L.fs_heat_log(self._h, rows.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
         return (rows, dropped.value) if with_dropped else rows
 
+    # -- momentum zones (include/fluidsim.h, "momentum zones"; single-GPU handles) ----------------------------------------------
+    def set_zones(self, zones, mode="step", log=0):
+        """Sets the momentum zones (fs_zones): `zones` is a sequence of rows of ZONE_PARAMS numbers, as the constructors of
+        fluid_simulation_amd.zones return them (a list of rows, or rows and lists of rows mixed: sponge() returns several).
+        mode "step" applies the pass in every step, "manual" leaves it to apply_zones(), "off" (or no rows) frees everything.
+        log=N keeps the zone budgets of the last N steps (zone_log())."""
+        rows = [np.asarray(z, dtype=np.float64).reshape(-1, _lib.ZONE_PARAMS) for z in ([] if zones is None else zones)]
+        par = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, _lib.ZONE_PARAMS))
+        m = _lib.ZONE_MODES[mode] if isinstance(mode, str) else int(mode)
+        check(self._L.fs_zones(self._h, par.ctypes.data if par.size else None, par.shape[0], m, int(log)))
+
+    def zones(self):
+        """The zones in force (fs_zones_get): (rows (n, ZONE_PARAMS), mode, log)."""
+        par = np.zeros((_lib.ZONE_MAX, _lib.ZONE_PARAMS), dtype=np.float64)
+        n, mode, log = C.c_int(), C.c_int(), C.c_int()
+        check(self._L.fs_zones_get(self._h, par.ctypes.data, C.byref(n), C.byref(mode), C.byref(log)))
+        return par[:n.value].copy(), mode.value, log.value
+
+    def apply_zones(self):
+        """The zone pass now (fs_zone_apply)."""
+        check(self._L.fs_zone_apply(self._h))
+
+    def zone_budget(self, per_plane=False):
+        """What a zone pass now would do (fs_zone_budget; changes nothing): (n_zones, ZONE_COLS) float64 -- the columns are
+        ZONE_NAMES; per_plane=True returns (that, the same per plane: (depth, n_zones, ZONE_COLS))."""
+        n = self.zones()[0].shape[0]
+        out = np.zeros((n, _lib.ZONE_COLS), dtype=np.float64)
+        pp = np.zeros((self.depth, n, _lib.ZONE_COLS), dtype=np.float64) if per_plane else None
+        check(self._L.fs_zone_budget(self._h, out.ctypes.data, None if pp is None else pp.ctypes.data))
+        return (out, pp) if per_plane else out
+
+    def zone_log(self, with_dropped=False):
+        """Drains the zone log (set_zones(log=N); fs_zone_log): one row per retained record, oldest first, (n, 1 + n_zones *
+        ZONE_COLS) float64 -- the step, then the budget taken before that step's pass.  with_dropped=True returns (rows,
+        records the ring overwrote since the last drain)."""
+        cols = 1 + self.zones()[0].shape[0] * _lib.ZONE_COLS
+        n, dropped = C.c_long(), C.c_long()
+        check(self._L.fs_zone_log(self._h, None, 0, C.byref(n), C.byref(dropped)))
+        rows = np.zeros((n.value, cols), dtype=np.float64)
+        check(self._L.fs_zone_log(self._h, rows.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        return (rows, dropped.value) if with_dropped else rows
+
+    def zone_mask(self):
+        """Which target cells lie in which zone (fs_zone_mask): uint8, shaped like get(); bit k = zone k."""
+        out = np.zeros(self.shape, dtype=np.uint8)
+        check(self._L.fs_zone_mask(self._h, out.ctypes.data, out.size))
+        return out
+
     def set_inflow(self, profile=None, rms=None, gust=None, eddies=0, sigma=4.0, u_rms=0.0, convect="auto", seed=1):
         """Configures the inflow generator and turns it on (include/fluidsim.h, "turbulent inflow"; single-GPU handles): every
         step then writes the x = 1 face as v_x = g(t) * U + r * u'_x, v_y = r * u'_y, v_z = r * u'_z.  `profile` (U) and

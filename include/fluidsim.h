@@ -692,6 +692,78 @@ int fs_heat_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dr
 int fs_heat_get(fs_sim* s, void* dst, size_t n_elems, int elem_size);
 int fs_heat_set(fs_sim* s, const void* src, size_t n_elems, int elem_size);
 
+/* ---- momentum zones (beyond the reference: it can put nothing into the flow that is not a solid voxel) ----
+ *
+ * A zone is a region of cells with a momentum source and a resistance: a screen, a honeycomb, a radiator as a porous block, a
+ * fan, a rotor as an actuator disk, a sponge layer in front of the outlet.  Up to FS_ZONE_MAX = 8 zones, each a row of
+ * FS_ZONE_PARAMS = 20 finite doubles.  Default off: a handle without zones allocates and launches nothing for them.  Single
+ * GPU only: with a communicator (the FSNULL one included) every entry below but switching off, and fs_step with zones on, is
+ * FS_EINVAL.  Both precisions, every solver mode.  Zones hold no state: a resumed run needs nothing of them.
+ *
+ * A ZONE'S ROW:
+ *    par[0]      shape: 0 = box, 1 = cylinder;   par[1] axis: 0, 1, 2 = x, y, z -- the cylinder's axis and the direction of the
+ *                flux column of the budget.
+ *    par[2..7]   the box x0, x1, y0, y1, z0, z1 in whole cells, 1 <= lo <= hi <= extent.  A cylinder is clipped to it too: that
+ *                is its length.
+ *    par[8], [9] the cylinder's centre c1, c2 in cell coordinates (doubles) on the two axes other than `axis`, lower axis first;
+ *    par[10]     its radius >= 0.
+ *    par[11..13] the acceleration g (any finite value);   par[14..16] the linear resistance D_a >= 0 per axis;
+ *    par[17..19] the quadratic resistance F_a >= 0 per axis.
+ * IN: cell (x, y, z) is IN zone k if it is inside the box and, for a cylinder, p*p + q*q <= R2, all three values rounded
+ * doubles: p = (double)i - c1 and q = (double)j - c2 with i, j the cell's indices on the two other axes (lower axis first),
+ * R2 = radius * radius computed once on the host.
+ * A TARGET cell is an interior cell whose flag byte has neither F_SOLID nor F_NEAR: obs != 1 and no interior 6-neighbour with
+ * obs == 1.  The other interior cells end at 0 under setBounds(1..3) anyway.
+ *
+ * THE PASS, fs_zone_apply: one streaming HIP kernel over v_x, v_y, v_z, in place.  All arithmetic is fp64 on the stored values
+ * widened, for fp32 and fp64 handles alike; every written operation is rounded once, in this order, without contraction.
+ * DT = (double)dt; G_a = DT * g_a, computed per zone on the host.  A target cell that is in no zone keeps its three stored
+ * values bit for bit (-0.0 too).  A target cell in at least one zone starts with u = (double)v and goes through its zones in
+ * increasing index, each STAGE reading the previous stage's fp64 result:
+ *     k0 = (ux*ux + uy*uy) + uz*uz;   m = sqrt(k0)   (correctly rounded)
+ *     for a = x, y, z:   n = u_a + G_a;  r = F_a * m;  s = D_a + r;  t = DT * s;  d = 1.0 + t;  u_a' = n / d
+ *     k1 = (ux'*ux' + uy'*uy') + uz'*uz'
+ * and after the last stage v_a = (T)u_a, T the handle's precision.  The denominators are >= 1: the implicit form is stable for
+ * any D, F and dt, so a sponge may be as stiff as one likes.  (x / 1.0 is x: an implementation may skip the divisions of a
+ * zone with D = F = 0 where m is finite.)  Afterwards the three arrays are exactly as fs_set_bounds(1, FS_VX), (2, FS_VY),
+ * (3, FS_VZ) would leave them: ghost faces from the un-zeroed values -- the stored ones where the cell is no target cell --
+ * then solid cells and their fluid neighbours zeroed.  One formula covers every use: a fan is g; a porous block D and F; a
+ * flow straightener a large D on the two transverse axes; a rotor disk F on its axis; a sponge D ramped over a few thin zones.
+ *
+ * THE BUDGET, fs_zone_budget: a pure function of the present state -- what a pass now would do; no field is written.  Per zone
+ * FS_ZONE_COLS = 7 doubles over the target cells in the zone, from that zone's stage as defined above (the earlier zones'
+ * stages are applied first):
+ *    0 cells   1, 2, 3 sum of u_a' - u_a   4 sum of 0.5 * (k1 - k0)   5 sum of u_axis, the stage's input
+ *    6 max of m, by "if (a > m) m = a" from -Inf.
+ * ORDER: the flow monitor's.  A COLUMN (z, x) adds its cells in increasing y from +0.0; a PLANE combines its columns in
+ * increasing x, the WHOLE the planes in increasing z.  Cells outside the zone are skipped, not added as zeros (a column without
+ * cells is +0.0, or -Inf in column 6).  out takes n_zones * 7 doubles, [zone][column]; per_plane, which may be NULL, d * n_zones
+ * * 7 doubles, [z - 1][zone][column].  INTEGRATION.md section 6m converts them to thrust, power and volume flux.
+ *
+ * fs_zones: the zones (n_zones rows of 20 at par), the mode -- 0 off, 1 manual (the pass runs only when called), 2 in fs_step --
+ * and the records the per-step zone log keeps (0 = off .. 2^20), in one atomic call: a bad value is FS_EINVAL with a message
+ * that names the zone and the entry, and nothing changes.  n_zones == 0 or mode 0 frees everything (par may be NULL).  A changed
+ * record or zone count clears the log.  fs_zones_get returns the zones in force: the rows into par (room for FS_ZONE_MAX rows;
+ * may be NULL), their count, the mode and the log's record count (each may be NULL).
+ * fs_step in mode 2: confinement (if on), heat's pass A (if on), the zone log's record -- the budget of the state the pass is
+ * about to change, { the running step's number, n_zones * 7 } -- the zone pass, then the reference's step exactly as without
+ * zones.  It is bit-identical to fs_zone_apply, fs_step on a mode-1 handle.
+ * fs_zone_log: the rows { step, n_zones * 7 } on a device ring written without a host synchronisation; the fetch has the shape
+ * of fs_heat_log and drains the log.
+ * fs_zone_mask: n = the padded size, one byte per cell as fs_get_field orders them; bit k is set where the cell is a target
+ * cell in zone k; ghost cells take 0.
+ * Timing family "zones"; fs_get_int "zone_mode", "zone_applies" (passes done, those inside steps included).
+ */
+#define FS_ZONE_MAX 8
+#define FS_ZONE_PARAMS 20
+#define FS_ZONE_COLS 7
+int fs_zones(fs_sim* s, const double* par, int n_zones, int mode, int log);
+int fs_zones_get(fs_sim* s, double* par, int* n_zones, int* mode, int* log);
+int fs_zone_apply(fs_sim* s);
+int fs_zone_budget(fs_sim* s, double* out, double* per_plane);
+int fs_zone_log(fs_sim* s, double* rows, long max_rows, long* n_rows, long* n_dropped);
+int fs_zone_mask(fs_sim* s, uint8_t* dst, size_t n);
+
 /* ---- turbulent inflow (beyond the reference: its only inflow is (speed, 0, 0) on the x = 1 face, simulation.cpp:103-105) ----
  *
  * An inflow generator for boundary layers, gusts and free-stream turbulence.  With option "inflow" = "on" fs_step writes, where

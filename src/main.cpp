@@ -89,6 +89,11 @@
 //                  float32 in the frames' layout whenever a frame is dumped (the run then goes step by step, as for
 //                  --images).  The other --heat-* flags need --heat.  A --resume run starts the temperature from zero: the
 //                  dumped frames do not hold it.  Single GPU.
+//   --zone SPEC    a momentum zone (fs_zones, mode 2; include/fluidsim.h, "momentum zones"): SPEC is the zone's 20 numbers,
+//                  comma-separated -- shape, axis, x0, x1, y0, y1, z0, z1, c1, c2, radius, gx, gy, gz, Dx, Dy, Dz, Fx, Fy, Fz.
+//                  Repeatable, up to 8 zones, applied in the order given.  --zone-log FILE.csv: every zone's budget before each
+//                  step's pass (fs_zone_log's columns, numbers as %.17g); it needs --zone.  Zones hold no state: --resume
+//                  needs nothing of them.  Single GPU.
 // Each flag can also be given as an environment variable FS_GRID, FS_STEPS, ...
 #include <algorithm>
 #include <chrono>
@@ -295,6 +300,33 @@ int write_heat_log(fs_sim* sim, const char* path)
         const double* r = &rows[(size_t)i * FS_HEAT_LOG_COLS];
         fprintf(fp, "%ld", (long)r[0]);
         for (int k = 1; k < FS_HEAT_LOG_COLS; ++k) fprintf(fp, ",%.17g", r[k]);
+        fprintf(fp, "\n");
+    }
+    const bool ok = fclose(fp) == 0;
+    if (!ok) fprintf(stderr, "simulation.out: writing %s failed\n", path);
+    return ok ? 0 : 1;
+}
+
+// the zone log of the run -> CSV (the columns of Simulation.zone_log() in the Python package)
+int write_zone_log(fs_sim* sim, int n_zones, const char* path)
+{
+    static const char* const name[FS_ZONE_COLS] = { "cells", "dvx", "dvy", "dvz", "dke", "flux", "max_speed" };
+    const int cols = 1 + n_zones * FS_ZONE_COLS;
+    long n = 0, dropped = 0;
+    if (fs_zone_log(sim, nullptr, 0, &n, &dropped)) return 1;
+    std::vector<double> rows((size_t)n * cols);
+    if (fs_zone_log(sim, rows.data(), n, &n, &dropped)) return 1;
+    if (dropped) fprintf(stderr, "simulation.out: %ld zone records were overwritten before they were written\n", dropped);
+    FILE* fp = fopen(path, "w");
+    if (!fp) { fprintf(stderr, "simulation.out: cannot write %s\n", path); return 1; }
+    fprintf(fp, "step");
+    for (int z = 0; z < n_zones; ++z)
+        for (int k = 0; k < FS_ZONE_COLS; ++k) fprintf(fp, ",z%d_%s", z, name[k]);
+    fprintf(fp, "\n");
+    for (long i = 0; i < n; ++i) {
+        const double* r = &rows[(size_t)i * cols];
+        fprintf(fp, "%ld", (long)r[0]);
+        for (int k = 1; k < cols; ++k) fprintf(fp, ",%.17g", r[k]);
         fprintf(fp, "\n");
     }
     const bool ok = fclose(fp) == 0;
@@ -552,6 +584,8 @@ int main(int argc, char** argv)
     bool heat = false, heat_other = false;
     double heat_par[FS_HEAT_PARAMS] = { 2, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };   // mode 2, up = +y; a box of zeros = the whole domain
     std::string heat_log_path, heat_dump_path;
+    std::vector<double> zone_rows;                       // --zone, FS_ZONE_PARAMS numbers each
+    std::string zone_log_path;
     int dump_every = 1;
     std::vector<int> view_spec;
     std::vector<double> view_range;
@@ -631,6 +665,18 @@ int main(int argc, char** argv)
         }
         if (key == "heat-log") { heat_other = true; heat_log_path = val; return true; }
         if (key == "heat-dump") { heat_other = true; heat_dump_path = val; return true; }
+        if (key == "zone") {
+            const char* p = val;
+            for (int k = 0; k < FS_ZONE_PARAMS; ++k) {
+                char* end = nullptr;
+                const double v = strtod(p, &end);
+                if (end == p || *end != (k + 1 < FS_ZONE_PARAMS ? ',' : '\0')) return false;
+                zone_rows.push_back(v);
+                p = end + 1;
+            }
+            return true;
+        }
+        if (key == "zone-log") { zone_log_path = val; return true; }
         if (key == "monitor-every") { monitor_every = atol(val); return monitor_every >= 1; }
         if (key == "monitor-stations") { options.push_back({ "monitor_stations", val }); return true; }
         return false;
@@ -641,7 +687,7 @@ int main(int argc, char** argv)
                                         "image-view", "tracers", "tracer-emitters", "tracer-every", "tracer-out", "volume", "volume-view", "volume-size",
                                         "volume-range", "volume-opacity", "volume-every", "confinement", "monitor", "monitor-every", "monitor-stations",
                                         "inflow-profile", "inflow-gust", "inflow-eddies", "inflow-sigma", "inflow-rms", "inflow-convect", "inflow-seed",
-                                        "heat", "heat-up", "heat-inlet", "heat-wall", "heat-log", "heat-dump" };
+                                        "heat", "heat-up", "heat-inlet", "heat-wall", "heat-log", "heat-dump", "zone", "zone-log" };
     for (const char* k : keys) {
         std::string env = "FS_";
         for (const char* p = k; *p; ++p) env += (*p == '-') ? '_' : (char)toupper(*p);
@@ -671,6 +717,14 @@ int main(int argc, char** argv)
     }
     if (heat_other && !heat) {
         fprintf(stderr, "simulation.out: --heat-up, --heat-inlet, --heat-wall, --heat-log and --heat-dump need --heat KAPPA,BETA,ALPHA\n");
+        return 2;
+    }
+    if (!zone_log_path.empty() && zone_rows.empty()) {
+        fprintf(stderr, "simulation.out: --zone-log needs --zone SPEC\n");
+        return 2;
+    }
+    if (zone_rows.size() > (size_t)FS_ZONE_MAX * FS_ZONE_PARAMS) {
+        fprintf(stderr, "simulation.out: --zone was given %zu times, a run takes %d zones\n", zone_rows.size() / FS_ZONE_PARAMS, FS_ZONE_MAX);
         return 2;
     }
     if (!stl_given) {
@@ -731,7 +785,11 @@ int main(int argc, char** argv)
         if (fs_heat_params(sim, heat_par, FS_HEAT_PARAMS)) return die("fs_heat_params");
         if (!heat_dump_path.empty()) remove(heat_dump_path.c_str());   // the run appends to it
     }
-    bool stepwise = !heat_dump_path.empty();             // --images, --volume: the run's frames do not fit the ring; --heat-dump
+    const int n_zones = (int)(zone_rows.size() / FS_ZONE_PARAMS);
+    if (n_zones > 0 &&
+        fs_zones(sim, zone_rows.data(), n_zones, 2, zone_log_path.empty() ? 0 : (int)std::min(1048576L, (long)std::max(iter, 0))))
+        return die("fs_zones");
+    bool stepwise = !heat_dump_path.empty();            // --images, --volume: the run's frames do not fit the ring; --heat-dump
     long image_ring = 0;
     if (!images_dir.empty()) {
         if (view_spec.empty()) {                         // the 2-D viewer's density and v_x frames (gui.py:271-279)
@@ -814,6 +872,7 @@ int main(int argc, char** argv)
     if (!residuals_path.empty() && write_residuals(sim, residuals_path.c_str())) return die("fs_residual_log");
     if (!monitor_path.empty() && write_monitor(sim, monitor_path.c_str(), width, height, depth, dt)) return die("fs_monitor_log");
     if (!heat_log_path.empty() && write_heat_log(sim, heat_log_path.c_str())) return die("fs_heat_log");
+    if (!zone_log_path.empty() && write_zone_log(sim, n_zones, zone_log_path.c_str())) return die("fs_zone_log");
     if (!probe_log_path.empty() && write_probes(sim, probe_log_path.c_str(), (long)(probe_cells.size() / 3))) return die("fs_probe_log");
     if (!images_dir.empty() && write_images(sim, images_dir, view_spec)) return die("writing the images");
     if (!volume_dir.empty() && write_volumes(sim, volume_dir, volume_cols, volume_rows)) return die("writing the volume frames");
