@@ -193,11 +193,13 @@ def main():
     g5_stock_run()
     g6_stock_run_console()
     g7_live_ref_cases()
+    g8_rough_passes()
     manifest = dict(
         compiler=subprocess.check_output(["g++", "--version"]).decode().splitlines()[0],
         flags="-std=c++20 -O2 -fopenmp -fPIC (reference Makefile:5 + -fPIC)",
         env="OMP_NUM_THREADS=1",
         command="OMP_NUM_THREADS=1 python3 oracle/make_golden.py",
+        g8_command="OMP_NUM_THREADS=1 python3 oracle/make_golden.py g8",
     )
     with open(os.path.join(OUT, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1)
@@ -300,11 +302,55 @@ def g6_stock_run_console():
     print("wrote g6_stock_run_stdout.txt (%d bytes)" % len(out.stdout))
 
 
+def g8_rough_passes():
+    """Every pass of the step, and two whole steps, on the rough and special-valued inputs of tests/rough_cases.py: what the
+    reference computes for each (grid, obstacle kind, value variant), as SHA-256 digests with every NaN mapped to one
+    canonical NaN (the reference's NaN sign and payload depend on its compiler).  The digest of every input array is
+    recorded too, so a drift of numpy's generator shows as "recipe changed".  Arrays are stored for 5x3x2 and for a
+    subset of 37x21x9 with 15 % solids (both variants) and face solids (g8_rough_37x21x9.npz: all of them would pass the
+    size of the largest fixture), so that a failure can be located.  The conditions the tests
+    repeat on the recorded numbers are asserted here while recording."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rough_cases as R
+    cases, stored = [], {}
+    for W, H, D, obs_kind, variant in R.recorded_cases():
+        name = R.case_id(W, H, D, obs_kind, variant)
+        inp = R.case_inputs(W, H, D, obs_kind, variant)
+        handles, outputs = {}, {}
+        for ps in R.pass_list(inp, variant):
+            if ps["acc"] not in handles:
+                handles[ps["acc"]] = O.Reference(W, H, D, iter=1, acc=ps["acc"])
+            outputs.update(R.run_pass(handles[ps["acc"]], inp, ps))
+        for h in handles.values():
+            h.close()
+        worst, fewest = R.check_conditions(name, variant, outputs)
+        rec = dict(id=name, W=W, H=H, D=D, obs=obs_kind, variant=variant, seed=R.SEED, acc=R.ACC,
+                   inputs={k: R.digest(v) for k, v in sorted(inp.items())},
+                   outputs={k: R.digest(v) for k, v in outputs.items()},
+                   solids=int(np.count_nonzero(inp["obs"][1:-1, 1:-1, 1:-1] == 1)), enclosed=R.enclosed_cells(inp["obs"]))
+        if variant == "nonfinite":
+            rec.update(nan_share={k: round(R.nan_share(v), 6) for k, v in outputs.items()},
+                       nonfinite={k: R.nonfinite_cells(v) for k, v in outputs.items()})
+            print("%-28s NaN share <= %.2f %%, non-finite cells >= %d" % (name, 100 * worst, fewest))
+        cases.append(rec)
+        if (W, H, D, obs_kind, variant) in R.STORED_CASES:
+            for k in R.stored_outputs(W, H, D, variant, outputs):
+                stored[name + "__" + k] = R.canon(outputs[k])
+    meta = dict(kind="rough_passes", recipe="tests/rough_cases.py", dt=0.05, diff=2.0e-5, speed=30, lin_accs=list(R.LIN_ACCS),
+                coeffs=[list(c) for c in R.COEFFS], nan_share_max=R.NAN_SHARE_MAX, nonfinite_min=R.NONFINITE_MIN, cases=cases)
+    with open(os.path.join(OUT, "g8_rough_digests.json"), "w") as f:
+        json.dump(meta, f, indent=0, sort_keys=True)
+    print("wrote g8_rough_digests.json (%d cases)" % len(cases))
+    # np.savez_compressed stamps no time into its members (zipfile writes the 1980 epoch for arrays it is handed), so the
+    # file is the same bytes on every run
+    save("g8_rough_37x21x9", dict(kind="rough_passes_arrays", cases=[R.case_id(*c) for c in R.STORED_CASES]), **stored)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("g6", "g7"):      # add one fixture without regenerating the others
+    if len(sys.argv) > 1 and sys.argv[1] in ("g6", "g7", "g8"):      # add one fixture without regenerating the others
         if os.environ.get("OMP_NUM_THREADS") != "1":
             sys.exit("run with OMP_NUM_THREADS=1")
         O.build()
-        g6_stock_run_console() if sys.argv[1] == "g6" else g7_live_ref_cases()
+        {"g6": g6_stock_run_console, "g7": g7_live_ref_cases, "g8": g8_rough_passes}[sys.argv[1]]()
     else:
         main()
