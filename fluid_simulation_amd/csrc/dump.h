@@ -5,9 +5,16 @@
 // (2.7 GB per step at 512^3).  Here a frame is packed on the device into one of
 // two staging buffers, copied to pinned host memory on a separate stream, and written by a
 // host thread, so the next step's kernels run while the previous frame is still on its way
-// to disk.  The bytes and their order in the files are unchanged.
+// to disk.  The bytes and their order in the files are unchanged.  The part that touches the files is dump_files.h.
+//
+// Errors: a failed write, flush or copy is kept by the writer and handed to the first acquire() or flush() that follows; that
+// call reports it once and the writer is clean again, so one full disk does not fail every later call on the handle.  Both
+// calls return only when the frames they wait for are out of the writer's hands, whatever happened to them: the caller may
+// close the files after a flush(), failed or not.
 #pragma once
 #include <hip/hip_runtime_api.h>
+
+#include "dump_files.h"
 
 #include <condition_variable>
 #include <cstdio>
@@ -19,7 +26,7 @@
 namespace fs {
 
 struct FrameWriter {
-    static constexpr int NSLOT = 2, NFILE = 5;
+    static constexpr int NSLOT = 2, NFILE = DUMP_NFILE;
     struct Job {
         int slot;
         long nloc;        // floats per field in this frame
@@ -40,6 +47,7 @@ struct FrameWriter {
     std::deque<Job> queue;
     bool stop = false, started = false;
     std::string error;
+    long slot_waits = 0;  // acquire() calls that found their slot still on its way to disk (fs_get_int "dump_slot_waits")
 
     // floats_per_slot = 5 fields x the planes this rank writes
     int init(int dev_id, long floats_per_slot, FILE** files, std::string* err)
@@ -60,20 +68,28 @@ struct FrameWriter {
             }
             busy[k] = false;
         }
-        stop = false;
-        error.clear();
+        stop = false;                 // (an error the old thread left stays for the acquire() that follows)
         th = std::thread([this] { run(); });
         started = true;
         return 0;
+    }
+
+    // hands an error the writer kept to the caller, once
+    int take_error(std::string* err)
+    {
+        if (error.empty()) return 0;
+        *err = error;
+        error.clear();
+        return -1;
     }
 
     // blocks until staging slot `k` is free again; returns -1 if the writer failed earlier
     int acquire(int k, std::string* err)
     {
         std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return !busy[k] || !error.empty(); });
-        if (!error.empty()) { *err = error; return -1; }
-        return 0;
+        if (busy[k]) ++slot_waits;
+        cv.wait(lk, [&] { return !busy[k]; });
+        return take_error(err);
     }
 
     // the caller has queued the pack kernels of slot k on `compute`; ship the frame
@@ -94,15 +110,15 @@ struct FrameWriter {
         return 0;
     }
 
+    // waits until every submitted frame has been written, then flushes the files; returns -1 if any of that failed
     int flush(std::string* err)
     {
         if (!started) return 0;
         std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return (queue.empty() && !busy[0] && !busy[1]) || !error.empty(); });
-        if (!error.empty()) { *err = error; return -1; }
-        for (int k = 0; k < NFILE; ++k)
-            if (fp && fp[k]) fflush(fp[k]);
-        return 0;
+        cv.wait(lk, [&] { return queue.empty() && !busy[0] && !busy[1]; });
+        std::string ferr;
+        if (flush_files(fp, &ferr) && error.empty()) error = ferr;
+        return take_error(err);
     }
 
     void shutdown()
@@ -142,27 +158,11 @@ struct FrameWriter {
             }
             std::string fail;
             if (hipEventSynchronize(copied[job.slot]) != hipSuccess) fail = "frame copy failed";
-            if (fail.empty()) {
-                // the five files are independent: one short-lived thread each (a single fwrite
-                // stream into the page cache tops out near 6 GB/s, far below the PCIe copy)
-                const char* errs[NFILE] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-                std::thread workers[NFILE];
-                for (int k = 0; k < NFILE; ++k)
-                    workers[k] = std::thread([&, k] {
-                        if (job.offset >= 0 && fseek(fp[k], job.offset, SEEK_SET) != 0) errs[k] = "fseek failed";
-                        else if (fwrite(host[job.slot] + (size_t)k * job.nloc, sizeof(float), (size_t)job.nloc, fp[k]) !=
-                                 (size_t)job.nloc)
-                            errs[k] = "short write to a frame dump file";
-                    });
-                for (int k = 0; k < NFILE; ++k) {
-                    workers[k].join();
-                    if (errs[k] && fail.empty()) fail = errs[k];
-                }
-            }
+            if (fail.empty()) write_frame(fp, host[job.slot], job.nloc, job.offset, &fail);
             {
                 std::lock_guard<std::mutex> lk(mu);
                 busy[job.slot] = false;
-                if (!fail.empty()) error = fail;
+                if (!fail.empty() && error.empty()) error = fail;
             }
             cv.notify_all();
         }

@@ -284,7 +284,8 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(GridDesc g, const T*
                                                              int zhi)
 {
     const long rows = (long)(g.H + 2) * (zhi - zlo + 1);
-    double s = 0.0, mn = 1e300, mx = -1e300;
+    // the extremes start from the infinities: a field that is +Inf everywhere, or above any finite start, has itself as minimum
+    double s = 0.0, mn = (double)INFINITY, mx = -(double)INFINITY;
     for (long r = blockIdx.x; r < rows; r += gridDim.x) {
         int y = (int)(r % (g.H + 2)), z = zlo + (int)(r / (g.H + 2));
         for (int x = threadIdx.x; x <= g.W + 1; x += blockDim.x) {
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(GridDesc g, const T*
 __global__ void stats_final_kernel(const double* part, int n, double* out3)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double s = 0.0, mn = 1e300, mx = -1e300;
+    double s = 0.0, mn = (double)INFINITY, mx = -(double)INFINITY;
     for (int i = 0; i < n; ++i) {
         s += part[3 * i];
         mn = fmin(mn, part[3 * i + 1]);

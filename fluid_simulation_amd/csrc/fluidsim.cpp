@@ -1676,6 +1676,17 @@ fs_sim* fs_create(int w, int h, int d, int iter, int speed, float dt, float diff
     return s;
 }
 
+// Waits for the frame writer, flushes and closes the five dump files; the next dump opens them anew.  Returns 0, or -1 with
+// the first thing that went wrong in *err (a frame that did not reach its file); the files are closed in either case.
+static int close_dumps(fs_sim* s, std::string* err)
+{
+    int rc = s->writer.flush(err);
+    std::string cerr;
+    if (fs::close_files(s->dump_fp, &cerr) && !rc) { *err = cerr; rc = -1; }
+    s->dump_open = false;
+    return rc;
+}
+
 int fs_destroy(fs_sim* s)
 {
     if (!s) return FS_OK;
@@ -1685,11 +1696,9 @@ int fs_destroy(fs_sim* s)
     for (hipEvent_t ev : s->event_pool) hipEventDestroy(ev);
     {
         std::string werr;
-        s->writer.flush(&werr);
+        close_dumps(s, &werr);
         s->writer.shutdown();
     }
-    for (int k = 0; k < 5; ++k)
-        if (s->dump_fp[k]) fclose(s->dump_fp[k]);
     if (s->comm.active()) hipDeviceSynchronize();   // the communication stream too
     s->comm.release_buffers();       // FSIPC: collective; no peer maps (or still writes) this rank's arrays once it returns
     delete s->eng;
@@ -1741,7 +1750,13 @@ int fs_set_option(fs_sim* s, const char* key, const char* value)
         if (!(om > 0.0f && om < 2.0f)) return fail(FS_EINVAL, "sor_omega must lie in (0, 2)");
         s->omega = om;
     } else if (k == "dump_dir") {
+        // another directory: the files of the old one are finished and closed, the next dump opens the new ones.  The
+        // change is made even if that reports a frame that did not reach the old files (FS_EIO, once)
+        const bool moved = s->dump_open && v != s->dump_dir;
+        const std::string old = s->dump_dir;
         s->dump_dir = v;
+        std::string werr;
+        if (moved && close_dumps(s, &werr)) return fail(FS_EIO, "frame writer: %s (%s)", werr.c_str(), old.c_str());
     } else if (k == "dump_every") {
         s->dump_every = atoi(value);
     } else if (k == "voxel_seed") {
@@ -1978,6 +1993,7 @@ int fs_get_int(fs_sim* s, const char* name, int* out)
     else if (n == "reach_wait_us") *out = (int)(s->reach_wait_ms * 1e3);  // host time spent blocked in them
     else if (n == "reach_hidden") *out = (int)s->n_reach_hidden;          // advections queued while the device still had the work placed before them ...
     else if (n == "reach_exposed") *out = (int)s->n_reach_exposed;        // ... and after it had run dry (a bubble on the device)
+    else if (n == "dump_slot_waits") *out = (int)std::min<long>(s->writer.slot_waits, 2147483647L);   // frame dumps that found their staging slot still being written
     else if (n == "probe_count") *out = (int)(s->probes.size() / 3);      // probes set by fs_set_probes
     else if (n == "body_count" || n == "body_components") {               // bodies / components of the labelling (made now if obs changed)
         int b = 0, c = 0;
@@ -2127,14 +2143,13 @@ int fs_run(fs_sim* s)
     ENGINE_OR_RETURN(s);
     const bool talk = !s->quiet && (!s->comm.active() || s->comm.rank == 0);
     if (talk) printf("starting 3-D simulation: %dx%dx%d  steps = %d\n", s->W, s->H, s->D, s->iter);   // simulation.cpp:51-53
-    // run() re-opens (truncates) the five files (simulation.cpp:56-60)
+    // run() re-opens (truncates) the five files (simulation.cpp:56-60).  Whatever the frames dumped since the last run
+    // still owe -- a failed write, flush or close -- is reported here, once: the files are closed either way, so the call
+    // that follows starts clean
     {
         std::string werr;
-        if (s->writer.flush(&werr)) return fail(FS_EIO, "frame writer: %s", werr.c_str());
+        if (close_dumps(s, &werr)) return fail(FS_EIO, "frame writer: %s", werr.c_str());
     }
-    for (int k = 0; k < 5; ++k)
-        if (s->dump_fp[k]) { fclose(s->dump_fp[k]); s->dump_fp[k] = nullptr; }
-    s->dump_open = false;
     s->in_run = true;
     s->step_no = 0;
     int rc = FS_OK;
@@ -2153,9 +2168,14 @@ int fs_run(fs_sim* s)
     s->in_run = false;
     {
         std::string werr;
-        if (s->writer.flush(&werr) && !rc) rc = fail(FS_EIO, "frame writer: %s", werr.c_str());
+        if (s->writer.flush(&werr) && !rc) rc = fail(FS_EIO, "frame writer: %s (%s)", werr.c_str(), s->dump_dir.c_str());
     }
-    if (rc) return rc;
+    if (rc) {
+        // a failed run leaves no files open and no error behind (the writer is drained: the flush above waited for it)
+        std::string werr;
+        close_dumps(s, &werr);
+        return rc;
+    }
     static const int which[4] = { FS_DENS, FS_VX, FS_VY, FS_VZ };
     static const char* const label[4] = { "density ", "velocity x", "velocity y", "velocity z" };
     if (talk) printf("\n--- statistics -------------------------------------------------\n");   // :81

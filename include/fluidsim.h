@@ -194,7 +194,7 @@ int fs_destroy(fs_sim* s);
  * "reach_waits_blocked" "reach_wait_us" "reach_hidden" "reach_exposed", and "flow_stats_samples" and "probe_count", and
  * "tracer_capacity" "tracer_count" "tracer_seeded" "tracer_emitters" (see the tracer particles below), and
  * "confinement_passes" (confinement passes done so far, inside steps and by fs_confine_vorticity), and "monitor_log"
- * "monitor_every" "monitor_stations" (the number of stations set).
+ * "monitor_every" "monitor_stations" (the number of stations set), and "dump_slot_waits" (see fs_dump_frame).
  */
 int fs_set_option(fs_sim* s, const char* key, const char* value);
 
@@ -249,8 +249,13 @@ int fs_advect(fs_sim* s, int b, int field, int prev);                           
 /* ---- data access ---------------------------------------------------------------- */
 
 /* Copies one field in the reference's own layout: padded (w+2)(h+2)(d+2), x fastest
- * (simulation.h:9).  elem_size selects the host element type (4 = float, 8 = double);
- * conversion happens on the device.  n is the element count of the host buffer.
+ * (simulation.h:9).  elem_size selects the host element type (4 = float, 8 = double,
+ * 1 = uint8_t); conversion happens on the device.  n is the element count of the host buffer.
+ * A transfer that keeps the format keeps every bit, NaN payloads included.  double -> float is IEEE round-to-nearest-even
+ * (float subnormals kept, overflow to infinity), float -> double is exact; a NaN that is converted stays a NaN, its sign and
+ * payload are not defined.  elem_size 1 is defined only for values v with 0 <= v < 256 (fs_get_field truncates toward zero,
+ * fs_set_field stores the byte's value); what another value, an infinity or a NaN becomes is not defined.
+ * A wrong n, another elem_size or a null buffer is FS_EINVAL and copies nothing.
  * The twelve edges of the padded box (cells that are ghosts in two or three directions) are written by no pass of the
  * reference, so they are 0 in every state a run reaches; a caller of fs_set_field keeps them 0.  Passes here do not
  * preserve other values there (a solve leaves its result in another array, row-wise kernels store whole 16-byte groups
@@ -259,10 +264,17 @@ int fs_get_field(fs_sim* s, int which, void* dst, size_t n, int elem_size);
 int fs_set_field(fs_sim* s, int which, const void* src, size_t n, int elem_size);
 size_t fs_padded_size(fs_sim* s);   /* Simulation::size  simulation.cpp:35 */
 
-/* Append one frame to <dump_dir>/{data,obs,v_x,v_y,v_z}.bin exactly as simulation.cpp:140-148. */
+/* Append one frame to <dump_dir>/{data,obs,v_x,v_y,v_z}.bin exactly as simulation.cpp:140-148.
+ * Write errors: a frame that did not reach its file -- a short write, a failed flush or close, a failed copy -- is FS_EIO
+ * from the first call that meets it: this one, a later fs_step / fs_dump_frame that needs the staging slot, fs_sync, fs_run
+ * (which ends with every frame flushed, so a run that returns FS_OK has written its frames), or fs_set_option "dump_dir".
+ * It is reported once.  A failed fs_run closes its files; fs_run reopens them, and a change of "dump_dir" closes the old
+ * directory's files (the next dump opens the new ones), so the handle is usable again after a full disk.
+ * fs_get_int "dump_slot_waits" counts the dumps that had to wait because their staging slot was still being written. */
 int fs_dump_frame(fs_sim* s);
 
-/* Diagnostics of run(): sum/min/max over the whole padded array (simulation.cpp:73-90). */
+/* Diagnostics of run(): sum/min/max over the whole padded array (simulation.cpp:73-90).  The sum is taken in double (its
+ * order is not defined), min and max ignore NaN (a field without any other value reports +infinity and -infinity). */
 int fs_field_stats(fs_sim* s, int which, double* sum, double* min, double* max);
 
 /* ---- measurement ---------------------------------------------------------------- */

@@ -383,14 +383,39 @@ def test_run_twice_truncates_dumps(F, tmp_path):
 
 
 def test_fs_run_statistics_lines(F, capfd):
-    sim = F.Simulation(8, 6, 5, 100, acc=1, dump_every=0)
-    sim.run()
-    sim.close()
-    out = capfd.readouterr().out
-    assert "starting 3-D simulation: 8x6x5  steps = 100" in out
-    assert "step 100" in out and "density sum = " in out
-    for k in ("density  min", "density  max", "velocity x min", "velocity z max", "simulation finished"):
-        assert k in out
+    """the console contract of run() (simulation.cpp:73-90), labels and numbers: the density sum is std::reduce's sum in the
+    handle's own precision, the extremes are those of the whole padded arrays, all printed with %g; a twin handle that makes
+    the same 100 steps supplies the fields and tests/boundary_model.py the numbers"""
+    import boundary_model as M
+    for precision in ("fp32", "fp64"):
+        capfd.readouterr()
+        sim = F.Simulation(8, 6, 5, 100, acc=1, dump_every=0, precision=precision)
+        sim.addObstacle(3, 3, 2)
+        sim.run()
+        sim.close()
+        out = capfd.readouterr().out
+        assert "starting 3-D simulation: 8x6x5  steps = 100" in out
+        assert "step 100" in out and "density sum = " in out
+        for k in ("density  min", "density  max", "velocity x min", "velocity z max", "simulation finished"):
+            assert k in out
+        twin = F.Simulation(8, 6, 5, 100, acc=1, dump_every=0, quiet=1, precision=precision)
+        twin.addObstacle(3, 3, 2)
+        for _ in range(100):
+            twin.run_one()
+        dens = twin.get(F.DENS)
+        assert dens.dtype == (np.float64 if precision == "fp64" else np.float32)
+        want = ["step 100", "  density sum = %g" % M.reduce_order_sum(dens), "",
+                "--- statistics -------------------------------------------------"]
+        for label, f in (("density ", F.DENS), ("velocity x", F.VX), ("velocity y", F.VY), ("velocity z", F.VZ)):
+            _, lo, hi = M.stats(twin.get(f))
+            assert f == F.VZ or lo < hi                                       # a flow, not zeros
+            want += ["%s min = %g" % (label, lo), "%s max = %g" % (label, hi)]
+        twin.close()
+        lines = out.splitlines()
+        at = lines.index("step 100")
+        assert lines[at:at + len(want)] == want, (precision, lines[at:at + len(want)], want)
+        assert lines[at + len(want)] == "simulation finished"
+        assert float(want[1].split("=")[1]) > 0
 
 
 def test_long_run_stays_bit_identical(F, oracle_mod):
